@@ -19,6 +19,9 @@ N > 1 (one process per GPU; `python bench.py --gpus N` starts the N ranks itself
       RCCL/xGMI, in the accumulator's own type; the sum of step i overlaps the deposits of step i+1.
   --shard snapshots ("weak"): every rank owns its own boxes, no data-path collective (SURVEY S8e level 2).
 value = deposits of all ranks / max-over-ranks time.  Rank 0 prints ONE JSON line.
+A plain run sets up, warms up, times --steps steps and prints that line (its roofline / kernels / parity / e2e /
+cpu_baseline / single_stream / reduce_layout entries are null); --full adds those measurements and checks.
+--dump-outputs DIR writes the maps and counts of the last timed step as .npy files (Layout.dump_outputs).
 """
 import argparse
 import json
@@ -63,12 +66,12 @@ def parse():
     ap.add_argument("--hydro", action="store_true",
                     help="per-particle masses (type 0, massarr = 0: densitymaps.cpp:358-372) instead of one mass per type")
     ap.add_argument("--shard", default="auto", choices=["auto", "snapshots", "files", "steps"],
-                    help="auto: steps (strong scaling: step i is built by rank i % N, whole) when N > 1")
+                    help="auto: steps (strong scaling: step i is built by rank i %% N, whole) when N > 1")
     ap.add_argument("--streams", type=int, default=1,
                     help="snapshots in flight per GPU: consecutive steps alternate between this many handles, each on "
                          "its own HIP stream.  With more than one the job is timed on ONE stream first (`single_stream`; "
                          "the per-kernel durations of `roofline` / `kernels` belong to that run) and `value` is the "
-                         "multi-stream run.  Measured gain of 2 over 1: about 2 %, inside the run-to-run scatter "
+                         "multi-stream run.  Measured gain of 2 over 1: about 2 %%, inside the run-to-run scatter "
                          "(DESIGN.md S5), hence the default of 1")
     ap.add_argument("--gather", default="off", choices=["on", "off"],
                     help="--shard steps: also send every finished map to rank 0 (point to point, overlapped).  Off: the maps "
@@ -95,7 +98,20 @@ def parse():
     ap.add_argument("--e2e", default="auto", choices=["auto", "on", "off"],
                     help="file -> C++ createDensityMaps -> host maps timing (outside the timed region)")
     ap.add_argument("--profile-steps", type=int, default=2)
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps, also run what the headline number does not need: the CPU baseline, "
+                         "the parity leg, the end-to-end leg, the per-kernel profile and roofline, the single-stream run "
+                         "under --streams > 1 and the reduce layouts under N > 1.  Without it their 'auto' means off")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the plane maps and counts of the last timed step to DIR/*.npy")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not a.full:
+        for k in ("cpu", "parity", "e2e", "reduce_layout"):
+            if getattr(a, k) == "auto":
+                setattr(a, k, "off")
+    return a
 
 
 # ------------------------------------------------------------------------------------------------
@@ -300,8 +316,9 @@ def main():
             row.append(buf)
         pos.append(row)
     masses = None
-    if a.hydro:  # one block of per-particle masses, shared by every sub-file (values in (0.5, 1.5) * MASS)
-        masses = (torch.rand(per_file, dtype=torch.float32, device="cuda") + 0.5) * MASS
+    if a.hydro:  # one block of per-particle masses, shared by every sub-file (values in (0.5, 1.5) * MASS), seeded
+        g = torch.Generator(device="cuda").manual_seed(SEED)
+        masses = (torch.rand(per_file, dtype=torch.float32, device="cuda", generator=g) + 0.5) * MASS
     torch.cuda.synchronize()
     gen.close()
 
@@ -467,12 +484,42 @@ def main():
             self.my_dep = my_dep
             return dt, tot_dep, tot_in
 
+        def dump_outputs(self, out_dir):
+            """What the last timed step handed its caller: every lens plane's f32 map and per-type counts, written by the
+            rank holding them (--shard files: the root of the sum).  Maps larger than 32 MiB in all are sampled at a
+            fixed, seeded set of pixels (2^21, the same for every plane); map_sums covers every pixel."""
+            import numpy as np
+            last = a.steps - 1
+            if self.gather_steps:
+                if last % world != rank:
+                    return
+                S = self.handles[(self.own_count - 1) % self.n_handles]
+            elif self.reduce_steps and rank != 0:
+                return
+            else:
+                S = self.handles[last % self.n_handles]
+            maps, counts = [], []
+            for p in range(len(lds)):
+                tot, _, nsel = S.plane_read(p, want_types=False)
+                maps.append(tot.reshape(-1))
+                counts.append(nsel)
+            maps = np.stack(maps)
+            os.makedirs(out_dir, exist_ok=True)
+            np.save(os.path.join(out_dir, "counts.npy"), np.array(counts, np.float64))
+            np.save(os.path.join(out_dir, "map_sums.npy"), maps.sum(axis=1, dtype=np.float64))
+            if maps.nbytes <= 32 << 20:
+                np.save(os.path.join(out_dir, "maps.npy"), maps.reshape(len(lds), a.npix, a.npix))
+            else:
+                idx = np.sort(np.random.default_rng(SEED).choice(npix2, size=1 << 21, replace=False))
+                np.save(os.path.join(out_dir, "maps_sample.npy"), maps[:, idx])
+                np.save(os.path.join(out_dir, "maps_sample_index.npy"), idx.astype(np.float64))
+
     # With several snapshots in flight the kernels of different steps share the GPU and their individual durations say
     # nothing about the kernels themselves.  So the job is timed twice: first on ONE stream (`single_stream`, the number
     # the per-kernel HIP-event durations add up to; the profile and parity phases below run on that layout too), then
-    # with `--streams` snapshots in flight -- that second run is `value`.
+    # with `--streams` snapshots in flight -- that second run is `value`.  (--full only: a plain run times `value` alone.)
     single_stream, Lmain = None, None
-    if a.streams > 1 and not use_dist:
+    if a.streams > 1 and not use_dist and a.full:
         L = Layout(shard, a.reduce_algo, streams=1)
         dt1, dep1, in1 = L.run()
         single_stream = {"value": dep1 / dt1, "ms_per_step": 1e3 * dt1 / a.steps, "n_in_per_s": in1 / dt1, "streams": 1}
@@ -480,52 +527,60 @@ def main():
         L = Layout(shard, a.reduce_algo)
         dt, tot_dep, tot_in = L.run()
         Lmain = L
+        if a.dump_outputs:
+            L.dump_outputs(a.dump_outputs)
     reduce_steps, gather_steps, overlap, gathered = L.reduce_steps, L.gather_steps, L.overlap, L.gather
     algo_mask = L.algo_mask
     n_handles, handles, my_files, my_dep = L.n_handles, L.handles, L.my_files, L.my_dep
     S0 = handles[0]
     step, local_step, drain = L.step, L.local_step, L.drain
 
-    # per-kernel durations, live, with HIP events on the launch stream (a few extra untimed steps)
-    S0.profile_reset()
-    S0.profile_enable(True)
-    for i in range(max(1, a.profile_steps) * n_handles):
+    roofline, kernels = None, None
+    if a.full:
+        # per-kernel durations, live, with HIP events on the launch stream (a few extra untimed steps)
+        S0.profile_reset()
+        S0.profile_enable(True)
+        for i in range(max(1, a.profile_steps) * n_handles):
+            if gather_steps:
+                if i % n_handles == 0:
+                    local_step(i)
+            else:
+                step(i)
+        drain()
+        torch.cuda.synchronize()
+        S0.profile_enable(False)
+        prof = S0.profile_get()
+        dom_name, (dom_n, dom_ms) = max(prof.items(), key=lambda kv: kv[1][1])
+        kernels = {k: {"launches": v[0], "avg_us": 1e3 * v[1] / max(v[0], 1)} for k, v in prof.items()}
+        # algorithmic bytes per launch of the dominant kernel (DESIGN.md "Algorithmic bytes")
+        # (the profiled handle ran max(1, profile_steps) steps; every project_bin launch streams one sub-file)
+        dep_per_step_rank = (my_dep / max(a.steps, 1)) * (len(my_files) / files if reduce_steps else 1.0)
         if gather_steps:
-            if i % n_handles == 0:
-                local_step(i)
+            dep_per_step_rank = my_dep / max(a.steps, 1)
+        if dom_name in ("direct_deposit", "project_bin"):
+            alg_bytes = 12.0 * per_file
+        elif dom_name in ("tile_deposit", "bin_scatter", "bin_sort"):
+            alg_bytes = 8.0 * dep_per_step_rank * max(1, a.profile_steps) / max(dom_n, 1)
         else:
-            step(i)
-    drain()
-    torch.cuda.synchronize()
-    S0.profile_enable(False)
-    prof = S0.profile_get()
-    dom_name, (dom_n, dom_ms) = max(prof.items(), key=lambda kv: kv[1][1])
-    kernels = {k: {"launches": v[0], "avg_us": 1e3 * v[1] / max(v[0], 1)} for k, v in prof.items()}
-    # algorithmic bytes per launch of the dominant kernel (DESIGN.md "Algorithmic bytes")
-    # (the profiled handle ran max(1, profile_steps) steps; every project_bin launch streams one sub-file)
-    dep_per_step_rank = (my_dep / max(a.steps, 1)) * (len(my_files) / files if reduce_steps else 1.0)
-    if gather_steps:
-        dep_per_step_rank = my_dep / max(a.steps, 1)
-    if dom_name in ("direct_deposit", "project_bin"):
-        alg_bytes = 12.0 * per_file
-    elif dom_name in ("tile_deposit", "bin_scatter", "bin_sort"):
-        alg_bytes = 8.0 * dep_per_step_rank * max(1, a.profile_steps) / max(dom_n, 1)
-    else:
-        alg_bytes = 4.0 * a.npix * a.npix
-    achieved = alg_bytes / (1e-3 * dom_ms / max(dom_n, 1))
-    traffic, traffic_step = None, None
-    tpath = os.path.join(ROOT, "profiles", "traffic.json")
-    if os.path.exists(tpath):
-        try:
-            tj = json.load(open(tpath))
-            ent = tj.get(dom_name)
-            if ent and ent.get("workload") == f"{a.side}^3/{a.npix}/{a.mas}/{a.algo}/{a.accum}":
-                traffic = ent.get("hbm_bytes_per_launch")
-            ws = tj.get("whole_step")
-            if ws and ws.get("workload") == f"{a.side}^3/{a.npix}/{a.mas}/{a.algo}/{a.accum}":
-                traffic_step = ws
-        except Exception:
-            traffic = None
+            alg_bytes = 4.0 * a.npix * a.npix
+        achieved = alg_bytes / (1e-3 * dom_ms / max(dom_n, 1))
+        traffic, traffic_step = None, None
+        tpath = os.path.join(ROOT, "profiles", "traffic.json")
+        if os.path.exists(tpath):
+            try:
+                tj = json.load(open(tpath))
+                ent = tj.get(dom_name)
+                if ent and ent.get("workload") == f"{a.side}^3/{a.npix}/{a.mas}/{a.algo}/{a.accum}":
+                    traffic = ent.get("hbm_bytes_per_launch")
+                ws = tj.get("whole_step")
+                if ws and ws.get("workload") == f"{a.side}^3/{a.npix}/{a.mas}/{a.algo}/{a.accum}":
+                    traffic_step = ws
+            except Exception:
+                traffic = None
+        roofline = {"bound": "hbm", "kernel": dom_name, "achieved": achieved / 1e9, "peak": HBM_PEAK / 1e9,
+                    "unit": "GB/s", "frac": achieved / HBM_PEAK, "traffic": traffic,
+                    "alg_bytes_per_launch": alg_bytes, "avg_launch_us": 1e3 * dom_ms / max(dom_n, 1),
+                    "whole_step_traffic": traffic_step}
 
     # ---- max |dpixel| vs ref: sub-file 0 of snapshot 0 through the same configuration, against the oracle's maps
     parity = None
@@ -557,6 +612,8 @@ def main():
         L.close()
         L = Lmain = Layout(shard, a.reduce_algo)
         dt, tot_dep, tot_in = L.run()
+        if a.dump_outputs:
+            L.dump_outputs(a.dump_outputs)
         algo_mask = L.algo_mask
         n_handles = L.n_handles
 
@@ -602,14 +659,11 @@ def main():
             },
             "n_in_per_s": tot_in / dt,
             "hbm_read_roofline_frac_whole_step": 12.0 * tot_in / dt / HBM_PEAK / world,
-            "roofline": {"bound": "hbm", "kernel": dom_name, "achieved": achieved / 1e9, "peak": HBM_PEAK / 1e9,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK, "traffic": traffic,
-                         "alg_bytes_per_launch": alg_bytes, "avg_launch_us": 1e3 * dom_ms / max(dom_n, 1),
-                         "whole_step_traffic": traffic_step},
+            "roofline": roofline,
             "kernels": kernels,
             "kernels_measured": "HIP events on one stream, in extra untimed steps right after the single-stream timed run (with "
                                 "several snapshots in flight the kernels of different steps share the GPU); they add up to "
-                                "single_stream.ms_per_step, or to ms_per_step under --streams 1",
+                                "single_stream.ms_per_step, or to ms_per_step under --streams 1" if a.full else None,
             "single_stream": single_stream,
             "max_rel_dpixel": parity["max_rel_dpixel"] if parity else None,
             "parity": parity,

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -21,8 +22,9 @@ def _bench(args, env=None):
     return json.loads(lines[0])
 
 
-SMALL = ["--side", "128", "--npix", "1024", "--files", "2", "--snapshots", "2", "--steps", "4", "--warmup", "1",
-         "--cpu-baseline", "off", "--parity", "off", "--e2e", "off", "--profile-steps", "1"]
+PLAIN = ["--side", "128", "--npix", "1024", "--files", "2", "--snapshots", "2", "--steps", "4", "--warmup", "1"]
+# the roofline, the single-stream run and the reduce layouts are measured under --full only
+SMALL = PLAIN + ["--full", "--cpu-baseline", "off", "--parity", "off", "--e2e", "off", "--profile-steps", "1"]
 
 
 def test_one_gpu_line_has_the_contract_fields():
@@ -61,3 +63,35 @@ def test_a_stuck_secondary_layout_cannot_take_the_main_number_down():
                env={"SLICER_BENCH_FORCE_DIST": "1", "MASTER_PORT": "29534"})
     assert d["value"] > 0 and d["config"]["shard"] == "steps"
     assert "cut off" in d["config"]["reduce_layout"]["error"]
+
+
+def test_plain_line_times_the_steps_alone_and_dumps_the_last_step(tmp_path):
+    d = _bench(PLAIN + ["--steps", "3", "--dump-outputs", str(tmp_path)])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["value"] > 0 and d["ms_per_step"] > 0 and d["dtype"] == "f32"
+    for k in ("roofline", "kernels", "parity", "e2e", "cpu_baseline", "single_stream"):
+        assert d[k] is None, k
+    maps, counts, sums = (np.load(tmp_path / f"{n}.npy") for n in ("maps", "counts", "map_sums"))
+    assert maps.dtype == np.float32 and maps.shape == (4, 1024, 1024)
+    assert counts.dtype == np.float64 and counts.shape == (4, 6) and counts[:, 1].sum() > 0
+    assert np.allclose(sums, maps.sum(axis=(1, 2), dtype=np.float64), rtol=1e-12)
+    # the map holds the mass of the step's deposits, less what TSC spreads past the edge from the one-pixel margin
+    mass = counts[:, 1] * 0.0123
+    assert np.all(sums <= mass * (1 + 1e-5)) and np.all(sums >= 0.98 * mass)
+
+
+def test_dumped_outputs_repeat_with_the_same_arguments(tmp_path):
+    """4096^2 maps are too large to dump whole: a fixed sample of pixels, the same in both runs."""
+    args = ["--side", "128", "--npix", "4096", "--files", "2", "--snapshots", "2", "--steps", "2", "--warmup", "1"]
+    for run in ("a", "b"):
+        _bench(args + ["--dump-outputs", str(tmp_path / run)])
+    a, b = ({n: np.load(tmp_path / r / f"{n}.npy") for n in ("counts", "map_sums", "maps_sample", "maps_sample_index")}
+            for r in ("a", "b"))
+    assert not (tmp_path / "a" / "maps.npy").exists()
+    assert a["maps_sample"].dtype == np.float32 and a["maps_sample"].shape == (4, 1 << 21)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert np.array_equal(a["counts"], b["counts"]) and np.array_equal(a["maps_sample_index"], b["maps_sample_index"])
+    # f32 atomics add in whatever order the hardware serves them: the last bits may differ, nothing more
+    assert np.allclose(a["maps_sample"], b["maps_sample"], rtol=1e-5, atol=1e-9)
+    assert np.allclose(a["map_sums"], b["map_sums"], rtol=1e-6)

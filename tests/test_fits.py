@@ -1,6 +1,6 @@
 """The plane FITS writer against libcfitsio itself (the library under the reference's CCfits calls,
-densitymaps.cpp:549-583): whole files must be byte-identical.  Runs without a GPU."""
-import ctypes as C
+densitymaps.cpp:549-583): whole files must be byte-identical.  Runs without a GPU.  The files libcfitsio writes for
+these inputs are stored under tests/golden/fits/ (tests/golden/make_fits_golden.py)."""
 import os
 
 import numpy as np
@@ -9,29 +9,15 @@ import pytest
 from slicer_amd import fits
 from slicer_amd.api import InputParams, Lens
 
-CFITSIO = "/opt/conda/lib/libcfitsio.so"
-pytestmark = pytest.mark.skipif(not os.path.exists(CFITSIO), reason="libcfitsio not present")
+GOLDEN_FITS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "fits")
+ALL_TYPES_NPIX = [8, 27, 64]
 
 
-def cfitsio_write(path, img, keys):
-    """The call sequence CCfits issues for FITS(name, FLOAT_IMG, 2, naxes); pHDU().write(...); addKey(...)*"""
-    L = C.CDLL(CFITSIO)
-    f, st = C.c_void_p(), C.c_int(0)
-    L.ffinit(C.byref(f), path.encode(), C.byref(st))
-    naxes = (C.c_long * 2)(img.shape[1], img.shape[0])
-    L.ffcrim(f, -32, 2, naxes, C.byref(st))
-    flat = np.ascontiguousarray(img, np.float32).reshape(-1)
-    L.ffppr(f, 42, C.c_longlong(1), C.c_longlong(flat.size), flat.ctypes.data_as(C.c_void_p), C.byref(st))
-    for name, val, comm in keys:
-        if isinstance(val, int):
-            v = C.c_int(val)
-            L.ffuky(f, 31, name.encode(), C.byref(v), comm.encode(), C.byref(st))
-        else:
-            v = C.c_double(val)
-            L.ffuky(f, 82, name.encode(), C.byref(v), comm.encode(), C.byref(st))
-    L.ffclos(f, C.byref(st))
-    assert st.value == 0
-    return open(path, "rb").read()
+def cfitsio_bytes(name):
+    """What libcfitsio wrote for the same image and keys, through the call sequence CCfits issues for
+    FITS(name, FLOAT_IMG, 2, naxes); pHDU().write(...); addKey(...)*"""
+    with open(os.path.join(GOLDEN_FITS, name), "rb") as fh:
+        return fh.read()
 
 
 def params(tmp_path, partinplanes=False):
@@ -39,31 +25,41 @@ def params(tmp_path, partinplanes=False):
                        simulation="sim", suffix="test", snpix="16")
 
 
-@pytest.mark.parametrize("npix", [8, 27, 64])
-def test_all_types_file_is_byte_identical_to_cfitsio(tmp_path, npix):
+def all_types_case(npix):
+    """Image, header and counts of the all-types plane file, and the keys fits.plane_keys makes of them."""
     rng = np.random.default_rng(npix)
     img = rng.uniform(0, 3, (npix, npix)).astype(np.float32)
     img[0, 1] = 0.0
+    hdr = dict(h=0.6774, om0=0.3089, oml=0.6911, massarr=[0.0, 0.0123456789, 0, 1e-30, 2.5e10, 0.5])
+    ntot = [0, 123456, 0, 7, 0, 2147483647]
+    keys = fits.plane_keys(params(""), 0.6774, 0.3089, 0.6911, hdr["massarr"], 123.456789, 223.4, 0.512345678901234567,
+                           ntot)
+    return img, hdr, ntot, keys
+
+
+def edge_keys():
+    vals = [0.0, 1.0, -1.0, 0.1, 1e-30, -2.5e300, 123456789012345678.0, 1e15, 1e16, 123456.5, 1 / 3, 2 / 3 * 1e-7,
+            9.99999999999999e22, 5e-324]
+    return [("K%d" % i, v, "c") for i, v in enumerate(vals)] + [("LONGKEYNAME%d" % i, v, " ") for i, v in enumerate(vals)]
+
+
+@pytest.mark.parametrize("npix", ALL_TYPES_NPIX)
+def test_all_types_file_is_byte_identical_to_cfitsio(tmp_path, npix):
+    img, hdr, ntot, _ = all_types_case(npix)
     p = params(tmp_path)
     p.npix = npix
     lens = Lens(nplanes=1, ld=[123.456789], ld2=[223.4])
-    hdr = dict(h=0.6774, om0=0.3089, oml=0.6911, massarr=[0.0, 0.0123456789, 0, 1e-30, 2.5e10, 0.5])
-    ntot = [0, 123456, 0, 7, 0, 2147483647]
     out = fits.writeMaps(p, hdr, lens, 0, 0.512345678901234567, "007", "16", img, None, ntot, 0)
     assert out == [fits.fileOutput(p, "007")] and out[0].endswith("sim.007.plane_16_test.fits")
-    keys = fits.plane_keys(p, 0.6774, 0.3089, 0.6911, hdr["massarr"], 123.456789, 223.4, 0.512345678901234567, ntot)
-    ref = cfitsio_write(str(tmp_path / "ref.fits"), img, keys)
+    ref = cfitsio_bytes(f"all_types_{npix}.fits")
     got = open(out[0], "rb").read()
     assert len(got) % 2880 == 0 and got == ref
 
 
 def test_double_formatting_edge_cases_match_cfitsio(tmp_path):
-    vals = [0.0, 1.0, -1.0, 0.1, 1e-30, -2.5e300, 123456789012345678.0, 1e15, 1e16, 123456.5, 1 / 3, 2 / 3 * 1e-7,
-            9.99999999999999e22, 5e-324]
-    keys = [("K%d" % i, v, "c") for i, v in enumerate(vals)] + [("LONGKEYNAME%d" % i, v, " ") for i, v in enumerate(vals)]
     img = np.zeros((4, 4), np.float32)
-    ref = cfitsio_write(str(tmp_path / "ref.fits"), img, keys)
-    fits.write_image(str(tmp_path / "mine.fits"), img, keys)
+    ref = cfitsio_bytes("double_edge_cases.fits")
+    fits.write_image(str(tmp_path / "mine.fits"), img, edge_keys())
     assert open(str(tmp_path / "mine.fits"), "rb").read() == ref
 
 
