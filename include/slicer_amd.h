@@ -297,6 +297,40 @@ int slicer_debug_box_quotient(slicer_handle h, double box, uint32_t *n_bad, uint
  * the IEEE division, ~1 ms, run once per npix and handle -- found no mismatch.  n_bad = mismatches (0 expected). */
 int slicer_debug_dl_quotient(slicer_handle h, int32_t npix, uint32_t *n_bad, uint32_t *examples8);
 
+/* ---- Born-approximation convergence (kappa) maps ----
+ * Weights, host only (no GPU): plane p has comoving edges ld[p] < ld2[p] (Mpc/h) and snapshot redshift zsnap[p]; the
+ * background is flat w0waCDM with H0 = 100.  coeff[s * n_planes + p] = c_sp, the factor of (m_p - mean m_p) in
+ * kappa_s = sum_p c_sp (m_p - mean m_p), m_p in 1e10 Msun/h per pixel; 0 for planes with z(ld2[p]) > zs[s] + 1e-4.
+ * zs = NULL: the source redshifts are z(ld2[p]) of every plane (n_sources must equal n_planes).  growth = 0: no growth
+ * correction D+(zl_p) / D+(zsnap[p]).  zlo, zup, zl, chil (n_planes each, any of them NULL): the edge redshifts, the
+ * effective lens redshift and its comoving distance.  A curved background (|1 - omega_m - omega_lambda| > 1e-5) and
+ * physical = 1 (a map size per plane) return SLICER_ERR_UNSUPPORTED; messages through slicer_last_error(NULL). */
+int slicer_lensing_weights(double omega_m, double omega_lambda, double w0, double wa, double fov_deg, int32_t npix,
+                           int32_t growth, int32_t physical, int32_t n_planes, const double *ld, const double *ld2,
+                           const double *zsnap, int32_t n_sources, const double *zs, double *coeff, double *zlo,
+                           double *zup, double *zl, double *chil);
+
+/* Device accumulator of n_sources kappa maps of npix^2 pixels, on the device and stream of h (create it after any
+ * slicer_set_stream; destroy it before h).  Every call is enqueued on that stream with no host synchronisation, except
+ * _plane_means and _read, which wait for it.
+ *   slicer_kappa_add       n_maps (1..SLICER_MAX_PLANES) device f32 maps, e.g. slicer_plane_device_maps of a finalized
+ *                          pass; coeff[m * n_sources + s] = c_sm (host memory, read before the call returns).  One read
+ *                          of every map: A_s += sum_m c_sm m_m in f64, and the maps' f64 pixel sums -> their means.
+ *   slicer_kappa_plane_means   the means of the first min(max, maps added) maps, in the order they were added
+ *   slicer_kappa_finalize  kappa_s = A_s - sum_m c_sm mean_m, rounded once to f32; more maps may be added afterwards
+ *                          (finalize again)
+ *   slicer_kappa_device_map / _read    kappa_s of the last finalize (SLICER_ERR_STATE if maps were added after it)
+ * The same call sequence gives bitwise the same maps.  The accumulators take n_sources * npix^2 * 12 bytes
+ * (SLICER_ERR_NOMEM). */
+typedef struct slicer_kappa_s *slicer_kappa_handle;
+int slicer_kappa_create(slicer_handle h, int32_t npix, int32_t n_sources, slicer_kappa_handle *out);
+int slicer_kappa_add(slicer_kappa_handle kh, int32_t n_maps, const float *const *d_maps, const double *coeff);
+int slicer_kappa_plane_means(slicer_kappa_handle kh, double *out, int32_t max);
+int slicer_kappa_finalize(slicer_kappa_handle kh);
+int slicer_kappa_device_map(slicer_kappa_handle kh, int32_t s, float **d_map);
+int slicer_kappa_read(slicer_kappa_handle kh, int32_t s, float *host);
+int slicer_kappa_destroy(slicer_kappa_handle kh);
+
 /* per-kernel HIP-event timing (off by default; adds two event records per launch) */
 int slicer_profile_enable(slicer_handle h, int on);
 int slicer_profile_reset(slicer_handle h);

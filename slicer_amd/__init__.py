@@ -7,4 +7,6 @@ from . import _lib, gadget, synth  # noqa: F401
 from .api import (ACC_F32, ACC_F64, ACC_FIXED64, ALGO_AUTO, ALGO_BINNED, ALGO_DIRECT, ELEM_F32, ELEM_F64,  # noqa: F401
                   ELEM_FIXED64, MAS_NGP, MAS_TSC, InputParams, Lens, Random, Slicer, SlicerError, createDensityMaps)
 
+from .lensing import Kappa, plane_weights  # noqa: F401
+
 __version__ = "0.2.0"

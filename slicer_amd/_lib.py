@@ -79,6 +79,16 @@ SYMBOLS = {
     "slicer_debug_box_quotient": (C.c_int, [_H, C.c_double, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "slicer_debug_dl_quotient": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "slicer_debug_math": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "slicer_lensing_weights": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32,
+                                         C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "slicer_kappa_create": (C.c_int, [_H, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "slicer_kappa_add": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_void_p), C.c_void_p]),
+    "slicer_kappa_plane_means": (C.c_int, [_H, C.c_void_p, C.c_int32]),
+    "slicer_kappa_finalize": (C.c_int, [_H]),
+    "slicer_kappa_device_map": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_void_p)]),
+    "slicer_kappa_read": (C.c_int, [_H, C.c_int32, C.c_void_p]),
+    "slicer_kappa_destroy": (C.c_int, [_H]),
     "slicer_profile_enable": (C.c_int, [_H, C.c_int]),
     "slicer_profile_reset": (C.c_int, [_H]),
     "slicer_profile_get": (C.c_int, [_H, C.POINTER(KernelTime), C.c_int, C.POINTER(C.c_int)]),

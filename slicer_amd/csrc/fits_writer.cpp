@@ -3,6 +3,7 @@
 #include <sys/stat.h>
 
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <iostream>
 #include <stdexcept>
@@ -89,6 +90,42 @@ bool fits_write_image(const std::string &path, const float *image, int npix, con
     bool ok = fwrite(hdr.data(), 1, hdr.size(), f) == hdr.size() && fwrite(data.data(), 1, data.size(), f) == data.size();
     ok = (fclose(f) == 0) && ok;
     return ok;
+}
+
+bool fits_read_image(const std::string &path, int npix, float *image)
+{
+    FILE *f = fopen(path.c_str(), "rb");
+    if (!f)
+        return false;
+    int bitpix = 0, naxis1 = -1, naxis2 = -1;
+    bool end = false;
+    char block[2880];
+    while (!end && fread(block, 1, sizeof block, f) == sizeof block) {
+        for (int c = 0; c < 36 && !end; c++) {
+            const std::string card(block + 80 * c, 80);
+            const std::string key = card.substr(0, 8);
+            if (key == "END     ")
+                end = true;
+            else if (card[8] == '=' && key == "BITPIX  ")
+                bitpix = atoi(card.c_str() + 10);
+            else if (card[8] == '=' && key == "NAXIS1  ")
+                naxis1 = atoi(card.c_str() + 10);
+            else if (card[8] == '=' && key == "NAXIS2  ")
+                naxis2 = atoi(card.c_str() + 10);
+        }
+    }
+    const size_t n = (size_t)npix * (size_t)npix;
+    std::vector<unsigned char> data(n * 4);
+    const bool ok = end && bitpix == -32 && naxis1 == npix && naxis2 == npix && fread(data.data(), 1, n * 4, f) == n * 4;
+    fclose(f);
+    if (!ok)
+        return false;
+    for (size_t i = 0; i < n; i++) {  // big-endian IEEE f32
+        const uint32_t u = (uint32_t)data[4 * i] << 24 | (uint32_t)data[4 * i + 1] << 16 | (uint32_t)data[4 * i + 2] << 8 |
+                           (uint32_t)data[4 * i + 3];
+        memcpy(&image[i], &u, 4);
+    }
+    return true;
 }
 
 }  // namespace slicer_amd

@@ -26,4 +26,7 @@ struct FitsKey {
 std::string fits_card(const FitsKey &k);
 // returns false if the file exists or cannot be written
 bool fits_write_image(const std::string &path, const float *image, int npix, const FitsKey *keys, int nkeys);
+// Reads back what fits_write_image writes (BITPIX -32, NAXIS1 = NAXIS2 = npix) into image[npix * npix]; false if the
+// file is missing, short or of another shape.
+bool fits_read_image(const std::string &path, int npix, float *image);
 }  // namespace slicer_amd

@@ -1453,6 +1453,12 @@ int slicer_version(void) { return SLICER_AMD_VERSION; }
 
 const char *slicer_last_error(slicer_handle h) { return h ? h->err.c_str() : g_null_err.c_str(); }
 
+// slicer_lensing*.{hip,cpp} report their errors through the same slicer_last_error (not exported)
+__attribute__((visibility("hidden"))) int slicer_internal_fail(slicer_handle h, int code, const char *msg)
+{
+    return fail(h, code, "%s", msg);
+}
+
 int slicer_create(int device, uint64_t max_chunk, slicer_handle *out)
 {
     if (!out)

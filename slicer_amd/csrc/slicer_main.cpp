@@ -10,6 +10,9 @@
 //     over the snapshot (the reference re-reads and re-transforms it for each of them);   --single-plane disables
 //   * nparttype* keys carry the real selected counts (the reference writes 0: densitymaps.cpp:497), which also makes
 //     partinplanes runs write their per-type files;                                      --reference-counts disables
+//   * --kappa all|z1,z2,... adds Born convergence maps, one FITS per source redshift, accumulated on device 0 from the
+//     finalized total maps of every pass (the reference's post-processing script Lens/kslicer.py);
+//     --kappa-no-growth drops its linear-growth correction.  Without --kappa the run is unchanged.
 //   * SubFind / halo-catalogue mode (npix == 0) is not supported; with snopt > 0 and several devices every rank thread
 //     draws from its own copy of the libc stream, like the reference's MPI ranks
 //     (the thinning deviates come from the process-global libc rand() stream, densitymaps.cpp:387-397: the reference's
@@ -108,6 +111,28 @@ int fill_from_file(void *user, float *dst_pos, float *dst_mass, uint64_t first, 
     if (dst_mass)
         std::copy(s->mass + first, s->mass + first + count, dst_mass);
     return 0;
+}
+
+// "all" -> empty list with all = true; "0.5,1" -> the redshifts; false on anything else
+bool parse_sources(const string &spec, bool &all, vector<double> &zs)
+{
+    all = spec == "all";
+    if (all)
+        return true;
+    size_t i = 0;
+    while (i <= spec.size()) {
+        size_t j = spec.find(',', i);
+        if (j == string::npos)
+            j = spec.size();
+        const string tok = spec.substr(i, j - i);
+        char *end = nullptr;
+        const double z = strtod(tok.c_str(), &end);
+        if (tok.empty() || *end != '\0' || !(z >= 0))
+            return false;
+        zs.push_back(z);
+        i = j + 1;
+    }
+    return !zs.empty();
 }
 
 // "0-3", "0,2,5", "1": HIP device ordinals, one rank each
@@ -276,7 +301,8 @@ int host_plane_reduce(vector<Rank> &ranks, int npix, int n_planes)
 
 int main(int argc, char **argv)
 {
-    string inifile, plan_path, devices_spec, reduce_mode = "rccl", reduce_algo = "rooted";
+    string inifile, plan_path, devices_spec, reduce_mode = "rccl", reduce_algo = "rooted", kappa_spec;
+    bool kappa_growth = true;
     int device = 0, mas = SLICER_MAS_TSC, accum = SLICER_ACC_F32;
     bool plan_only = false, single_plane = false, reference_counts = false, replication = false;
     for (int i = 1; i < argc; i++) {
@@ -293,7 +319,9 @@ int main(int argc, char **argv)
         else if (a == "--dump-plan" && i + 1 < argc) plan_path = argv[++i];
         else if (a == "--single-plane") single_plane = true;
         else if (a == "--reference-counts") reference_counts = true;
-        else if (a == "--replication") replication = true;  // -DUSE_REPLICATION (ReplicationOnPerpendicularPlane)
+        else if (a == "--replication") replication = true;
+        else if (a == "--kappa" && i + 1 < argc) kappa_spec = argv[++i];  // all | z1,z2,...
+        else if (a == "--kappa-no-growth") kappa_growth = false;  // -DUSE_REPLICATION (ReplicationOnPerpendicularPlane)
         else if (inifile.empty()) inifile = a;
         else {
             cerr << "unknown argument " << a << endl;
@@ -364,6 +392,29 @@ int main(int argc, char **argv)
         dump_plan(plan_path, p, lens, random, snapbox, fovradiants);
     if (plan_only)
         return 0;
+
+    // Born convergence maps: weights c[s][p] for every plane of the cone (slicer_lensing_weights), before any GPU work
+    bool kappa_all = false;
+    vector<double> kappa_zs, kappa_c;
+    if (!kappa_spec.empty()) {
+        if (!parse_sources(kappa_spec, kappa_all, kappa_zs)) {
+            cerr << "bad --kappa (all, or a comma-separated list of source redshifts)" << endl;
+            return 2;
+        }
+        const int P = lens.nplanes;
+        vector<double> zup(P);
+        const int S = kappa_all ? P : (int)kappa_zs.size();
+        kappa_c.assign((size_t)S * P, 0.0);
+        if (slicer_lensing_weights(simdata.om0, simdata.oml, p.w, 0.0, p.fov, p.npix, kappa_growth, p.physical, P,
+                                   lens.ld.data(), lens.ld2.data(), lens.zfromsnap.data(), S,
+                                   kappa_all ? nullptr : kappa_zs.data(), kappa_c.data(), nullptr, zup.data(), nullptr,
+                                   nullptr) != SLICER_OK) {
+            cerr << "slicer_amd: --kappa: " << slicer_last_error(nullptr) << endl;
+            return 1;
+        }
+        if (kappa_all)
+            kappa_zs = zup;
+    }
     // (snopt > 0: thinning consumes libc rand() plane by plane, densitymaps.cpp:387-397.  A pass over several planes
     // keeps that order -- the library replays its chunks plane-major when the pass ends -- so the planes of a box
     // replication still share one read of the snapshot.)
@@ -419,6 +470,63 @@ int main(int argc, char **argv)
             ranks[r].comm = comms[r];
     }
     slicer_handle h = ranks[0].h;  // device 0 of the list is the root: it ends up with the sums and writes the maps
+    const int n_kappa = (int)kappa_zs.size();
+    slicer_kappa_handle kh = nullptr;
+    if (n_kappa && slicer_kappa_create(h, p.npix, n_kappa, &kh) != SLICER_OK) {
+        cerr << "slicer_amd: --kappa: " << slicer_last_error(h) << endl;
+        return 1;
+    }
+    // The planes isnap .. iend-1 of one pass go into the kappa maps as ONE batch whether they were deposited now (their
+    // finalized maps on device 0, plane k of `todo`) or read back from the files a previous run left (resume): the
+    // batches, and with them the roundings, are the same in both cases.
+    vector<float *> kappa_upload;  // device buffers for planes read back from their files
+    auto kappa_add_pass = [&](int i0, int i1, const vector<int> &todo) -> int {
+        const size_t np2 = (size_t)p.npix * (size_t)p.npix;
+        vector<const float *> maps;
+        vector<double> coeff;
+        vector<float> host;
+        size_t n_up = 0;
+        for (int i = i0; i < i1; i++) {
+            const auto it = std::find(todo.begin(), todo.end(), i);
+            float *d = nullptr;
+            if (it != todo.end()) {
+                if (slicer_plane_device_maps(h, (int)(it - todo.begin()), &d, nullptr) != SLICER_OK) {
+                    cerr << "slicer_amd: " << slicer_last_error(h) << endl;
+                    return 1;
+                }
+            } else {
+                const string path = fileOutput(p, plane_label(lens.pll[i]));
+                host.resize(np2);
+                if (!fits_read_image(path, p.npix, host.data())) {
+                    cerr << "slicer_amd: --kappa: cannot read the plane back from " << path << endl;
+                    return 1;
+                }
+                const size_t slot = n_up++;
+                if (kappa_upload.size() <= slot) {
+                    void *b = nullptr;
+                    if (slicer_device_malloc(h, np2 * sizeof(float), &b) != SLICER_OK) {
+                        cerr << "slicer_amd: " << slicer_last_error(h) << endl;
+                        return 1;
+                    }
+                    kappa_upload.push_back((float *)b);
+                }
+                d = kappa_upload[slot];
+                // (stream-ordered after the previous batch's kernels, which may still read this buffer)
+                if (slicer_copy_to_device(h, d, host.data(), np2 * sizeof(float)) != SLICER_OK) {
+                    cerr << "slicer_amd: " << slicer_last_error(h) << endl;
+                    return 1;
+                }
+            }
+            maps.push_back(d);
+            for (int s = 0; s < n_kappa; s++)
+                coeff.push_back(kappa_c[(size_t)s * lens.nplanes + i]);
+        }
+        if (slicer_kappa_add(kh, (int)maps.size(), maps.data(), coeff.data()) != SLICER_OK) {
+            cerr << "slicer_amd: --kappa: " << slicer_last_error(h) << endl;
+            return 1;
+        }
+        return 0;
+    };
     Rendezvous rendezvous(nranks);
     cout << " Now loop on " << lens.nplanes << " planes " << endl;
     float rcase = 0.0f;  // slicer-v2.cpp:137
@@ -453,6 +561,10 @@ int main(int argc, char **argv)
         if (p.partinplanes && isnap == 0)
             cout << "!It is not possible to resume a Gadget run with partinplanes == true!" << endl;
         if (todo.empty()) {
+            if (kh && kappa_add_pass(isnap, iend, todo)) {
+                rc_all = 1;
+                break;
+            }
             isnap = iend;
             continue;
         }
@@ -610,8 +722,36 @@ int main(int argc, char **argv)
                 rc_all = 1;
             }
         }
+        if (rc_all == 0 && kh && kappa_add_pass(isnap, iend, todo))
+            rc_all = 1;
         isnap = iend;
     }
+    if (rc_all == 0 && kh) {  // one f32 FITS per source: the keys of kslicer's genericHeader (ZSOURCE, ANGLE)
+        vector<float> map((size_t)p.npix * (size_t)p.npix);
+        if (slicer_kappa_finalize(kh) != SLICER_OK)
+            rc_all = 1;
+        for (int s = 0; s < n_kappa && rc_all == 0; s++) {
+            char zbuf[32];
+            snprintf(zbuf, sizeof zbuf, "%.4f", kappa_zs[s]);
+            const string path = p.directory + p.simulation + ".kappa_z" + zbuf + "_" + p.snpix + "_" + p.suffix + ".fits";
+            const FitsKey keys[2] = {{"ZSOURCE", false, 0, kappa_zs[s], " "}, {"ANGLE", false, 0, p.fov, " "}};
+            if (slicer_kappa_read(kh, s, map.data()) != SLICER_OK) {
+                rc_all = 1;
+                break;
+            }
+            cout << "Saving the convergence map on: " << path << endl;
+            if (!fits_write_image(path, map.data(), p.npix, keys, 2)) {
+                cerr << "It was not possible to create the map: " << path << endl;
+                rc_all = 1;
+            }
+        }
+        if (rc_all)
+            cerr << "slicer_amd: --kappa: " << slicer_last_error(h) << endl;
+    }
+    if (kh)
+        slicer_kappa_destroy(kh);
+    for (float *b : kappa_upload)
+        slicer_device_free(h, b);
     for (auto &R : ranks) {
         if (R.comm)
             rccl.destroy(R.comm);

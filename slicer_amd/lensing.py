@@ -1,0 +1,109 @@
+"""Born-approximation convergence (kappa) maps from the lens planes.
+
+plane_weights wraps the host weights of include/slicer_amd.h (slicer_lensing_weights); Kappa is the device accumulator
+(slicer_kappa_*) bound to a Slicer handle: it reads the finalized plane maps where they are, in HBM.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from .api import Slicer, SlicerError
+
+_L = _lib.load()
+
+
+def _dptr(a):
+    return a.ctypes.data if a is not None else None
+
+
+def plane_weights(omega_m, omega_lambda, w0, fov_deg, npix, ld, ld2, zsnap, sources="all", growth=True, wa=0.0,
+                  physical=False):
+    """c[s, p] of kappa_s = sum_p c[s, p] (m_p - mean m_p), plus the per-plane zlo, zup, zl, chil and the source list.
+
+    ld, ld2: comoving plane edges in Mpc/h (Lens.ld / ld2); zsnap: snapshot redshift of every plane (Lens.zfromsnap);
+    sources: "all" (the far-edge redshift of every plane) or a sequence of source redshifts."""
+    ld = np.ascontiguousarray(ld, np.float64)
+    ld2 = np.ascontiguousarray(ld2, np.float64)
+    zsnap = np.ascontiguousarray(zsnap, np.float64)
+    P = ld.size
+    assert ld2.size == P and zsnap.size == P
+    zs = None if isinstance(sources, str) and sources == "all" else np.ascontiguousarray(sources, np.float64)
+    S = P if zs is None else zs.size
+    coeff = np.zeros((S, P), np.float64)
+    out = {k: np.zeros(P, np.float64) for k in ("zlo", "zup", "zl", "chil")}
+    rc = _L.slicer_lensing_weights(float(omega_m), float(omega_lambda), float(w0), float(wa), float(fov_deg), int(npix),
+                                   int(bool(growth)), int(bool(physical)), P, _dptr(ld), _dptr(ld2), _dptr(zsnap), S,
+                                   _dptr(zs), _dptr(coeff), _dptr(out["zlo"]), _dptr(out["zup"]), _dptr(out["zl"]),
+                                   _dptr(out["chil"]))
+    if rc:
+        raise SlicerError(rc, (_L.slicer_last_error(None) or b"").decode())
+    out["c"] = coeff
+    out["zs"] = out["zup"].copy() if zs is None else zs
+    return out
+
+
+class Kappa:
+    """n_sources kappa maps of npix^2 pixels accumulated on the device of `slicer`, on its stream."""
+
+    def __init__(self, slicer: Slicer, npix, n_sources):
+        self._s = slicer
+        self.npix, self.n_sources = int(npix), int(n_sources)
+        self.n_added = 0
+        self._dirty = True
+        kh = C.c_void_p()
+        slicer._chk(_L.slicer_kappa_create(slicer._h, self.npix, self.n_sources, C.byref(kh)))
+        self._kh = kh
+
+    def close(self):
+        if getattr(self, "_kh", None):
+            _L.slicer_kappa_destroy(self._kh)
+            self._kh = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def add_device(self, ptrs, coeff):
+        """ptrs: device addresses of n_maps f32 maps; coeff: [n_maps][n_sources] weights."""
+        ptrs = [int(p) for p in ptrs]
+        coeff = np.ascontiguousarray(coeff, np.float64).reshape(len(ptrs), self.n_sources)
+        arr = (C.c_void_p * len(ptrs))(*ptrs)
+        self._s._chk(_L.slicer_kappa_add(self._kh, len(ptrs), arr, coeff.ctypes.data))
+        self.n_added += len(ptrs)
+        self._dirty = True
+
+    def add(self, plane_indices, coeff):
+        """The total maps of planes `plane_indices` of the slicer's current (finalized) pass."""
+        self.add_device([self._s.plane_device_maps(int(i))[0] for i in plane_indices], coeff)
+
+    def finalize(self):
+        self._s._chk(_L.slicer_kappa_finalize(self._kh))
+        self._dirty = False
+
+    def plane_means(self):
+        out = np.zeros(self.n_added, np.float64)
+        self._s._chk(_L.slicer_kappa_plane_means(self._kh, out.ctypes.data, self.n_added))
+        return out
+
+    def device_map(self, s):
+        if self._dirty:
+            self.finalize()
+        p = C.c_void_p()
+        self._s._chk(_L.slicer_kappa_device_map(self._kh, int(s), C.byref(p)))
+        return p.value
+
+    def read(self, s):
+        if self._dirty:
+            self.finalize()
+        out = np.empty((self.npix, self.npix), np.float32)
+        self._s._chk(_L.slicer_kappa_read(self._kh, int(s), out.ctypes.data))
+        return out
