@@ -144,6 +144,7 @@ const char *slicer_last_error(slicer_handle h); /* valid until the next call on 
  *   zero_batch   1 (default): the maps of a pass are cleared by one launch; 0: one hipMemsetAsync per map
  *   thin_host    1: shot-noise deviates (snopt > 0) drawn by libc rand() on the host, one call per selected entry;
  *                default 0: the process-global rand() stream continues on the device (slicer_libc_rand_supported)
+ *   shear_split  1: every FFT of a slicer_shear handle created afterwards goes in passes of at most sqrt(length) points
  * Unknown keys return SLICER_ERR_ARG. */
 int slicer_set_option(slicer_handle h, const char *key, int32_t value);
 int slicer_get_option(slicer_handle h, const char *key, int32_t *value);
@@ -330,6 +331,34 @@ int slicer_kappa_finalize(slicer_kappa_handle kh);
 int slicer_kappa_device_map(slicer_kappa_handle kh, int32_t s, float **d_map);
 int slicer_kappa_read(slicer_kappa_handle kh, int32_t s, float *host);
 int slicer_kappa_destroy(slicer_kappa_handle kh);
+
+/* ---- Lensing potential and shear maps from a kappa map ----
+ * For an npix^2 map kappa (row i0 slow, i1 contiguous) of side theta = angle_deg * pi / 180 radians, d = theta / npix:
+ * K0 = 2 pi fftfreq(npix, d) along i0, K1 = 2 pi rfftfreq(npix, d) along i1, k^2 = K0^2 + K1^2 (every quotient 0 at 0),
+ *   khat = rfft2(kappa);  phi = irfft2(-2 khat / k^2);  gamma1 = irfft2(khat (K0^2 - K1^2) / k^2);
+ *   gamma2 = irfft2(khat 2 K0 K1 / k^2);  |gamma| = sqrt(gamma1^2 + gamma2^2),  irfft2 with s = (npix, npix),
+ * computed in f64 and rounded once to f32, on the device and stream of h (create it after any slicer_set_stream;
+ * destroy it before h).  Supported: 2 <= npix <= 16384 with prime factors 2, 3, 5, 7 only (slicer_shear_supported, host
+ * only); others return SLICER_ERR_UNSUPPORTED.  angle_deg <= 0 or not finite: SLICER_ERR_ARG.
+ *   slicer_shear_run         any device f32 npix^2 map (e.g. slicer_kappa_device_map); enqueued, no synchronisation
+ *   slicer_shear_spectrum    khat of the last run, [npix][npix/2+1] (re, im) f64 pairs; waits for the stream
+ *   slicer_shear_device_map / _read   map `which` (SLICER_SHEAR_*) of the last run (SLICER_ERR_STATE before any run);
+ *                            _read waits for the stream
+ * Option shear_split = 1 (slicer_set_option, read at create) splits every transform into passes of at most
+ * sqrt(length) points, the path that longer maps take.  The same input gives bitwise the same maps.  Device memory:
+ * about 4 f64 complex npix x (npix/2+1) arrays plus the four f32 maps (SLICER_ERR_NOMEM). */
+#define SLICER_SHEAR_PHI 0
+#define SLICER_SHEAR_GAMMA1 1
+#define SLICER_SHEAR_GAMMA2 2
+#define SLICER_SHEAR_GAMMA 3
+int slicer_shear_supported(int32_t n);
+typedef struct slicer_shear_s *slicer_shear_handle;
+int slicer_shear_create(slicer_handle h, int32_t npix, double angle_deg, slicer_shear_handle *out);
+int slicer_shear_run(slicer_shear_handle sh, const float *d_kappa);
+int slicer_shear_spectrum(slicer_shear_handle sh, double *host);
+int slicer_shear_device_map(slicer_shear_handle sh, int32_t which, float **d_map);
+int slicer_shear_read(slicer_shear_handle sh, int32_t which, float *host);
+int slicer_shear_destroy(slicer_shear_handle sh);
 
 /* per-kernel HIP-event timing (off by default; adds two event records per launch) */
 int slicer_profile_enable(slicer_handle h, int on);

@@ -89,6 +89,13 @@ SYMBOLS = {
     "slicer_kappa_device_map": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_void_p)]),
     "slicer_kappa_read": (C.c_int, [_H, C.c_int32, C.c_void_p]),
     "slicer_kappa_destroy": (C.c_int, [_H]),
+    "slicer_shear_supported": (C.c_int, [C.c_int32]),
+    "slicer_shear_create": (C.c_int, [_H, C.c_int32, C.c_double, C.POINTER(C.c_void_p)]),
+    "slicer_shear_run": (C.c_int, [_H, C.c_void_p]),
+    "slicer_shear_spectrum": (C.c_int, [_H, C.c_void_p]),
+    "slicer_shear_device_map": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_void_p)]),
+    "slicer_shear_read": (C.c_int, [_H, C.c_int32, C.c_void_p]),
+    "slicer_shear_destroy": (C.c_int, [_H]),
     "slicer_profile_enable": (C.c_int, [_H, C.c_int]),
     "slicer_profile_reset": (C.c_int, [_H]),
     "slicer_profile_get": (C.c_int, [_H, C.POINTER(KernelTime), C.c_int, C.POINTER(C.c_int)]),

@@ -61,6 +61,7 @@ struct Options {
     int thin_host = 0;    // 1: shot-noise deviates drawn by libc rand() on the host (0: the stream continues on the device)
     int sort2 = 0;        // 1: two-level sort (project+bin sorts by coarse bin in LDS, k_sort2 by tile) where a pass
                           // qualifies.  Off by default: it moves fewer bytes but costs more instructions
+    int shear_split = 0;  // 1: slicer_shear handles split every FFT into passes of <= sqrt(length) points (tests)
 };
 struct OptionName {
     const char *key, *env;
@@ -81,6 +82,7 @@ const OptionName kOptionNames[] = {
     {"thin_host", "SLICER_THIN_HOST", &Options::thin_host},
     {"pending", "SLICER_PENDING", &Options::pending},
     {"zero_batch", "SLICER_ZERO_BATCH", &Options::zero_batch},
+    {"shear_split", "SLICER_SHEAR_SPLIT", &Options::shear_split},
 };
 
 constexpr size_t kPassScalarsBytes = sizeof(unsigned long long) * SLICER_MAX_PLANES * 6 + sizeof(int) + 7 * sizeof(unsigned);

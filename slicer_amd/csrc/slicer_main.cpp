@@ -13,6 +13,8 @@
 //   * --kappa all|z1,z2,... adds Born convergence maps, one FITS per source redshift, accumulated on device 0 from the
 //     finalized total maps of every pass (the reference's post-processing script Lens/kslicer.py);
 //     --kappa-no-growth drops its linear-growth correction.  Without --kappa the run is unchanged.
+//   * --shear (with --kappa) also writes, per source, the shear maps gamma1, gamma2, |gamma| and the lensing potential
+//     phi computed on device 0 from the kappa map (the reference's Lens/smr.py).
 //   * SubFind / halo-catalogue mode (npix == 0) is not supported; with snopt > 0 and several devices every rank thread
 //     draws from its own copy of the libc stream, like the reference's MPI ranks
 //     (the thinning deviates come from the process-global libc rand() stream, densitymaps.cpp:387-397: the reference's
@@ -302,7 +304,7 @@ int host_plane_reduce(vector<Rank> &ranks, int npix, int n_planes)
 int main(int argc, char **argv)
 {
     string inifile, plan_path, devices_spec, reduce_mode = "rccl", reduce_algo = "rooted", kappa_spec;
-    bool kappa_growth = true;
+    bool kappa_growth = true, shear = false;
     int device = 0, mas = SLICER_MAS_TSC, accum = SLICER_ACC_F32;
     bool plan_only = false, single_plane = false, reference_counts = false, replication = false;
     for (int i = 1; i < argc; i++) {
@@ -322,6 +324,7 @@ int main(int argc, char **argv)
         else if (a == "--replication") replication = true;
         else if (a == "--kappa" && i + 1 < argc) kappa_spec = argv[++i];  // all | z1,z2,...
         else if (a == "--kappa-no-growth") kappa_growth = false;  // -DUSE_REPLICATION (ReplicationOnPerpendicularPlane)
+        else if (a == "--shear") shear = true;
         else if (inifile.empty()) inifile = a;
         else {
             cerr << "unknown argument " << a << endl;
@@ -332,11 +335,19 @@ int main(int argc, char **argv)
         cout << "No params!! Nothing to be done!" << endl;  // slicer-v2.cpp:34
         return 2;
     }
+    if (shear && kappa_spec.empty()) {
+        cerr << "--shear needs --kappa (the shear maps are computed from the kappa maps)" << endl;
+        return 2;
+    }
     const int myid = 0;
     InputParams p{};
     double fovradiants = 0;
     if (readInput(p, inifile))
         return 1;
+    if (shear && !slicer_shear_supported(p.npix)) {
+        cerr << "--shear: npix = " << p.npix << " is not supported (2 ... 16384, prime factors 2, 3, 5, 7 only)" << endl;
+        return 2;
+    }
     if (p.simType == "SubFind") {
         cerr << "SubFind / halo light-cone mode (npix == 0) is outside this driver's scope" << endl;
         return 1;
@@ -474,6 +485,12 @@ int main(int argc, char **argv)
     slicer_kappa_handle kh = nullptr;
     if (n_kappa && slicer_kappa_create(h, p.npix, n_kappa, &kh) != SLICER_OK) {
         cerr << "slicer_amd: --kappa: " << slicer_last_error(h) << endl;
+        return 1;
+    }
+    slicer_shear_handle shh = nullptr;
+    if (kh && shear && slicer_shear_create(h, p.npix, p.fov, &shh) != SLICER_OK) {
+        cerr << "slicer_amd: --shear: " << slicer_last_error(h) << endl;
+        slicer_kappa_destroy(kh);
         return 1;
     }
     // The planes isnap .. iend-1 of one pass go into the kappa maps as ONE batch whether they were deposited now (their
@@ -744,10 +761,38 @@ int main(int argc, char **argv)
                 cerr << "It was not possible to create the map: " << path << endl;
                 rc_all = 1;
             }
+            if (!shh || rc_all)
+                continue;
+            // smr.smr(kappa file): the same name with the .kappa_z token replaced, the same header
+            float *d_kappa = nullptr;
+            if (slicer_kappa_device_map(kh, s, &d_kappa) != SLICER_OK || slicer_shear_run(shh, d_kappa) != SLICER_OK) {
+                rc_all = 1;
+                break;
+            }
+            const struct {
+                const char *token;
+                int which;
+            } outs[4] = {{".gamma1_z", SLICER_SHEAR_GAMMA1}, {".gamma2_z", SLICER_SHEAR_GAMMA2},
+                         {".gamma_z", SLICER_SHEAR_GAMMA}, {".phi_z", SLICER_SHEAR_PHI}};
+            for (const auto &o : outs) {
+                const string spath = p.directory + p.simulation + o.token + zbuf + "_" + p.snpix + "_" + p.suffix + ".fits";
+                if (slicer_shear_read(shh, o.which, map.data()) != SLICER_OK) {
+                    rc_all = 1;
+                    break;
+                }
+                cout << "Saving the shear map on: " << spath << endl;
+                if (!fits_write_image(spath, map.data(), p.npix, keys, 2)) {
+                    cerr << "It was not possible to create the map: " << spath << endl;
+                    rc_all = 1;
+                    break;
+                }
+            }
         }
         if (rc_all)
             cerr << "slicer_amd: --kappa: " << slicer_last_error(h) << endl;
     }
+    if (shh)
+        slicer_shear_destroy(shh);
     if (kh)
         slicer_kappa_destroy(kh);
     for (float *b : kappa_upload)

@@ -1,0 +1,637 @@
+// slicer_shear.hip -- on-device lensing potential and shear maps from a kappa map.
+//
+// With K0 = 2 pi fftfreq(n, d) along axis 0 (rows), K1 = 2 pi rfftfreq(n, d) along axis 1 (the contiguous axis),
+// k^2 = K0^2 + K1^2, d = theta / n and every quotient 0 at k = 0:
+//   khat = rfft2(kappa);  phi = irfft2(-2 khat / k^2);  gamma1 = irfft2(khat (K0^2 - K1^2) / k^2);
+//   gamma2 = irfft2(khat 2 K0 K1 / k^2);  |gamma| = sqrt(gamma1^2 + gamma2^2)
+// in f64, every output rounded once to f32.  One kernel, k_fft_pass, does everything: one pass of a multi-pass
+// Stockham FFT over a batch of lines (rows or columns).  A workgroup gathers C lines x R points of the line into LDS
+// (points j + r L/R, twiddled by W_{Ns R}^{r k}), transforms them there with radix-2/3/4/5/7/8 stages, and scatters
+// them to j/Ns Ns R + k + q Ns.  One pass covers a line when it fits (R = L); longer lines take two or three passes.
+// The first pass of a chain may load through a mode and the last may store through one, which is where the
+// pre/post-processing is fused:
+//   forward rows     even n: z[m] = x[2m] + i x[2m+1] (n/2 points); odd n: z = row 2p + i row 2p+1 (n points)
+//   forward columns  the r2c split of those rows (into khat's [n][n/2+1]) fused into the first column load
+//   inverse columns  the filter of the output, from the bin indices, fused into the first column load
+//   inverse rows     the c2r merge (with irfft's Hermitian projection of columns 0 and n/2) fused into the first row
+//                    load; the last row pass rounds to f32.  gamma1's last pass keeps f64 (aux); gamma2's last pass
+//                    reads it and writes gamma1, gamma2 and |gamma|.
+// Twiddles: one f64 table W_n^j = exp(-2 pi i j / n), j < n, from long-double sincos on the host.  No atomics and
+// no work handed between workgroups: the results are bitwise repeatable.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+#include <new>
+#include <vector>
+
+#include "../../include/slicer_amd.h"
+
+extern "C" int slicer_internal_fail(slicer_handle h, int code, const char *msg);  // slicer_capi.cpp (not exported)
+
+namespace {
+
+constexpr int kThreads = 512;
+constexpr int kPerThread = 16;                   // complex points a thread holds through an LDS stage
+constexpr int kLdsPoints = kThreads * kPerThread;  // C * R of one workgroup (128 KiB of f64 complex, + padding)
+constexpr int kMaxN = 16384;
+constexpr int kColCap = kLdsPoints / 8;          // column passes: at least 8 adjacent columns (128 B) per workgroup
+constexpr int kMaxLines = 64;
+constexpr int kMaxStages = 16;
+
+enum Load { L_COMPLEX = 0, L_REAL_EVEN, L_REAL_PAIR, L_SPLIT_EVEN, L_SPLIT_PAIR, L_FILTER, L_C2R_EVEN, L_C2R_PAIR };
+enum Store { S_COMPLEX = 0, S_REAL_EVEN, S_REAL_PAIR, S_GAMMA_EVEN, S_GAMMA_PAIR };
+
+struct PassArgs {
+    const void *in;
+    void *out;          // complex f64 (S_COMPLEX) or the f32 map (gamma1 for S_GAMMA_*)
+    float *out2, *out3;  // S_GAMMA_*: gamma2, |gamma|
+    const double2 *aux;  // S_GAMMA_*: gamma1 in f64, as its last row pass left it
+    const double2 *tw;   // W_n^j, j < n
+    int n, H, len;       // map side, half-spectrum width n/2+1, row-transform length (n/2 even, n odd)
+    int L, R, Ns;        // this chain's length; this pass's radix; product of the earlier passes' radices
+    int nlines, C, Rp;   // lines of the chain; lines per workgroup; LDS pitch of a line
+    int ls_in, es_in, ls_out, es_out;  // L_COMPLEX / S_COMPLEX strides (line, element), in complex elements
+    int load, store, inv, cfast;       // cfast: adjacent threads take adjacent lines (columns)
+    int filt;                          // L_FILTER: SLICER_SHEAR_PHI / _GAMMA1 / _GAMMA2
+    double phi_c;                      // L_FILTER phi: -2 / (2 pi / theta)^2
+    double scale;                      // S_REAL_* / S_GAMMA_*: 1 / n^2
+    int nst;
+    int rad[kMaxStages];
+};
+
+__device__ inline double2 cmul(double2 a, double2 b)
+{
+    return make_double2(fma(a.x, b.x, -a.y * b.y), fma(a.x, b.y, a.y * b.x));
+}
+__device__ inline double2 cadd(double2 a, double2 b) { return make_double2(a.x + b.x, a.y + b.y); }
+__device__ inline double2 csub(double2 a, double2 b) { return make_double2(a.x - b.x, a.y - b.y); }
+__device__ inline double2 conjg(double2 a) { return make_double2(a.x, -a.y); }
+
+// W_M^x (conjugated for the inverse), M | n, 0 <= x < M
+__device__ inline double2 twid(const PassArgs &a, int x, int M)
+{
+    const double2 w = a.tw[(size_t)x * (a.n / M)];
+    return a.inv ? conjg(w) : w;
+}
+
+__device__ double2 load_point(const PassArgs &a, int l, int e)
+{
+    const int n = a.n, H = a.H;
+    switch (a.load) {
+    case L_REAL_EVEN: {  // row l: x[2e] + i x[2e+1]
+        const float *k = (const float *)a.in + (size_t)l * n + 2 * e;
+        return make_double2((double)k[0], (double)k[1]);
+    }
+    case L_REAL_PAIR: {  // rows 2l, 2l+1 at column e
+        const float *k = (const float *)a.in + (size_t)(2 * l) * n + e;
+        return make_double2((double)k[0], 2 * l + 1 < n ? (double)k[n] : 0.0);
+    }
+    case L_SPLIT_EVEN: {  // khat[e][l] from the n/2-point transform of row e
+        const int h = n / 2;
+        const double2 *T = (const double2 *)a.in + (size_t)e * h;
+        const double2 z = T[l % h], zc = conjg(T[(h - l % h) % h]);
+        const double2 ev = make_double2(0.5 * (z.x + zc.x), 0.5 * (z.y + zc.y));
+        const double2 d = csub(z, zc);
+        const double2 od = make_double2(0.5 * d.y, -0.5 * d.x);  // d / 2i
+        return cadd(ev, cmul(twid(a, l, n), od));
+    }
+    case L_SPLIT_PAIR: {  // khat[e][l] from the n-point transform of rows (e & ~1) + i (e | 1)
+        const double2 *T = (const double2 *)a.in + (size_t)(e / 2) * n;
+        const double2 z = T[l], zc = conjg(T[(n - l) % n]);
+        if (e % 2 == 0)
+            return make_double2(0.5 * (z.x + zc.x), 0.5 * (z.y + zc.y));
+        const double2 d = csub(z, zc);
+        return make_double2(0.5 * d.y, -0.5 * d.x);
+    }
+    case L_FILTER: {  // khat[e][l] times the filter at K0 ~ fftfreq index e, K1 ~ l
+        const double2 s = ((const double2 *)a.in)[(size_t)e * H + l];
+        const double f0 = (double)(e < (n + 1) / 2 ? e : e - n), f1 = (double)l;
+        const double k2 = f0 * f0 + f1 * f1;  // exact: integers below 2^28
+        if (k2 == 0.0)
+            return make_double2(0.0, 0.0);
+        double g;
+        if (a.filt == SLICER_SHEAR_PHI)
+            g = a.phi_c / k2;
+        else if (a.filt == SLICER_SHEAR_GAMMA1)
+            g = (f0 * f0 - f1 * f1) / k2;
+        else
+            g = 2.0 * f0 * f1 / k2;
+        return make_double2(s.x * g, s.y * g);
+    }
+    case L_C2R_EVEN: {  // Z'[e] = (X + Y) + i W_n^-e (X - Y), X = U[l][e], Y = conj U[l][h-e]; irfft keeps Re at 0, h
+        const int h = n / 2;
+        const double2 *U = (const double2 *)a.in + (size_t)l * H;
+        double2 x = U[e], y = conjg(U[h - e]);
+        if (e == 0) {
+            x.y = 0.0;
+            y.y = 0.0;
+        }
+        const double2 o = cmul(twid(a, e, n), csub(x, y));  // a.inv: W_n^-e
+        return make_double2(x.x + y.x - o.y, x.y + y.y + o.x);
+    }
+    case L_C2R_PAIR: {  // Hermitian extensions of rows 2l and 2l+1, packed as E_a + i E_b
+        const double2 *U = (const double2 *)a.in + (size_t)(2 * l) * H;
+        double2 ea, eb = make_double2(0.0, 0.0);
+        const bool lo = e <= (n - 1) / 2;
+        ea = lo ? U[e] : conjg(U[n - e]);
+        if (2 * l + 1 < n)
+            eb = lo ? U[H + e] : conjg(U[H + n - e]);
+        if (e == 0) {
+            ea.y = 0.0;
+            eb.y = 0.0;
+        }
+        return make_double2(ea.x - eb.y, ea.y + eb.x);
+    }
+    default:
+        return ((const double2 *)a.in)[(size_t)l * a.ls_in + (size_t)e * a.es_in];
+    }
+}
+
+__device__ void store_point(const PassArgs &a, int l, int e, double2 v)
+{
+    const int n = a.n;
+    switch (a.store) {
+    case S_REAL_EVEN: {
+        float *o = (float *)a.out + (size_t)l * n + 2 * e;
+        o[0] = (float)(v.x * a.scale);
+        o[1] = (float)(v.y * a.scale);
+        return;
+    }
+    case S_REAL_PAIR: {
+        float *o = (float *)a.out + (size_t)(2 * l) * n + e;
+        o[0] = (float)(v.x * a.scale);
+        if (2 * l + 1 < n)
+            o[n] = (float)(v.y * a.scale);
+        return;
+    }
+    case S_GAMMA_EVEN:
+    case S_GAMMA_PAIR: {
+        const double2 g1 = a.aux[(size_t)l * a.len + e];
+        const double g1x = g1.x * a.scale, g1y = g1.y * a.scale, g2x = v.x * a.scale, g2y = v.y * a.scale;
+        size_t i0, i1;  // map indices of the .x and .y halves
+        bool two = true;
+        if (a.store == S_GAMMA_EVEN) {
+            i0 = (size_t)l * n + 2 * e;
+            i1 = i0 + 1;
+        } else {
+            i0 = (size_t)(2 * l) * n + e;
+            i1 = i0 + n;
+            two = 2 * l + 1 < n;
+        }
+        float *o1 = (float *)a.out;
+        o1[i0] = (float)g1x;
+        a.out2[i0] = (float)g2x;
+        a.out3[i0] = (float)sqrt(g1x * g1x + g2x * g2x);
+        if (two) {
+            o1[i1] = (float)g1y;
+            a.out2[i1] = (float)g2y;
+            a.out3[i1] = (float)sqrt(g1y * g1y + g2y * g2y);
+        }
+        return;
+    }
+    default:
+        ((double2 *)a.out)[(size_t)l * a.ls_out + (size_t)e * a.es_out] = v;
+    }
+}
+
+// One radix-RAD Stockham stage over the C lines of R points in LDS (line c at c * Rp), in place: every thread first
+// takes its butterflies into registers, then writes them back.  C * R <= kLdsPoints.
+template <int RAD>
+__device__ void lds_stage(const PassArgs &a, double2 *lds, int C, int R, int Ns)
+{
+    constexpr int kMaxB = (kPerThread + RAD - 1) / RAD;
+    const int nj = R / RAD, nb = C * nj;
+    double2 w[RAD];
+#pragma unroll
+    for (int e = 0; e < RAD; e++)
+        w[e] = twid(a, e, RAD);
+    double2 v[kMaxB][RAD];
+#pragma unroll
+    for (int u = 0; u < kMaxB; u++) {
+        const int b = threadIdx.x + u * kThreads;
+        if (b < nb) {
+            const int c = b / nj, j = b - c * nj, k = j % Ns;
+            const double2 *p = lds + c * a.Rp + j;
+#pragma unroll
+            for (int q = 0; q < RAD; q++) {
+                double2 x = p[q * nj];
+                if (q && k)
+                    x = cmul(x, twid(a, q * k, Ns * RAD));
+                v[u][q] = x;
+            }
+        }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < kMaxB; u++) {
+        const int b = threadIdx.x + u * kThreads;
+        if (b < nb) {
+            const int c = b / nj, j = b - c * nj, k = j % Ns;
+            double2 *p = lds + c * a.Rp + (j / Ns) * Ns * RAD + k;
+#pragma unroll
+            for (int m = 0; m < RAD; m++) {
+                double2 y = v[u][0];
+#pragma unroll
+                for (int q = 1; q < RAD; q++)
+                    y = cadd(y, cmul(v[u][q], w[(q * m) % RAD]));
+                p[m * Ns] = y;
+            }
+        }
+    }
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(kThreads) void k_fft_pass(PassArgs a)
+{
+    extern __shared__ double2 lds[];
+    const int C = a.C, R = a.R, l0 = blockIdx.x * C, j = blockIdx.y, k = j % a.Ns, stride = a.L / R;
+    for (int t = threadIdx.x; t < C * R; t += kThreads) {
+        const int c = a.cfast ? t % C : t / R, r = a.cfast ? t / C : t % R, l = l0 + c;
+        double2 v = make_double2(0.0, 0.0);
+        if (l < a.nlines) {
+            v = load_point(a, l, j + r * stride);
+            if (k && r)
+                v = cmul(v, twid(a, r * k, a.Ns * R));
+        }
+        lds[c * a.Rp + r] = v;
+    }
+    __syncthreads();
+    int ns = 1;
+    for (int s = 0; s < a.nst; s++) {
+        switch (a.rad[s]) {
+        case 2: lds_stage<2>(a, lds, C, R, ns); break;
+        case 3: lds_stage<3>(a, lds, C, R, ns); break;
+        case 4: lds_stage<4>(a, lds, C, R, ns); break;
+        case 5: lds_stage<5>(a, lds, C, R, ns); break;
+        case 7: lds_stage<7>(a, lds, C, R, ns); break;
+        default: lds_stage<8>(a, lds, C, R, ns); break;
+        }
+        ns *= a.rad[s];
+    }
+    const int base = (j / a.Ns) * a.Ns * R + k;
+    for (int t = threadIdx.x; t < C * R; t += kThreads) {
+        const int c = a.cfast ? t % C : t / R, q = a.cfast ? t / C : t % R, l = l0 + c;
+        if (l < a.nlines)
+            store_point(a, l, base + q * a.Ns, lds[c * a.Rp + q]);
+    }
+}
+
+bool smooth(int n)
+{
+    if (n < 2 || n > kMaxN)
+        return false;
+    for (int p : {2, 3, 5, 7})
+        while (n % p == 0)
+            n /= p;
+    return n == 1;
+}
+
+// one pass of a chain: radix R (itself split into LDS stages), Ns, lines per workgroup
+struct Pass {
+    int R, Ns, C, Rp, nst;
+    int rad[kMaxStages];
+};
+
+// passes of a length-L transform over nlines lines, each radix at most cap
+std::vector<Pass> plan_chain(int L, int nlines, int cap)
+{
+    std::vector<Pass> out;
+    int rem = L, ns = 1;
+    do {
+        int R = 1;
+        for (int d = std::min(rem, cap); d >= 2; d--)
+            if (rem % d == 0) {
+                R = d;
+                break;
+            }
+        if (R == 1 && rem > 1)  // cap below the smallest prime factor (only a forced split): take that factor
+            for (int p : {2, 3, 5, 7})
+                if (rem % p == 0) {
+                    R = p;
+                    break;
+                }
+        Pass p{};
+        p.R = R;
+        p.Ns = ns;
+        p.C = std::max(1, std::min({kLdsPoints / std::max(R, 1), kMaxLines, nlines}));
+        p.Rp = R + (R % 2 == 0);  // odd LDS pitch: the line-strided accesses of column loads spread over the banks
+        int x = R;
+        for (int r : {8, 4, 2, 3, 5, 7})
+            while (x % r == 0) {
+                p.rad[p.nst++] = r;
+                x /= r;
+            }
+        out.push_back(p);
+        rem /= R;
+        ns *= R;
+    } while (rem > 1);
+    return out;
+}
+
+}  // namespace
+
+struct slicer_shear_s {
+    slicer_handle h = nullptr;
+    int device = 0;
+    int n = 0, H = 0, len = 0, rows = 0;  // rows x len: the row transforms (n x n/2 even, ceil(n/2) x n odd)
+    double angle = 0.0;
+    std::vector<Pass> fwd_rows, fwd_cols, inv_cols, inv_rows;
+    double2 *tw = nullptr;
+    double2 *S = nullptr, *A = nullptr, *B = nullptr, *Cb = nullptr, *G = nullptr;  // complex f64, n * H each
+    float *maps[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool ran = false;
+};
+
+namespace {
+
+int sfail(slicer_shear_handle sh, int code, const char *fmt, ...) __attribute__((format(printf, 3, 4)));
+int sfail(slicer_shear_handle sh, int code, const char *fmt, ...)
+{
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    return slicer_internal_fail(sh ? sh->h : nullptr, code, buf);
+}
+
+#define SCHK(sh, expr)                                                                                            \
+    do {                                                                                                          \
+        hipError_t e_ = (expr);                                                                                   \
+        if (e_ != hipSuccess)                                                                                     \
+            return sfail(sh, e_ == hipErrorOutOfMemory ? SLICER_ERR_NOMEM : SLICER_ERR_HIP, "%s failed: %s (%s:%d)", \
+                         #expr, hipGetErrorString(e_), __FILE__, __LINE__);                                       \
+    } while (0)
+
+int stream_of(slicer_shear_handle sh, hipStream_t *st)
+{
+    void *p = nullptr;
+    if (slicer_get_stream(sh->h, &p) != SLICER_OK)
+        return SLICER_ERR_ARG;
+    *st = (hipStream_t)p;
+    SCHK(sh, hipSetDevice(sh->device));
+    return SLICER_OK;
+}
+
+void release(slicer_shear_handle sh)
+{
+    (void)hipSetDevice(sh->device);
+    for (void *p : {(void *)sh->tw, (void *)sh->S, (void *)sh->A, (void *)sh->B, (void *)sh->Cb, (void *)sh->G})
+        if (p)
+            (void)hipFree(p);
+    for (float *p : sh->maps)
+        if (p)
+            (void)hipFree(p);
+    delete sh;
+}
+
+// Where the ends of a chain read and write, and how (see PassArgs).
+struct End {
+    const void *in;
+    void *out;
+    int load, store;
+    int ls_in, es_in, ls_out, es_out;
+};
+
+// Launch the passes of one chain; intermediates alternate between x and y (neither is e.in nor e.out).
+int run_chain(slicer_shear_handle sh, hipStream_t st, const std::vector<Pass> &passes, bool cols, bool inv,
+              const End &e, const PassArgs &proto, double2 *x, double2 *y)
+{
+    const int m = (int)passes.size();
+    const int ls = cols ? 1 : sh->len, es = cols ? sh->H : 1;  // intermediate layout of the chain's domain
+    const void *in = e.in;
+    for (int p = 0; p < m; p++) {
+        const Pass &ps = passes[p];
+        PassArgs a = proto;
+        a.tw = sh->tw;
+        a.n = sh->n;
+        a.H = sh->H;
+        a.len = sh->len;
+        a.L = cols ? sh->n : sh->len;
+        a.nlines = cols ? sh->H : sh->rows;
+        a.R = ps.R;
+        a.Ns = ps.Ns;
+        a.C = ps.C;
+        a.Rp = ps.Rp;
+        a.nst = ps.nst;
+        for (int s = 0; s < ps.nst; s++)
+            a.rad[s] = ps.rad[s];
+        a.inv = inv;
+        a.cfast = cols;
+        a.in = in;
+        a.load = p == 0 ? e.load : L_COMPLEX;
+        a.ls_in = p == 0 ? e.ls_in : ls;
+        a.es_in = p == 0 ? e.es_in : es;
+        if (p == m - 1) {
+            a.out = e.out;
+            a.store = e.store;
+            a.ls_out = e.ls_out;
+            a.es_out = e.es_out;
+        } else {
+            a.out = (m - 2 - p) % 2 == 0 ? x : y;
+            a.store = S_COMPLEX;
+            a.ls_out = ls;
+            a.es_out = es;
+        }
+        const size_t lds = (size_t)ps.C * ps.Rp * sizeof(double2);
+        const dim3 grid((unsigned)((a.nlines + ps.C - 1) / ps.C), (unsigned)(a.L / ps.R));
+        hipLaunchKernelGGL(k_fft_pass, grid, dim3(kThreads), lds, st, a);
+        SCHK(sh, hipGetLastError());
+        in = a.out;
+    }
+    return SLICER_OK;
+}
+
+}  // namespace
+
+int slicer_shear_supported(int32_t n) { return smooth(n) ? 1 : 0; }
+
+int slicer_shear_create(slicer_handle h, int32_t npix, double angle_deg, slicer_shear_handle *out)
+{
+    if (!h || !out)
+        return slicer_internal_fail(h, SLICER_ERR_ARG, "slicer_shear_create: null argument");
+    *out = nullptr;
+    if (!smooth(npix)) {
+        char buf[160];
+        snprintf(buf, sizeof buf, "slicer_shear_create: npix = %d unsupported (2..%d, prime factors 2, 3, 5, 7 only)",
+                 npix, kMaxN);
+        return slicer_internal_fail(h, SLICER_ERR_UNSUPPORTED, buf);
+    }
+    if (!std::isfinite(angle_deg) || angle_deg <= 0.0)
+        return slicer_internal_fail(h, SLICER_ERR_ARG, "slicer_shear_create: the angle must be positive and finite");
+    int split = 0;
+    if (slicer_get_option(h, "shear_split", &split) != SLICER_OK)
+        return SLICER_ERR_ARG;
+    slicer_shear_handle sh = new (std::nothrow) slicer_shear_s;
+    if (!sh)
+        return slicer_internal_fail(h, SLICER_ERR_NOMEM, "out of host memory");
+    const int n = npix;
+    sh->h = h;
+    sh->n = n;
+    sh->H = n / 2 + 1;
+    sh->len = n % 2 == 0 ? n / 2 : n;
+    sh->rows = n % 2 == 0 ? n : (n + 1) / 2;
+    sh->angle = angle_deg;
+    auto cap = [&](int L, int c) { return split ? std::max(2, (int)std::floor(std::sqrt((double)L))) : c; };
+    sh->fwd_rows = plan_chain(sh->len, sh->rows, cap(sh->len, kLdsPoints));
+    sh->fwd_cols = plan_chain(n, sh->H, cap(n, kColCap));
+    sh->inv_cols = sh->fwd_cols;
+    sh->inv_rows = sh->fwd_rows;
+    const size_t passes = std::max(sh->fwd_rows.size(), sh->fwd_cols.size());
+
+    void *sp = nullptr;
+    int dev = 0;
+    int rc = slicer_get_stream(h, &sp);
+    hipStream_t st = (hipStream_t)sp;
+    if (rc == SLICER_OK && hipStreamGetDevice(st, &dev) != hipSuccess)
+        rc = sfail(sh, SLICER_ERR_HIP, "slicer_shear_create: the handle's stream has no device");
+    sh->device = dev;
+    if (rc == SLICER_OK && hipSetDevice(dev) != hipSuccess)
+        rc = sfail(sh, SLICER_ERR_HIP, "hipSetDevice(%d) failed", dev);
+    if (rc == SLICER_OK &&
+        hipFuncSetAttribute((const void *)k_fft_pass, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)((kLdsPoints + kMaxLines) * sizeof(double2))) != hipSuccess)
+        rc = sfail(sh, SLICER_ERR_HIP, "slicer_shear_create: cannot raise the LDS limit of the FFT kernel");
+    auto alloc = [&](void **p, size_t bytes) {
+        if (rc != SLICER_OK)
+            return;
+        hipError_t e = hipMalloc(p, bytes);
+        if (e != hipSuccess)
+            rc = sfail(sh, e == hipErrorOutOfMemory ? SLICER_ERR_NOMEM : SLICER_ERR_HIP,
+                       "slicer_shear_create: %zu bytes of device memory: %s", bytes, hipGetErrorString(e));
+    };
+    const size_t cbytes = (size_t)n * sh->H * sizeof(double2);
+    alloc((void **)&sh->tw, (size_t)n * sizeof(double2));
+    alloc((void **)&sh->S, cbytes);
+    alloc((void **)&sh->A, cbytes);
+    alloc((void **)&sh->G, cbytes);
+    if (passes >= 2)
+        alloc((void **)&sh->B, cbytes);
+    if (passes >= 3)
+        alloc((void **)&sh->Cb, cbytes);
+    for (float *&m : sh->maps)
+        alloc((void **)&m, (size_t)n * n * sizeof(float));
+    if (rc == SLICER_OK) {
+        std::vector<double2> tw(n);
+        const long double two_pi = 6.283185307179586476925286766559005768L;
+        for (int j = 0; j < n; j++) {
+            const long double t = two_pi * (long double)j / (long double)n;
+            tw[j] = make_double2((double)cosl(t), (double)-sinl(t));
+        }
+        hipError_t e = hipMemcpyAsync(sh->tw, tw.data(), n * sizeof(double2), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess)
+            e = hipStreamSynchronize(st);  // tw is a host temporary
+        if (e != hipSuccess)
+            rc = sfail(sh, SLICER_ERR_HIP, "slicer_shear_create: twiddle upload: %s", hipGetErrorString(e));
+    }
+    if (rc != SLICER_OK) {
+        release(sh);
+        return rc;
+    }
+    *out = sh;
+    return SLICER_OK;
+}
+
+int slicer_shear_run(slicer_shear_handle sh, const float *d_kappa)
+{
+    if (!sh || !d_kappa)
+        return sfail(sh, SLICER_ERR_ARG, "slicer_shear_run: null argument");
+    hipStream_t st;
+    if (int rc = stream_of(sh, &st))
+        return rc;
+    const int n = sh->n, H = sh->H, len = sh->len;
+    const bool even = n % 2 == 0;
+    PassArgs proto{};
+    const double c = 2.0 * M_PI / (sh->angle * M_PI / 180.0);  // K = c * (fftfreq index)
+    proto.phi_c = -2.0 / (c * c);
+    proto.scale = 1.0 / ((double)n * (double)n);
+    // forward: rows of kappa -> A (row layout) -> split + columns -> S (column layout)
+    End e{d_kappa, sh->A, even ? L_REAL_EVEN : L_REAL_PAIR, S_COMPLEX, 0, 0, len, 1};
+    if (int rc = run_chain(sh, st, sh->fwd_rows, false, false, e, proto, sh->B, sh->Cb))
+        return rc;
+    e = End{sh->A, sh->S, even ? L_SPLIT_EVEN : L_SPLIT_PAIR, S_COMPLEX, 0, 0, 1, H};
+    if (int rc = run_chain(sh, st, sh->fwd_cols, true, false, e, proto, sh->B, sh->Cb))
+        return rc;
+    // inverses: filter + columns S -> A; c2r rows A -> maps (gamma1 -> G in f64 first; gamma2 also writes |gamma|)
+    for (int which : {SLICER_SHEAR_PHI, SLICER_SHEAR_GAMMA1, SLICER_SHEAR_GAMMA2}) {
+        PassArgs p = proto;
+        p.filt = which;
+        e = End{sh->S, sh->A, L_FILTER, S_COMPLEX, 0, 0, 1, H};
+        if (int rc = run_chain(sh, st, sh->inv_cols, true, true, e, p, sh->B, sh->Cb))
+            return rc;
+        e = End{sh->A, sh->maps[which], even ? L_C2R_EVEN : L_C2R_PAIR, even ? S_REAL_EVEN : S_REAL_PAIR, 0, 0, 0, 0};
+        if (which == SLICER_SHEAR_GAMMA1) {
+            e.out = sh->G;
+            e.store = S_COMPLEX;
+            e.ls_out = len;
+            e.es_out = 1;
+        } else if (which == SLICER_SHEAR_GAMMA2) {
+            e.out = sh->maps[SLICER_SHEAR_GAMMA1];
+            e.store = even ? S_GAMMA_EVEN : S_GAMMA_PAIR;
+            p.out2 = sh->maps[SLICER_SHEAR_GAMMA2];
+            p.out3 = sh->maps[SLICER_SHEAR_GAMMA];
+            p.aux = sh->G;
+        }
+        if (int rc = run_chain(sh, st, sh->inv_rows, false, true, e, p, sh->B, sh->Cb))
+            return rc;
+    }
+    sh->ran = true;
+    return SLICER_OK;
+}
+
+int slicer_shear_spectrum(slicer_shear_handle sh, double *host)
+{
+    if (!sh || !host)
+        return sfail(sh, SLICER_ERR_ARG, "slicer_shear_spectrum: null argument");
+    if (!sh->ran)
+        return sfail(sh, SLICER_ERR_STATE, "slicer_shear_spectrum before any slicer_shear_run");
+    hipStream_t st;
+    if (int rc = stream_of(sh, &st))
+        return rc;
+    SCHK(sh, hipMemcpyAsync(host, sh->S, (size_t)sh->n * sh->H * sizeof(double2), hipMemcpyDeviceToHost, st));
+    SCHK(sh, hipStreamSynchronize(st));
+    return SLICER_OK;
+}
+
+int slicer_shear_device_map(slicer_shear_handle sh, int32_t which, float **d_map)
+{
+    if (!sh || !d_map)
+        return sfail(sh, SLICER_ERR_ARG, "slicer_shear_device_map: null argument");
+    if (which < SLICER_SHEAR_PHI || which > SLICER_SHEAR_GAMMA)
+        return sfail(sh, SLICER_ERR_ARG, "slicer_shear_device_map: which = %d, expected 0..3", which);
+    if (!sh->ran)
+        return sfail(sh, SLICER_ERR_STATE, "shear maps are available after slicer_shear_run");
+    *d_map = sh->maps[which];
+    return SLICER_OK;
+}
+
+int slicer_shear_read(slicer_shear_handle sh, int32_t which, float *host)
+{
+    float *d = nullptr;
+    if (int rc = slicer_shear_device_map(sh, which, &d))
+        return rc;
+    if (!host)
+        return sfail(sh, SLICER_ERR_ARG, "slicer_shear_read: null host pointer");
+    hipStream_t st;
+    if (int rc = stream_of(sh, &st))
+        return rc;
+    SCHK(sh, hipMemcpyAsync(host, d, (size_t)sh->n * sh->n * sizeof(float), hipMemcpyDeviceToHost, st));
+    SCHK(sh, hipStreamSynchronize(st));
+    return SLICER_OK;
+}
+
+int slicer_shear_destroy(slicer_shear_handle sh)
+{
+    if (!sh)
+        return SLICER_ERR_ARG;
+    void *sp = nullptr;
+    if (slicer_get_stream(sh->h, &sp) == SLICER_OK) {
+        (void)hipSetDevice(sh->device);
+        (void)hipStreamSynchronize((hipStream_t)sp);
+    }
+    release(sh);
+    return SLICER_OK;
+}

@@ -1,7 +1,9 @@
-"""Born-approximation convergence (kappa) maps from the lens planes.
+"""Born-approximation convergence (kappa) maps from the lens planes, and the shear and lensing
+potential maps from them (row N6).
 
 plane_weights wraps the host weights of include/slicer_amd.h (slicer_lensing_weights); Kappa is the device accumulator
-(slicer_kappa_*) bound to a Slicer handle: it reads the finalized plane maps where they are, in HBM.
+(slicer_kappa_*) bound to a Slicer handle: it reads the finalized plane maps where they are, in HBM.  Shear (slicer_shear_*)
+turns one kappa map into phi, gamma1, gamma2 and |gamma| on the same device.
 """
 import ctypes as C
 
@@ -106,4 +108,65 @@ class Kappa:
             self.finalize()
         out = np.empty((self.npix, self.npix), np.float32)
         self._s._chk(_L.slicer_kappa_read(self._kh, int(s), out.ctypes.data))
+        return out
+
+
+SHEAR_PHI, SHEAR_GAMMA1, SHEAR_GAMMA2, SHEAR_GAMMA = 0, 1, 2, 3
+
+
+def shear_supported(npix):
+    """True if Shear takes npix (2 ... 16384, prime factors 2, 3, 5, 7 only); host only, no device needed."""
+    return bool(_L.slicer_shear_supported(int(npix)))
+
+
+class Shear:
+    """Lensing potential phi and shear gamma1, gamma2, |gamma| of npix^2 kappa maps of side angle_deg degrees,
+    computed on the device of `slicer`, on its stream.  read / device_map take SHEAR_*."""
+
+    def __init__(self, slicer: Slicer, npix, angle_deg):
+        self._s = slicer
+        self.npix, self.angle_deg = int(npix), float(angle_deg)
+        sh = C.c_void_p()
+        slicer._chk(_L.slicer_shear_create(slicer._h, self.npix, self.angle_deg, C.byref(sh)))
+        self._sh = sh
+
+    def close(self):
+        if getattr(self, "_sh", None):
+            _L.slicer_shear_destroy(self._sh)
+            self._sh = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def run(self, d_kappa):
+        """d_kappa: device address of an f32 npix^2 map."""
+        self._s._chk(_L.slicer_shear_run(self._sh, int(d_kappa)))
+
+    def run_kappa(self, kappa: Kappa, s):
+        """The map of source s of a Kappa accumulator, where it is."""
+        self.run(kappa.device_map(s))
+
+    def spectrum(self):
+        """rfft2 of the last run's input, [npix, npix // 2 + 1] complex128."""
+        out = np.empty((self.npix, self.npix // 2 + 1), np.complex128)
+        self._s._chk(_L.slicer_shear_spectrum(self._sh, out.ctypes.data))
+        return out
+
+    def device_map(self, which):
+        p = C.c_void_p()
+        self._s._chk(_L.slicer_shear_device_map(self._sh, int(which), C.byref(p)))
+        return p.value
+
+    def read(self, which):
+        out = np.empty((self.npix, self.npix), np.float32)
+        self._s._chk(_L.slicer_shear_read(self._sh, int(which), out.ctypes.data))
         return out
