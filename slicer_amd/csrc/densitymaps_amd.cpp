@@ -2,16 +2,15 @@
 // Host orchestration only; every particle goes through libslicer_amd.so's HIP kernels.
 #include "densitymaps_amd.hpp"
 
-#include <cstdio>
-#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <iostream>
+#include <numeric>
 #include <thread>
 #include <vector>
 
 #include "../../include/slicer_amd.h"
-#include "gadget2_reader.hpp"
+#include "subfile_deposit.hpp"
 
 namespace {
 
@@ -66,9 +65,8 @@ bool ensure_handle(int myid)
     // handle thins from its own copy (slicer_rand_stream_set); the process's stream stays where randomizeBox left it.
     uint32_t stream[31];
     const bool have_stream = slicer_libc_rand_state_get(stream) == SLICER_OK;
-    int rc = slicer_create(dev, 1ull << chunk, &g.h);
-    if (rc != SLICER_OK) {
-        std::cerr << "slicer_amd: " << slicer_last_error(nullptr) << std::endl;
+    if (slicer_create(dev, 1ull << chunk, &g.h) != SLICER_OK) {
+        slicer_amd::fail(nullptr, "slicer_amd");
         g.h = nullptr;
         return false;
     }
@@ -171,25 +169,12 @@ int createDensityMaps(InputParams &p, Lens &lens, Random &random, int isnap, uns
         if (env_int("SLICER_AMD_LOOKAHEAD", 1) && p.snopt == 0 && !p.physical && isnap < (int)lens.fromsnap.size())
             while (n < SLICER_MAX_PLANES && isnap + n < lens.nplanes && same(isnap + n))
                 n++;
-        slicer_plane_desc d{};
-        d.npix = p.npix;
-        d.n_planes = n;
-        d.mas = g.mas;
-        d.accum = g.accum;
-        d.algo = g.algo;
-        d.hydro = p.hydro ? 1 : 0;
-        d.snopt = p.snopt;
-        d.want_type_maps = skip_types ? 0 : 1;
-        d.fov_rad = fovradiants;
-        for (int j = 0; j < n; j++) {
-            d.ld[j] = lens.ld[isnap + j];
-            d.ld2[j] = lens.ld2[isnap + j];
-            d.nrepperp[j] = lens.nrepperp[isnap + j];
-        }
-        if (slicer_plane_begin(h, &d) != SLICER_OK) {
-            std::cerr << "slicer_amd: " << slicer_last_error(h) << std::endl;
-            return 1;
-        }
+        std::vector<int> planes(n);
+        std::iota(planes.begin(), planes.end(), isnap);
+        const slicer_plane_desc d = slicer_amd::plane_desc(p, lens, planes, g.mas, g.accum, g.algo, skip_types ? 0 : 1,
+                                                           fovradiants);
+        if (slicer_plane_begin(h, &d) != SLICER_OK)
+            return slicer_amd::fail(h, "slicer_amd");
         if (n > 1) {
             made_group = true;
             G.first = isnap;
@@ -210,81 +195,10 @@ int createDensityMaps(InputParams &p, Lens &lens, Random &random, int isnap, uns
     }
 
     for (unsigned int ff = ffmin; ff < ffmax && !hit; ff++) {
-        char suffix[32];
-        snprintf(suffix, sizeof suffix, "%i", (int)ff);  // sconv(ff, fINT)
-        const std::string file_in = File + "." + suffix;
-        slicer_amd::SnapshotFile snap;
-        if (!snap.open(file_in)) {
-            std::cerr << "Error in opening the file: " << file_in << "!\n\a";  // gadget2io.cpp:20
+        // sconv(ff, fINT); readPos takes "float rcase" (gadget2io.h:122)
+        if (slicer_amd::deposit_subfile(h, File + "." + std::to_string(ff), p.hydro, random, isnap, (float)rcase,
+                                        "slicer_amd"))
             return 1;
-        }
-        const Header &data = snap.header();
-        long pos_off = 0, pos_bytes = 0;
-        if (!snap.locate_block("POS ", pos_off, pos_bytes)) {
-            std::cerr << "slicer_amd: no POS block in " << snap.path() << std::endl;
-            return 1;
-        }
-        std::vector<float> mass[6];
-        if (p.hydro && !snap.read_masses(mass)) {
-            std::cerr << "slicer_amd: cannot read MASS/BHMA in " << snap.path() << std::endl;
-            return 1;
-        }
-        slicer_file_desc f{};
-        size_t ntot = 0;
-        for (int t = 0; t < 6; t++) {
-            f.npart[t] = data.npart[t];
-            f.massarr[t] = data.massarr[t];
-            ntot += data.npart[t] > 0 ? (size_t)data.npart[t] : 0;
-        }
-        if ((size_t)pos_bytes < 12 * ntot) {
-            std::cerr << "slicer_amd: POS block of " << snap.path() << " is shorter than the header says" << std::endl;
-            return 1;
-        }
-        f.boxsize = data.boxsize;
-        f.sgn[0] = random.sgnX[isnap];
-        f.sgn[1] = random.sgnY[isnap];
-        f.sgn[2] = random.sgnZ[isnap];
-        f.face = random.face[isnap];
-        f.center[0] = random.x0[isnap];
-        f.center[1] = random.y0[isnap];
-        f.center[2] = random.z0[isnap];
-        f.rcase = (float)rcase;  // readPos takes "float rcase" (gadget2io.h:122)
-        if (slicer_file_begin(h, &f) != SLICER_OK) {
-            std::cerr << "slicer_amd: " << slicer_last_error(h) << std::endl;
-            return 1;
-        }
-        // The POS block is streamed straight into the library's pinned staging buffers (no pageable copy of the
-        // block): file reads overlap with the H2D copies and kernels of the previous chunk.
-        struct Span {
-            slicer_amd::SnapshotFile *snap;
-            long base;          // file offset of this type's first particle
-            const float *mass;  // or nullptr
-        };
-        auto fill = [](void *user, float *dst_pos, float *dst_mass, uint64_t first, uint64_t count) -> int {
-            Span *s = static_cast<Span *>(user);
-            if (!s->snap->read_at(s->base + (long)(12 * first), dst_pos, (size_t)(12 * count)))
-                return 1;
-            if (dst_mass)
-                std::copy(s->mass + first, s->mass + first + count, dst_mass);
-            return 0;
-        };
-        size_t off = 0;
-        for (int t = 0; t < 6; t++) {
-            const size_t n = data.npart[t] > 0 ? (size_t)data.npart[t] : 0;
-            if (n) {
-                const float *m = (p.hydro && data.massarr[t] == 0 && !mass[t].empty()) ? mass[t].data() : nullptr;
-                Span span{&snap, pos_off + (long)(12 * off), m};
-                if (slicer_deposit_stream(h, t, n, m != nullptr, fill, &span) != SLICER_OK) {
-                    std::cerr << "slicer_amd: " << slicer_last_error(h) << std::endl;
-                    return 1;
-                }
-            }
-            off += n;
-        }
-        if (slicer_file_end(h) != SLICER_OK) {
-            std::cerr << "slicer_amd: " << slicer_last_error(h) << std::endl;
-            return 1;
-        }
         if (myid == 0)
             std::cout << " done map*tot " << std::endl;
     }
@@ -294,23 +208,19 @@ int createDensityMaps(InputParams &p, Lens &lens, Random &random, int isnap, uns
     int64_t nsel[6] = {0, 0, 0, 0, 0, 0};
     int rc = slicer_plane_read(h, slot, &mapxytot[0], nullptr, nsel);
     if (rc != SLICER_OK) {
-        std::cerr << "slicer_amd: " << slicer_last_error(h) << std::endl;
+        slicer_amd::fail(h, "slicer_amd");
         if (rc == SLICER_ERR_NEGATIVE_COORD)
             std::cerr << "Aborting from Rank " << myid << std::endl;  // densitymaps.cpp:343
         return 1;
     }
     float *d_toti[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (!skip_types && slicer_plane_device_maps(h, slot, nullptr, d_toti) != SLICER_OK) {
-        std::cerr << "slicer_amd: " << slicer_last_error(h) << std::endl;
-        return 1;
-    }
+    if (!skip_types && slicer_plane_device_maps(h, slot, nullptr, d_toti) != SLICER_OK)
+        return slicer_amd::fail(h, "slicer_amd");
     if (zeroer.t.joinable())
         zeroer.t.join();  // every per-type array now reads zero
     for (int i = 0; i < 6; i++) {
-        if (d_toti[i] && slicer_copy_to_host(h, &mapxytoti[i][0], d_toti[i], np2 * sizeof(float)) != SLICER_OK) {
-            std::cerr << "slicer_amd: " << slicer_last_error(h) << std::endl;
-            return 1;
-        }
+        if (d_toti[i] && slicer_copy_to_host(h, &mapxytoti[i][0], d_toti[i], np2 * sizeof(float)) != SLICER_OK)
+            return slicer_amd::fail(h, "slicer_amd");
         ntotxyi[i] = g.true_counts ? (int)nsel[i] : 0;
     }
     if (made_group)

@@ -8,6 +8,7 @@ import pytest
 
 import oracle
 from slicer_amd import gadget, synth
+from test_driver import bump_npart1
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DRIVER = os.path.join(ROOT, "tests", "cpp", "adapter_driver")
@@ -69,6 +70,18 @@ def test_adapter_matches_oracle(tmp_path, hydro):
     # a missing sub-file makes createDensityMaps return 1, as readHeader's failure does (densitymaps.cpp:438)
     r = run_driver(base, 0, 3, npix, fov, ld, ld2, rcase, 1, hydro, str(tmp_path / "x.bin"))
     assert r.returncode == 1 and "Error in opening the file" in r.stderr
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("hydro", [False, True])
+def test_adapter_refuses_a_pos_block_shorter_than_its_header(tmp_path, hydro):
+    """The second sub-file's header claims one particle more than its POS block holds (with hydro, MASS follows POS)."""
+    base, _ = make_files(tmp_path, hydro)
+    bump_npart1(base + ".1")
+    out = str(tmp_path / "maps.bin")
+    r = run_driver(base, 0, 2, 64, 0.25, 3.0, 4.0, 3.0, 1, hydro, out)
+    assert r.returncode == 1 and "shorter than the header says" in r.stderr, r.stderr
+    assert not os.path.exists(out)
 
 
 @pytest.mark.gpu

@@ -353,6 +353,29 @@ def test_a_rank_that_fails_locally_stops_every_rank_before_the_collective(tmp_pa
     assert not [f for f in os.listdir(out) if f.endswith(".fits")]
 
 
+def bump_npart1(path):
+    """Raise npart[1] of a sub-file's header by one in place: its POS block is then one particle short."""
+    with open(path, "r+b") as f:
+        f.seek(20)   # npart: the first 6 int32 of the header
+        npart = np.frombuffer(f.read(24), "<i4").copy()
+        npart[1] += 1
+        f.seek(20)
+        f.write(npart.tobytes())
+
+
+@pytest.mark.gpu
+def test_a_pos_block_shorter_than_its_header_stops_the_run(tmp_path):
+    """A hydro sub-file has its MASS block right after POS: a reader that trusted the header would deposit the POS end
+    marker and the start of the MASS block as one more particle.  The first pass reads snap_003.1, so the run must
+    stop before any plane is written."""
+    ini, _, out = make_cone(tmp_path, hydro=True)
+    bump_npart1(str(tmp_path / "snapdir_003/snap_003.1"))
+    r = run([ini, "--ngp"])
+    assert r.returncode == 1, r.stderr[-2000:]
+    assert "shorter than the header says" in r.stderr
+    assert not [f for f in os.listdir(out) if f.endswith(".fits")]
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("single_plane", [False, True])
 def test_shot_noise_thinning_through_the_driver_matches_the_oracle(tmp_path, single_plane):
