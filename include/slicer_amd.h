@@ -360,6 +360,40 @@ int slicer_shear_device_map(slicer_shear_handle sh, int32_t which, float **d_map
 int slicer_shear_read(slicer_shear_handle sh, int32_t which, float *host);
 int slicer_shear_destroy(slicer_shear_handle sh);
 
+/* ---- Binned auto and cross power spectra of kappa maps ----
+ * For n_maps maps kappa_s of npix^2 pixels (row i0 slow, i1 contiguous) of side theta = angle_deg * pi / 180 radians:
+ * khat_s = rfft2(kappa_s) in f64 on the [npix][npix/2+1] half plane (the spectrum of slicer_shear_run).  Mode (i0, i1)
+ * has j0 = the signed fftfreq index of i0, j1 = i1, the integer m2 = j0^2 + j1^2 and ell = l_f sqrt(m2), with
+ * l_f = 2 pi / theta.  Edges r_0 < ... < r_B are radii in units of l_f; a mode is in bin b iff
+ * r_b * r_b <= m2 < r_{b+1} * r_{b+1} (the squares rounded to f64), the last bin closed on the right; other modes are
+ * dropped.  edges = NULL: 0, 1, ..., npix-1 (n_edges must then be npix).  Every half-plane coefficient is one mode.
+ *   counts[b] = N_b,  mean_radius[b] = mean of sqrt(m2) over the bin (NaN if N_b = 0),
+ *   C_st,b = theta^2 / npix^4 * (1 / N_b) * sum over the bin of Re(khat_s conj khat_t)   (NaN if N_b = 0).
+ *   slicer_power_bins      N_b and the mean radii, host only (no device); messages through slicer_last_error(NULL)
+ *   slicer_power_create    on the device and stream of h (create it after any slicer_set_stream, destroy it before h);
+ *                          reads the shear_split option.  cross = 0: the n_maps auto-spectra; cross = 1: all
+ *                          n_maps (n_maps + 1) / 2 pairs (0,0), (0,1), ..., (0,S-1), (1,1), ...  Refused before any
+ *                          allocation: npix that slicer_shear_supported rejects or n_maps outside 1..128
+ *                          (SLICER_ERR_UNSUPPORTED); bad edges (fewer than 2, negative, not finite, not strictly
+ *                          ascending) or an angle that is not positive and finite (SLICER_ERR_ARG).  Device memory:
+ *                          the transform's buffers plus one (cross = 0) or n_maps (cross = 1) spectra of
+ *                          16 npix (npix/2+1) bytes (SLICER_ERR_NOMEM).
+ *   slicer_power_run       n_maps device f32 maps (e.g. slicer_kappa_device_map); enqueued, no synchronisation
+ *   slicer_power_spectrum  khat of map `map` of the last run, [npix][npix/2+1] (re, im) f64 pairs, bitwise equal to
+ *                          slicer_shear_spectrum under the same shear_split; with cross = 0 only the last map's is kept
+ *                          (others: SLICER_ERR_STATE); waits for the stream
+ *   slicer_power_read      cl [pairs][n_edges-1], ell_mean = l_f * mean_radius and counts [n_edges-1] of the last run
+ *                          (any of them NULL); waits for the stream.  Before any run: SLICER_ERR_STATE.
+ * No atomics: the same maps give bitwise the same spectra, and C_ss is the same with cross = 0 and cross = 1. */
+int slicer_power_bins(int32_t npix, int32_t n_edges, const double *edges, int64_t *counts, double *mean_radius);
+typedef struct slicer_power_s *slicer_power_handle;
+int slicer_power_create(slicer_handle h, int32_t npix, double angle_deg, int32_t n_maps, int32_t cross,
+                        int32_t n_edges, const double *edges, slicer_power_handle *out);
+int slicer_power_run(slicer_power_handle ph, const float *const *d_maps);
+int slicer_power_spectrum(slicer_power_handle ph, int32_t map, double *host);
+int slicer_power_read(slicer_power_handle ph, double *cl, double *ell_mean, int64_t *counts);
+int slicer_power_destroy(slicer_power_handle ph);
+
 /* per-kernel HIP-event timing (off by default; adds two event records per launch) */
 int slicer_profile_enable(slicer_handle h, int on);
 int slicer_profile_reset(slicer_handle h);

@@ -7,7 +7,7 @@ from . import _lib, gadget, synth  # noqa: F401
 from .api import (ACC_F32, ACC_F64, ACC_FIXED64, ALGO_AUTO, ALGO_BINNED, ALGO_DIRECT, ELEM_F32, ELEM_F64,  # noqa: F401
                   ELEM_FIXED64, MAS_NGP, MAS_TSC, InputParams, Lens, Random, Slicer, SlicerError, createDensityMaps)
 
-from .lensing import (SHEAR_GAMMA, SHEAR_GAMMA1, SHEAR_GAMMA2, SHEAR_PHI, Kappa, Shear,  # noqa: F401
-                      plane_weights, shear_supported)
+from .lensing import (SHEAR_GAMMA, SHEAR_GAMMA1, SHEAR_GAMMA2, SHEAR_PHI, Kappa, Power, Shear,  # noqa: F401
+                      ell_fundamental, plane_weights, power_bins, shear_supported)
 
 __version__ = "0.2.0"

@@ -37,8 +37,12 @@ struct ProfEntry {
 };
 
 const char *kKernelNames[] = {"direct_deposit", "finalize_tsc", "fold_ngp",  "synth",         "project_bin",
-                              "bin_scan",       "bin_scatter",  "tile_deposit", "debug_project", "bin_sort"};
-enum { KN_DIRECT = 0, KN_FINALIZE, KN_FOLD, KN_SYNTH, KN_PROJECT, KN_SCAN, KN_SCATTER, KN_TILE, KN_DEBUG, KN_SORT2, KN_COUNT };
+                              "bin_scan",       "bin_scatter",  "tile_deposit", "debug_project", "bin_sort",
+                              "power_fft",      "power_bin"};
+enum {
+    KN_DIRECT = 0, KN_FINALIZE, KN_FOLD, KN_SYNTH, KN_PROJECT, KN_SCAN, KN_SCATTER, KN_TILE, KN_DEBUG, KN_SORT2,
+    KN_POWER_FFT, KN_POWER_BIN, KN_COUNT
+};
 
 }  // namespace
 
@@ -1460,6 +1464,17 @@ __attribute__((visibility("hidden"))) int slicer_internal_fail(slicer_handle h, 
 {
     return fail(h, code, "%s", msg);
 }
+
+// slicer_power.hip times its forward transforms (which = 0) and its binning (1) through the handle's profile: a scope
+// opened here (nullptr when profiling is off) and closed by slicer_internal_prof_end after the launches.  Not exported.
+__attribute__((visibility("hidden"))) void *slicer_internal_prof_begin(slicer_handle h, int which)
+{
+    if (!h || !h->profiling)
+        return nullptr;
+    return new (std::nothrow) ProfScope(h, which == 0 ? KN_POWER_FFT : KN_POWER_BIN);
+}
+
+__attribute__((visibility("hidden"))) void slicer_internal_prof_end(void *scope) { delete (ProfScope *)scope; }
 
 int slicer_create(int device, uint64_t max_chunk, slicer_handle *out)
 {

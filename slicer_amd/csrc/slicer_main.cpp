@@ -15,12 +15,17 @@
 //     --kappa-no-growth drops its linear-growth correction.  Without --kappa the run is unchanged.
 //   * --shear (with --kappa) also writes, per source, the shear maps gamma1, gamma2, |gamma| and the lensing potential
 //     phi computed on device 0 from the kappa map (the reference's Lens/smr.py).
+//   * --power auto|cross (with --kappa) also writes <directory><simulation>.cl_<npix>_<suffix>.txt: the binned auto
+//     (or auto and cross) power spectra C_l of the kappa maps, computed on device 0 (Lens/smr.py's PS without its
+//     defects); --power-edges r0,r1,... sets the bin edges in units of l_f = 2 pi / ANGLE
+//     (default 0, 1, ..., npix-1).
 //   * SubFind / halo-catalogue mode (npix == 0) is not supported; with snopt > 0 and several devices every rank thread
 //     draws from its own copy of the libc stream, like the reference's MPI ranks (Ranks::create).
 #include <dlfcn.h>
 #include <sys/stat.h>
 
 #include <algorithm>
+#include <cmath>
 #include <condition_variable>
 #include <mutex>
 #include <cstdio>
@@ -268,6 +273,8 @@ int host_plane_reduce(vector<Rank> &ranks, int npix, int n_planes)
 struct Options {
     string inifile, plan_path, devices_spec, reduce_mode = "rccl", reduce_algo = "rooted", kappa_spec;
     bool kappa_growth = true, shear = false;
+    string power;                // "", "auto" or "cross"
+    vector<double> power_edges;  // empty: the default edges
     int device = 0, mas = SLICER_MAS_TSC, accum = SLICER_ACC_F32;
     bool plan_only = false, single_plane = false, reference_counts = false, replication = false;
 };
@@ -293,6 +300,18 @@ int parse_args(int argc, char **argv, Options &o)
         else if (a == "--kappa" && i + 1 < argc) o.kappa_spec = argv[++i];  // all | z1,z2,...
         else if (a == "--kappa-no-growth") o.kappa_growth = false;
         else if (a == "--shear") o.shear = true;
+        else if (a == "--power" && i + 1 < argc) o.power = argv[++i];  // auto | cross
+        else if (a == "--power-edges" && i + 1 < argc) {
+            for (const string &tok : split(argv[++i])) {
+                char *end = nullptr;
+                const double r = strtod(tok.c_str(), &end);
+                if (tok.empty() || *end != '\0') {
+                    cerr << "bad --power-edges (a comma-separated list of radii in units of l_f)" << endl;
+                    return 2;
+                }
+                o.power_edges.push_back(r);
+            }
+        }
         else if (o.inifile.empty()) o.inifile = a;
         else {
             cerr << "unknown argument " << a << endl;
@@ -305,6 +324,18 @@ int parse_args(int argc, char **argv, Options &o)
     }
     if (o.shear && o.kappa_spec.empty()) {
         cerr << "--shear needs --kappa (the shear maps are computed from the kappa maps)" << endl;
+        return 2;
+    }
+    if (!o.power.empty() && o.power != "auto" && o.power != "cross") {
+        cerr << "bad --power (auto or cross)" << endl;
+        return 2;
+    }
+    if (!o.power.empty() && o.kappa_spec.empty()) {
+        cerr << "--power needs --kappa (the power spectra are those of the kappa maps)" << endl;
+        return 2;
+    }
+    if (!o.power_edges.empty() && o.power.empty()) {
+        cerr << "--power-edges needs --power" << endl;
         return 2;
     }
     return 0;
@@ -344,6 +375,20 @@ int plan_cone(const Options &o, Cone &c)
     if (o.shear && !slicer_shear_supported(p.npix)) {
         cerr << "--shear: npix = " << p.npix << " is not supported (2 ... 16384, prime factors 2, 3, 5, 7 only)" << endl;
         return 2;
+    }
+    if (!o.power.empty() && !slicer_shear_supported(p.npix)) {
+        cerr << "--power: npix = " << p.npix << " is not supported (2 ... 16384, prime factors 2, 3, 5, 7 only)" << endl;
+        return 2;
+    }
+    if (!o.power.empty()) {  // the edges, checked on the host before any device work
+        const int ne = o.power_edges.empty() ? p.npix : (int)o.power_edges.size();
+        vector<int64_t> cnt(std::max(ne - 1, 1));
+        vector<double> mr(cnt.size());
+        if (slicer_power_bins(p.npix, ne, o.power_edges.empty() ? nullptr : o.power_edges.data(), cnt.data(),
+                              mr.data()) != SLICER_OK) {
+            cerr << "--power-edges: " << slicer_last_error(nullptr) << endl;
+            return 2;
+        }
     }
     if (p.simType == "SubFind") {
         cerr << "SubFind / halo light-cone mode (npix == 0) is outside this driver's scope" << endl;
@@ -475,7 +520,8 @@ struct Ranks {
     }
 };
 
-// --kappa / --shear: the kappa maps, and the shear maps computed from them, on the root handle.  Declared after the
+// --kappa / --shear / --power: the kappa maps, and the shear maps and power spectra computed from them, on the root
+// handle.  Declared after the
 // Ranks, so that it is released before its parent handle.
 struct LensingOutputs {
     const slicer_handle h;
@@ -484,12 +530,17 @@ struct LensingOutputs {
     const vector<double> &zs, &coeff;  // source redshifts; coeff[s * nplanes + i] = c[s][i] (kappa_weights)
     slicer_kappa_handle kh = nullptr;  // nullptr without --kappa
     slicer_shear_handle shh = nullptr;
+    slicer_power_handle ph = nullptr;
+    string power_mode{};           // "", "auto" or "cross"
+    vector<double> power_edges{};  // empty: 0 .. npix-1
     vector<float *> upload{};  // device buffers for planes read back from their files
 
     ~LensingOutputs()
     {
         for (float *b : upload)
             slicer_device_free(h, b);
+        if (ph)
+            slicer_power_destroy(ph);
         if (shh)
             slicer_shear_destroy(shh);
         if (kh)
@@ -502,6 +553,16 @@ struct LensingOutputs {
             return fail(h, "slicer_amd: --kappa");
         if (kh && shear && slicer_shear_create(h, p.npix, p.fov, &shh) != SLICER_OK)
             return fail(h, "slicer_amd: --shear");
+        if (kh && !power_mode.empty()) {
+            const int ne = power_edges.empty() ? p.npix : (int)power_edges.size();
+            if ((int)zs.size() > 128) {
+                cerr << "slicer_amd: --power: " << zs.size() << " sources, at most 128" << endl;
+                return 2;
+            }
+            if (slicer_power_create(h, p.npix, p.fov, (int)zs.size(), power_mode == "cross", ne,
+                                    power_edges.empty() ? nullptr : power_edges.data(), &ph) != SLICER_OK)
+                return fail(h, "slicer_amd: --power");
+        }
         return 0;
     }
 
@@ -585,6 +646,58 @@ struct LensingOutputs {
             for (const auto &o : outs)
                 if (slicer_shear_read(shh, o.which, map.data()) != SLICER_OK || !save("shear", o.token, zbuf, map, keys))
                     return fail(h, "slicer_amd: --kappa");
+        }
+        return ph ? write_power() : 0;
+    }
+
+    // The binned spectra of the kappa maps, one text file: '#' lines (npix, angle, source redshifts, column names),
+    // then per bin ell_lo ell_hi ell_mean n_modes and C of every pair (%.17g; nan for an empty bin)
+    int write_power()
+    {
+        const int S = (int)zs.size(), ne = power_edges.empty() ? p.npix : (int)power_edges.size(), B = ne - 1;
+        const bool cross = power_mode == "cross";
+        vector<const float *> maps(S);
+        for (int s = 0; s < S; s++) {
+            float *d = nullptr;
+            if (slicer_kappa_device_map(kh, s, &d) != SLICER_OK)
+                return fail(h, "slicer_amd: --power");
+            maps[s] = d;
+        }
+        vector<std::pair<int, int>> pairs;
+        for (int s = 0; s < S; s++)
+            for (int t = s; t < (cross ? S : s + 1); t++)
+                pairs.emplace_back(s, t);
+        vector<double> cl(pairs.size() * B), ell(B);
+        vector<int64_t> counts(B);
+        if (slicer_power_run(ph, maps.data()) != SLICER_OK ||
+            slicer_power_read(ph, cl.data(), ell.data(), counts.data()) != SLICER_OK)
+            return fail(h, "slicer_amd: --power");
+        const string path = p.directory + p.simulation + ".cl_" + p.snpix + "_" + p.suffix + ".txt";
+        cout << "Saving the power spectra on: " << path << endl;
+        FILE *f = fopen(path.c_str(), "w");
+        if (!f) {
+            cerr << "It was not possible to create the file: " << path << endl;
+            return 1;
+        }
+        const double ell_f = 2.0 * M_PI / (p.fov * M_PI / 180.0);
+        fprintf(f, "# npix %d\n# angle_deg %.17g\n# zs", p.npix, p.fov);
+        for (double z : zs)
+            fprintf(f, " %.17g", z);
+        fprintf(f, "\n# ell_lo ell_hi ell_mean n_modes");
+        for (const auto &pr : pairs)
+            fprintf(f, " C_%d_%d", pr.first, pr.second);
+        fprintf(f, "\n");
+        for (int b = 0; b < B; b++) {
+            const double lo = power_edges.empty() ? (double)b : power_edges[b];
+            const double hi = power_edges.empty() ? (double)(b + 1) : power_edges[b + 1];
+            fprintf(f, "%.17g %.17g %.17g %lld", lo * ell_f, hi * ell_f, ell[b], (long long)counts[b]);
+            for (size_t q = 0; q < pairs.size(); q++)
+                fprintf(f, " %.17g", cl[q * B + b]);
+            fprintf(f, "\n");
+        }
+        if (fclose(f) != 0) {
+            cerr << "It was not possible to write the file: " << path << endl;
+            return 1;
         }
         return 0;
     }
@@ -738,8 +851,10 @@ int main(int argc, char **argv)
     if (const int rc = ranks.create(devs, c.p.snopt, o.reduce_mode == "rccl"))
         return rc;
     LensingOutputs lensing{ranks.root(), c.p, c.lens, kappa_zs, kappa_c};  // (after `ranks`, see there)
-    if (lensing.create(o.shear))
-        return 1;
+    lensing.power_mode = o.power;
+    lensing.power_edges = o.power_edges;
+    if (const int rc = lensing.create(o.shear))
+        return rc;
     const int rc = run_planes(o, c, ranks, lensing);
     return rc == 0 && lensing.kh ? lensing.write() : rc;
 }

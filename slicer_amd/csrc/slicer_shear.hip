@@ -17,7 +17,8 @@
 //                    load; the last row pass rounds to f32.  gamma1's last pass keeps f64 (aux); gamma2's last pass
 //                    reads it and writes gamma1, gamma2 and |gamma|.
 // Twiddles: one f64 table W_n^j = exp(-2 pi i j / n), j < n, from long-double sincos on the host.  No atomics and
-// no work handed between workgroups: the results are bitwise repeatable.
+// no work handed between workgroups: the results are bitwise repeatable.  The plan and the forward chains are shared
+// with the power-spectrum handle (slicer_power.hip) through slicer_fft.hpp.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -28,6 +29,7 @@
 #include <vector>
 
 #include "../../include/slicer_amd.h"
+#include "slicer_fft.hpp"
 
 extern "C" int slicer_internal_fail(slicer_handle h, int code, const char *msg);  // slicer_capi.cpp (not exported)
 
@@ -333,36 +335,43 @@ std::vector<Pass> plan_chain(int L, int nlines, int cap)
 
 }  // namespace
 
-struct slicer_shear_s {
+// The forward transform's plan (slicer_fft.hpp).  The inverses of the shear handle run the same chains backwards.
+struct slicer_fft_s {
     slicer_handle h = nullptr;
     int device = 0;
     int n = 0, H = 0, len = 0, rows = 0;  // rows x len: the row transforms (n x n/2 even, ceil(n/2) x n odd)
-    double angle = 0.0;
-    std::vector<Pass> fwd_rows, fwd_cols, inv_cols, inv_rows;
+    std::vector<Pass> row_chain, col_chain;
     double2 *tw = nullptr;
-    double2 *S = nullptr, *A = nullptr, *B = nullptr, *Cb = nullptr, *G = nullptr;  // complex f64, n * H each
+    double2 *A = nullptr, *B = nullptr, *Cb = nullptr;  // complex f64, n * H each: row output, pass intermediates
+};
+
+struct slicer_shear_s {
+    slicer_handle h = nullptr;
+    slicer_fft_s *fft = nullptr;
+    double angle = 0.0;
+    double2 *S = nullptr, *G = nullptr;  // complex f64, n * H each
     float *maps[4] = {nullptr, nullptr, nullptr, nullptr};
     bool ran = false;
 };
 
 namespace {
 
-int sfail(slicer_shear_handle sh, int code, const char *fmt, ...) __attribute__((format(printf, 3, 4)));
-int sfail(slicer_shear_handle sh, int code, const char *fmt, ...)
+int sfail(slicer_handle h, int code, const char *fmt, ...) __attribute__((format(printf, 3, 4)));
+int sfail(slicer_handle h, int code, const char *fmt, ...)
 {
     char buf[512];
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(buf, sizeof buf, fmt, ap);
     va_end(ap);
-    return slicer_internal_fail(sh ? sh->h : nullptr, code, buf);
+    return slicer_internal_fail(h, code, buf);
 }
 
-#define SCHK(sh, expr)                                                                                            \
+#define SCHK(h, expr)                                                                                             \
     do {                                                                                                          \
         hipError_t e_ = (expr);                                                                                   \
         if (e_ != hipSuccess)                                                                                     \
-            return sfail(sh, e_ == hipErrorOutOfMemory ? SLICER_ERR_NOMEM : SLICER_ERR_HIP, "%s failed: %s (%s:%d)", \
+            return sfail(h, e_ == hipErrorOutOfMemory ? SLICER_ERR_NOMEM : SLICER_ERR_HIP, "%s failed: %s (%s:%d)", \
                          #expr, hipGetErrorString(e_), __FILE__, __LINE__);                                       \
     } while (0)
 
@@ -372,14 +381,17 @@ int stream_of(slicer_shear_handle sh, hipStream_t *st)
     if (slicer_get_stream(sh->h, &p) != SLICER_OK)
         return SLICER_ERR_ARG;
     *st = (hipStream_t)p;
-    SCHK(sh, hipSetDevice(sh->device));
+    SCHK(sh->h, hipSetDevice(sh->fft->device));
     return SLICER_OK;
 }
 
 void release(slicer_shear_handle sh)
 {
-    (void)hipSetDevice(sh->device);
-    for (void *p : {(void *)sh->tw, (void *)sh->S, (void *)sh->A, (void *)sh->B, (void *)sh->Cb, (void *)sh->G})
+    if (sh->fft) {
+        (void)hipSetDevice(sh->fft->device);
+        slicer_fft_destroy(sh->fft);
+    }
+    for (void *p : {(void *)sh->S, (void *)sh->G})
         if (p)
             (void)hipFree(p);
     for (float *p : sh->maps)
@@ -396,22 +408,22 @@ struct End {
     int ls_in, es_in, ls_out, es_out;
 };
 
-// Launch the passes of one chain; intermediates alternate between x and y (neither is e.in nor e.out).
-int run_chain(slicer_shear_handle sh, hipStream_t st, const std::vector<Pass> &passes, bool cols, bool inv,
-              const End &e, const PassArgs &proto, double2 *x, double2 *y)
+// Launch the passes of one chain; intermediates alternate between f->B and f->Cb (neither is e.in nor e.out).
+int run_chain(slicer_fft_s *f, hipStream_t st, const std::vector<Pass> &passes, bool cols, bool inv, const End &e,
+              const PassArgs &proto)
 {
     const int m = (int)passes.size();
-    const int ls = cols ? 1 : sh->len, es = cols ? sh->H : 1;  // intermediate layout of the chain's domain
+    const int ls = cols ? 1 : f->len, es = cols ? f->H : 1;  // intermediate layout of the chain's domain
     const void *in = e.in;
     for (int p = 0; p < m; p++) {
         const Pass &ps = passes[p];
         PassArgs a = proto;
-        a.tw = sh->tw;
-        a.n = sh->n;
-        a.H = sh->H;
-        a.len = sh->len;
-        a.L = cols ? sh->n : sh->len;
-        a.nlines = cols ? sh->H : sh->rows;
+        a.tw = f->tw;
+        a.n = f->n;
+        a.H = f->H;
+        a.len = f->len;
+        a.L = cols ? f->n : f->len;
+        a.nlines = cols ? f->H : f->rows;
         a.R = ps.R;
         a.Ns = ps.Ns;
         a.C = ps.C;
@@ -431,7 +443,7 @@ int run_chain(slicer_shear_handle sh, hipStream_t st, const std::vector<Pass> &p
             a.ls_out = e.ls_out;
             a.es_out = e.es_out;
         } else {
-            a.out = (m - 2 - p) % 2 == 0 ? x : y;
+            a.out = (m - 2 - p) % 2 == 0 ? f->B : f->Cb;
             a.store = S_COMPLEX;
             a.ls_out = ls;
             a.es_out = es;
@@ -439,13 +451,98 @@ int run_chain(slicer_shear_handle sh, hipStream_t st, const std::vector<Pass> &p
         const size_t lds = (size_t)ps.C * ps.Rp * sizeof(double2);
         const dim3 grid((unsigned)((a.nlines + ps.C - 1) / ps.C), (unsigned)(a.L / ps.R));
         hipLaunchKernelGGL(k_fft_pass, grid, dim3(kThreads), lds, st, a);
-        SCHK(sh, hipGetLastError());
+        SCHK(f->h, hipGetLastError());
         in = a.out;
     }
     return SLICER_OK;
 }
 
 }  // namespace
+
+int slicer_fft_create(slicer_handle h, int npix, int split, hipStream_t st, const char *who, slicer_fft_s **out)
+{
+    *out = nullptr;
+    slicer_fft_s *f = new (std::nothrow) slicer_fft_s;
+    if (!f)
+        return slicer_internal_fail(h, SLICER_ERR_NOMEM, "out of host memory");
+    const int n = npix;
+    f->h = h;
+    f->n = n;
+    f->H = n / 2 + 1;
+    f->len = n % 2 == 0 ? n / 2 : n;
+    f->rows = n % 2 == 0 ? n : (n + 1) / 2;
+    auto cap = [&](int L, int c) { return split ? std::max(2, (int)std::floor(std::sqrt((double)L))) : c; };
+    f->row_chain = plan_chain(f->len, f->rows, cap(f->len, kLdsPoints));
+    f->col_chain = plan_chain(n, f->H, cap(n, kColCap));
+    const size_t passes = std::max(f->row_chain.size(), f->col_chain.size());
+
+    int rc = SLICER_OK, dev = 0;
+    if (hipStreamGetDevice(st, &dev) != hipSuccess)
+        rc = sfail(h, SLICER_ERR_HIP, "%s: the handle's stream has no device", who);
+    f->device = dev;
+    if (rc == SLICER_OK && hipSetDevice(dev) != hipSuccess)
+        rc = sfail(h, SLICER_ERR_HIP, "hipSetDevice(%d) failed", dev);
+    if (rc == SLICER_OK &&
+        hipFuncSetAttribute((const void *)k_fft_pass, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)((kLdsPoints + kMaxLines) * sizeof(double2))) != hipSuccess)
+        rc = sfail(h, SLICER_ERR_HIP, "%s: cannot raise the LDS limit of the FFT kernel", who);
+    auto alloc = [&](void **p, size_t bytes) {
+        if (rc != SLICER_OK)
+            return;
+        hipError_t e = hipMalloc(p, bytes);
+        if (e != hipSuccess)
+            rc = sfail(h, e == hipErrorOutOfMemory ? SLICER_ERR_NOMEM : SLICER_ERR_HIP,
+                       "%s: %zu bytes of device memory: %s", who, bytes, hipGetErrorString(e));
+    };
+    const size_t cbytes = (size_t)n * f->H * sizeof(double2);
+    alloc((void **)&f->tw, (size_t)n * sizeof(double2));
+    alloc((void **)&f->A, cbytes);
+    if (passes >= 2)
+        alloc((void **)&f->B, cbytes);
+    if (passes >= 3)
+        alloc((void **)&f->Cb, cbytes);
+    if (rc == SLICER_OK) {
+        std::vector<double2> tw(n);
+        const long double two_pi = 6.283185307179586476925286766559005768L;
+        for (int j = 0; j < n; j++) {
+            const long double t = two_pi * (long double)j / (long double)n;
+            tw[j] = make_double2((double)cosl(t), (double)-sinl(t));
+        }
+        hipError_t e = hipMemcpyAsync(f->tw, tw.data(), n * sizeof(double2), hipMemcpyHostToDevice, st);
+        if (e == hipSuccess)
+            e = hipStreamSynchronize(st);  // tw is a host temporary
+        if (e != hipSuccess)
+            rc = sfail(h, SLICER_ERR_HIP, "%s: twiddle upload: %s", who, hipGetErrorString(e));
+    }
+    if (rc != SLICER_OK) {
+        slicer_fft_destroy(f);
+        return rc;
+    }
+    *out = f;
+    return SLICER_OK;
+}
+
+int slicer_fft_forward(slicer_fft_s *f, hipStream_t st, const float *map, double2 *khat)
+{
+    const bool even = f->n % 2 == 0;
+    const PassArgs proto{};
+    // rows of the map -> A (row layout) -> split + columns -> khat (column layout)
+    End e{map, f->A, even ? L_REAL_EVEN : L_REAL_PAIR, S_COMPLEX, 0, 0, f->len, 1};
+    if (int rc = run_chain(f, st, f->row_chain, false, false, e, proto))
+        return rc;
+    e = End{f->A, khat, even ? L_SPLIT_EVEN : L_SPLIT_PAIR, S_COMPLEX, 0, 0, 1, f->H};
+    return run_chain(f, st, f->col_chain, true, false, e, proto);
+}
+
+void slicer_fft_destroy(slicer_fft_s *f)
+{
+    if (!f)
+        return;
+    for (void *p : {(void *)f->tw, (void *)f->A, (void *)f->B, (void *)f->Cb})
+        if (p)
+            (void)hipFree(p);
+    delete f;
+}
 
 int slicer_shear_supported(int32_t n) { return smooth(n) ? 1 : 0; }
 
@@ -470,63 +567,26 @@ int slicer_shear_create(slicer_handle h, int32_t npix, double angle_deg, slicer_
         return slicer_internal_fail(h, SLICER_ERR_NOMEM, "out of host memory");
     const int n = npix;
     sh->h = h;
-    sh->n = n;
-    sh->H = n / 2 + 1;
-    sh->len = n % 2 == 0 ? n / 2 : n;
-    sh->rows = n % 2 == 0 ? n : (n + 1) / 2;
     sh->angle = angle_deg;
-    auto cap = [&](int L, int c) { return split ? std::max(2, (int)std::floor(std::sqrt((double)L))) : c; };
-    sh->fwd_rows = plan_chain(sh->len, sh->rows, cap(sh->len, kLdsPoints));
-    sh->fwd_cols = plan_chain(n, sh->H, cap(n, kColCap));
-    sh->inv_cols = sh->fwd_cols;
-    sh->inv_rows = sh->fwd_rows;
-    const size_t passes = std::max(sh->fwd_rows.size(), sh->fwd_cols.size());
 
     void *sp = nullptr;
-    int dev = 0;
     int rc = slicer_get_stream(h, &sp);
     hipStream_t st = (hipStream_t)sp;
-    if (rc == SLICER_OK && hipStreamGetDevice(st, &dev) != hipSuccess)
-        rc = sfail(sh, SLICER_ERR_HIP, "slicer_shear_create: the handle's stream has no device");
-    sh->device = dev;
-    if (rc == SLICER_OK && hipSetDevice(dev) != hipSuccess)
-        rc = sfail(sh, SLICER_ERR_HIP, "hipSetDevice(%d) failed", dev);
-    if (rc == SLICER_OK &&
-        hipFuncSetAttribute((const void *)k_fft_pass, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)((kLdsPoints + kMaxLines) * sizeof(double2))) != hipSuccess)
-        rc = sfail(sh, SLICER_ERR_HIP, "slicer_shear_create: cannot raise the LDS limit of the FFT kernel");
+    if (rc == SLICER_OK)
+        rc = slicer_fft_create(h, n, split, st, "slicer_shear_create", &sh->fft);
     auto alloc = [&](void **p, size_t bytes) {
         if (rc != SLICER_OK)
             return;
         hipError_t e = hipMalloc(p, bytes);
         if (e != hipSuccess)
-            rc = sfail(sh, e == hipErrorOutOfMemory ? SLICER_ERR_NOMEM : SLICER_ERR_HIP,
+            rc = sfail(h, e == hipErrorOutOfMemory ? SLICER_ERR_NOMEM : SLICER_ERR_HIP,
                        "slicer_shear_create: %zu bytes of device memory: %s", bytes, hipGetErrorString(e));
     };
-    const size_t cbytes = (size_t)n * sh->H * sizeof(double2);
-    alloc((void **)&sh->tw, (size_t)n * sizeof(double2));
+    const size_t cbytes = (size_t)n * (n / 2 + 1) * sizeof(double2);
     alloc((void **)&sh->S, cbytes);
-    alloc((void **)&sh->A, cbytes);
     alloc((void **)&sh->G, cbytes);
-    if (passes >= 2)
-        alloc((void **)&sh->B, cbytes);
-    if (passes >= 3)
-        alloc((void **)&sh->Cb, cbytes);
     for (float *&m : sh->maps)
         alloc((void **)&m, (size_t)n * n * sizeof(float));
-    if (rc == SLICER_OK) {
-        std::vector<double2> tw(n);
-        const long double two_pi = 6.283185307179586476925286766559005768L;
-        for (int j = 0; j < n; j++) {
-            const long double t = two_pi * (long double)j / (long double)n;
-            tw[j] = make_double2((double)cosl(t), (double)-sinl(t));
-        }
-        hipError_t e = hipMemcpyAsync(sh->tw, tw.data(), n * sizeof(double2), hipMemcpyHostToDevice, st);
-        if (e == hipSuccess)
-            e = hipStreamSynchronize(st);  // tw is a host temporary
-        if (e != hipSuccess)
-            rc = sfail(sh, SLICER_ERR_HIP, "slicer_shear_create: twiddle upload: %s", hipGetErrorString(e));
-    }
     if (rc != SLICER_OK) {
         release(sh);
         return rc;
@@ -538,31 +598,27 @@ int slicer_shear_create(slicer_handle h, int32_t npix, double angle_deg, slicer_
 int slicer_shear_run(slicer_shear_handle sh, const float *d_kappa)
 {
     if (!sh || !d_kappa)
-        return sfail(sh, SLICER_ERR_ARG, "slicer_shear_run: null argument");
+        return sfail(sh ? sh->h : nullptr, SLICER_ERR_ARG, "slicer_shear_run: null argument");
     hipStream_t st;
     if (int rc = stream_of(sh, &st))
         return rc;
-    const int n = sh->n, H = sh->H, len = sh->len;
+    slicer_fft_s *f = sh->fft;
+    const int n = f->n, H = f->H, len = f->len;
     const bool even = n % 2 == 0;
     PassArgs proto{};
     const double c = 2.0 * M_PI / (sh->angle * M_PI / 180.0);  // K = c * (fftfreq index)
     proto.phi_c = -2.0 / (c * c);
     proto.scale = 1.0 / ((double)n * (double)n);
-    // forward: rows of kappa -> A (row layout) -> split + columns -> S (column layout)
-    End e{d_kappa, sh->A, even ? L_REAL_EVEN : L_REAL_PAIR, S_COMPLEX, 0, 0, len, 1};
-    if (int rc = run_chain(sh, st, sh->fwd_rows, false, false, e, proto, sh->B, sh->Cb))
-        return rc;
-    e = End{sh->A, sh->S, even ? L_SPLIT_EVEN : L_SPLIT_PAIR, S_COMPLEX, 0, 0, 1, H};
-    if (int rc = run_chain(sh, st, sh->fwd_cols, true, false, e, proto, sh->B, sh->Cb))
+    if (int rc = slicer_fft_forward(f, st, d_kappa, sh->S))
         return rc;
     // inverses: filter + columns S -> A; c2r rows A -> maps (gamma1 -> G in f64 first; gamma2 also writes |gamma|)
     for (int which : {SLICER_SHEAR_PHI, SLICER_SHEAR_GAMMA1, SLICER_SHEAR_GAMMA2}) {
         PassArgs p = proto;
         p.filt = which;
-        e = End{sh->S, sh->A, L_FILTER, S_COMPLEX, 0, 0, 1, H};
-        if (int rc = run_chain(sh, st, sh->inv_cols, true, true, e, p, sh->B, sh->Cb))
+        End e{sh->S, f->A, L_FILTER, S_COMPLEX, 0, 0, 1, H};
+        if (int rc = run_chain(f, st, f->col_chain, true, true, e, p))
             return rc;
-        e = End{sh->A, sh->maps[which], even ? L_C2R_EVEN : L_C2R_PAIR, even ? S_REAL_EVEN : S_REAL_PAIR, 0, 0, 0, 0};
+        e = End{f->A, sh->maps[which], even ? L_C2R_EVEN : L_C2R_PAIR, even ? S_REAL_EVEN : S_REAL_PAIR, 0, 0, 0, 0};
         if (which == SLICER_SHEAR_GAMMA1) {
             e.out = sh->G;
             e.store = S_COMPLEX;
@@ -575,7 +631,7 @@ int slicer_shear_run(slicer_shear_handle sh, const float *d_kappa)
             p.out3 = sh->maps[SLICER_SHEAR_GAMMA];
             p.aux = sh->G;
         }
-        if (int rc = run_chain(sh, st, sh->inv_rows, false, true, e, p, sh->B, sh->Cb))
+        if (int rc = run_chain(f, st, f->row_chain, false, true, e, p))
             return rc;
     }
     sh->ran = true;
@@ -585,25 +641,25 @@ int slicer_shear_run(slicer_shear_handle sh, const float *d_kappa)
 int slicer_shear_spectrum(slicer_shear_handle sh, double *host)
 {
     if (!sh || !host)
-        return sfail(sh, SLICER_ERR_ARG, "slicer_shear_spectrum: null argument");
+        return sfail(sh ? sh->h : nullptr, SLICER_ERR_ARG, "slicer_shear_spectrum: null argument");
     if (!sh->ran)
-        return sfail(sh, SLICER_ERR_STATE, "slicer_shear_spectrum before any slicer_shear_run");
+        return sfail(sh->h, SLICER_ERR_STATE, "slicer_shear_spectrum before any slicer_shear_run");
     hipStream_t st;
     if (int rc = stream_of(sh, &st))
         return rc;
-    SCHK(sh, hipMemcpyAsync(host, sh->S, (size_t)sh->n * sh->H * sizeof(double2), hipMemcpyDeviceToHost, st));
-    SCHK(sh, hipStreamSynchronize(st));
+    SCHK(sh->h, hipMemcpyAsync(host, sh->S, (size_t)sh->fft->n * sh->fft->H * sizeof(double2), hipMemcpyDeviceToHost, st));
+    SCHK(sh->h, hipStreamSynchronize(st));
     return SLICER_OK;
 }
 
 int slicer_shear_device_map(slicer_shear_handle sh, int32_t which, float **d_map)
 {
     if (!sh || !d_map)
-        return sfail(sh, SLICER_ERR_ARG, "slicer_shear_device_map: null argument");
+        return sfail(sh ? sh->h : nullptr, SLICER_ERR_ARG, "slicer_shear_device_map: null argument");
     if (which < SLICER_SHEAR_PHI || which > SLICER_SHEAR_GAMMA)
-        return sfail(sh, SLICER_ERR_ARG, "slicer_shear_device_map: which = %d, expected 0..3", which);
+        return sfail(sh->h, SLICER_ERR_ARG, "slicer_shear_device_map: which = %d, expected 0..3", which);
     if (!sh->ran)
-        return sfail(sh, SLICER_ERR_STATE, "shear maps are available after slicer_shear_run");
+        return sfail(sh->h, SLICER_ERR_STATE, "shear maps are available after slicer_shear_run");
     *d_map = sh->maps[which];
     return SLICER_OK;
 }
@@ -614,12 +670,12 @@ int slicer_shear_read(slicer_shear_handle sh, int32_t which, float *host)
     if (int rc = slicer_shear_device_map(sh, which, &d))
         return rc;
     if (!host)
-        return sfail(sh, SLICER_ERR_ARG, "slicer_shear_read: null host pointer");
+        return sfail(sh->h, SLICER_ERR_ARG, "slicer_shear_read: null host pointer");
     hipStream_t st;
     if (int rc = stream_of(sh, &st))
         return rc;
-    SCHK(sh, hipMemcpyAsync(host, d, (size_t)sh->n * sh->n * sizeof(float), hipMemcpyDeviceToHost, st));
-    SCHK(sh, hipStreamSynchronize(st));
+    SCHK(sh->h, hipMemcpyAsync(host, d, (size_t)sh->fft->n * sh->fft->n * sizeof(float), hipMemcpyDeviceToHost, st));
+    SCHK(sh->h, hipStreamSynchronize(st));
     return SLICER_OK;
 }
 
@@ -629,7 +685,7 @@ int slicer_shear_destroy(slicer_shear_handle sh)
         return SLICER_ERR_ARG;
     void *sp = nullptr;
     if (slicer_get_stream(sh->h, &sp) == SLICER_OK) {
-        (void)hipSetDevice(sh->device);
+        (void)hipSetDevice(sh->fft->device);
         (void)hipStreamSynchronize((hipStream_t)sp);
     }
     release(sh);

@@ -1,11 +1,13 @@
 """Born-approximation convergence (kappa) maps from the lens planes, and the shear and lensing
-potential maps from them (row N6).
+potential maps from them (row N6), and the binned auto and cross power spectra of such maps (row N7).
 
 plane_weights wraps the host weights of include/slicer_amd.h (slicer_lensing_weights); Kappa is the device accumulator
 (slicer_kappa_*) bound to a Slicer handle: it reads the finalized plane maps where they are, in HBM.  Shear (slicer_shear_*)
-turns one kappa map into phi, gamma1, gamma2 and |gamma| on the same device.
+turns one kappa map into phi, gamma1, gamma2 and |gamma| on the same device; Power (slicer_power_*) bins the spectra
+of several of them into C_l.
 """
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -170,3 +172,110 @@ class Shear:
         out = np.empty((self.npix, self.npix), np.float32)
         self._s._chk(_L.slicer_shear_read(self._sh, int(which), out.ctypes.data))
         return out
+
+
+def ell_fundamental(angle_deg):
+    """l_f = 2 pi / theta of a map of side angle_deg degrees, rounded as slicer_power_* round it."""
+    return 2.0 * math.pi / (float(angle_deg) * math.pi / 180.0)
+
+
+def _edges(npix, edges, ell_edges, angle_deg):
+    """(n_edges, f64 array or None) of edges in units of l_f; ell_edges are divided by l_f on the host."""
+    if edges is not None and ell_edges is not None:
+        raise ValueError("give edges or ell_edges, not both")
+    if ell_edges is not None:
+        if not (math.isfinite(angle_deg) and angle_deg > 0):
+            raise ValueError("ell_edges need a positive, finite angle")
+        edges = np.asarray(ell_edges, np.float64) / ell_fundamental(angle_deg)
+    if edges is None:
+        return int(npix), None
+    edges = np.ascontiguousarray(edges, np.float64).ravel()
+    return edges.size, edges
+
+
+def power_bins(npix, edges=None):
+    """Host only (no device): {"counts": N_b int64, "mean_radius": mean sqrt(m2) per bin in units of l_f} for the
+    edges (units of l_f; None: 0, 1, ..., npix - 1)."""
+    n_edges, e = _edges(npix, edges, None, 1.0)
+    B = max(n_edges - 1, 0)
+    counts = np.zeros(B, np.int64)
+    mean = np.zeros(B, np.float64)
+    rc = _L.slicer_power_bins(int(npix), n_edges, _dptr(e), counts.ctypes.data, mean.ctypes.data)
+    if rc:
+        raise SlicerError(rc, (_L.slicer_last_error(None) or b"").decode())
+    return {"counts": counts, "mean_radius": mean}
+
+
+class Power:
+    """Binned power spectra C_l of n_maps npix^2 maps of side angle_deg degrees, on the device of `slicer`, on its
+    stream.  cross=False: the auto-spectra; cross=True: every pair.  edges in units of
+    l_f = 2 pi / theta (None: 0, 1, ..., npix - 1), or ell_edges in multipoles."""
+
+    def __init__(self, slicer: Slicer, npix, angle_deg, n_maps, cross=False, edges=None, ell_edges=None):
+        self._s = slicer
+        self.npix, self.angle_deg, self.n_maps, self.cross = int(npix), float(angle_deg), int(n_maps), bool(cross)
+        ok = math.isfinite(self.angle_deg) and self.angle_deg > 0  # otherwise slicer_power_create refuses it
+        self.ell_f = ell_fundamental(self.angle_deg) if ok else math.nan
+        n_edges, e = _edges(self.npix, edges, ell_edges, self.angle_deg)
+        self.edges = np.arange(self.npix, dtype=np.float64) if e is None else e.copy()
+        self.n_bins = n_edges - 1
+        ph = C.c_void_p()
+        slicer._chk(_L.slicer_power_create(slicer._h, self.npix, self.angle_deg, self.n_maps, int(self.cross), n_edges,
+                                           _dptr(e), C.byref(ph)))
+        self._ph = ph
+
+    def close(self):
+        if getattr(self, "_ph", None):
+            _L.slicer_power_destroy(self._ph)
+            self._ph = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def run(self, ptrs):
+        """ptrs: device addresses of the n_maps f32 npix^2 maps."""
+        ptrs = [int(p) for p in ptrs]
+        if len(ptrs) != self.n_maps:
+            raise ValueError(f"expected {self.n_maps} maps, got {len(ptrs)}")
+        arr = (C.c_void_p * len(ptrs))(*ptrs)
+        self._s._chk(_L.slicer_power_run(self._ph, arr))
+
+    def run_kappa(self, kappa: Kappa):
+        """The maps of every source of a Kappa accumulator, where they are."""
+        self.run([kappa.device_map(s) for s in range(kappa.n_sources)])
+
+    def spectrum(self, map):
+        """rfft2 of map `map` of the last run, [npix, npix // 2 + 1] complex128 (auto mode: the last map only)."""
+        out = np.empty((self.npix, self.npix // 2 + 1), np.complex128)
+        self._s._chk(_L.slicer_power_spectrum(self._ph, int(map), out.ctypes.data))
+        return out
+
+    def read(self):
+        """dict: ell_lo, ell_hi (bin edges in multipoles), ell (mean l), counts, and cl: [S][S][B], symmetric (cross)
+        or [S][B] (auto)."""
+        S, B = self.n_maps, self.n_bins
+        npairs = S * (S + 1) // 2 if self.cross else S
+        flat = np.empty((npairs, B), np.float64)
+        ell = np.empty(B, np.float64)
+        counts = np.empty(B, np.int64)
+        self._s._chk(_L.slicer_power_read(self._ph, flat.ctypes.data, ell.ctypes.data, counts.ctypes.data))
+        if self.cross:
+            cl = np.empty((S, S, B), np.float64)
+            p = 0
+            for s in range(S):
+                for t in range(s, S):
+                    cl[s, t] = cl[t, s] = flat[p]
+                    p += 1
+        else:
+            cl = flat
+        return {"ell_lo": self.edges[:-1] * self.ell_f, "ell_hi": self.edges[1:] * self.ell_f, "ell": ell,
+                "counts": counts, "cl": cl}
