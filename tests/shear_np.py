@@ -55,6 +55,16 @@ def shortcut_gamma(kappa, angle_deg):
     return z.real, z.imag
 
 
+def seven_smooth(n):
+    """The sizes the device transforms take: 2 <= n <= 16384 with no prime factor above 7."""
+    if not 2 <= n <= 16384:
+        return False
+    for p in (2, 3, 5, 7):
+        while n % p == 0:
+            n //= p
+    return n == 1
+
+
 def within_bound(got, ref):
     """The f32 output bound: |got - ref| <= 2^-23 |ref| + 1e-9 max|ref|; returns (ok, worst ratio to the bound)."""
     got = np.asarray(got, np.float64)

@@ -88,6 +88,18 @@ def test_power_file_matches_the_restatement_of_the_kappa_files(tmp_path, npix):
 
 
 @pytest.mark.gpu
+def test_power_file_of_every_pair_of_every_plane(tmp_path):
+    """--kappa all makes one source per plane: more than 8, so the binning runs over pairs of source blocks."""
+    ini, _, out = make_cone(tmp_path)
+    r = run([ini, "--ngp", "--kappa", "all", "--power", "cross"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    S = check_against_kappa_files(out, 32, cross=True)
+    assert S >= 20
+    _, cols, table = parse(cl_file(out, 32))
+    assert len(cols) - 4 == table.shape[1] - 4 == S * (S + 1) // 2 >= 210
+
+
+@pytest.mark.gpu
 def test_power_file_is_the_same_resumed_and_on_two_ranks(tmp_path):
     ini, _, out = make_cone(tmp_path)
     args = ["--accum", "fixed64", "--kappa", "0.05,0.2", "--power", "cross"]

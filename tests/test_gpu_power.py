@@ -6,6 +6,7 @@ import pytest
 import power_np
 import shear_np
 import slicer_amd
+from test_power_host import brute_force_cross
 
 
 def log_edges(n):
@@ -18,6 +19,12 @@ def maps_for(n, S):
     for s in range(S):
         out.append(rng.standard_normal((n, n)).astype(np.float32) if s % 2 == 0 else shear_np.clustered(n, n + s))
     return out
+
+
+def scaled_maps(n, S):
+    """maps_for with every map times its own factor: no two pairs have the same spectrum, so a pair written to or read
+    from another pair's place cannot agree by accident."""
+    return [m * np.float32(0.5 + 0.173 * k) for k, m in enumerate(maps_for(n, S))]
 
 
 def run_power(s, maps, angle, cross, edges=None, split=False, twice=False):
@@ -96,6 +103,7 @@ def check(s, maps, angle, edges, split):
             bnd = norm * (eps[a] * mb + eps[b] * ma + eps[a] * eps[b]) + 1e-13 * np.abs(exact_cl[a, b][nz])
             d = np.abs(cross["cl"][a, b][nz] - exact_cl[a, b][nz])
             assert np.all(d <= bnd), (a, b, float((d / bnd).max()))
+    return cross
 
 
 CASES = [(n, False) for n in (16, 30, 45, 49, 100, 1000, 4096)] + [(30, True), (45, True), (1024, True)]
@@ -112,10 +120,32 @@ def test_power_matches_restatement(n, split):
                 check(s, maps_for(n, 1), angle, edges, split)
 
 
+# S > 8: k_power_bin<8> works on pairs of blocks of 8 sources.  9 and 17 leave a last block of one source, 24 gives
+# three full blocks (block rows 1 and 2 of the triangle), 128 is the most the ABI takes (136 block pairs, 8256 pairs).
+BLOCK_CASES = [(n, S) for n in (45, 100) for S in (8, 9, 16, 17, 24)] + [(16, 128)]
+
+
 @pytest.mark.gpu
-def test_power_16384_one_map():
-    n, angle = 16384, 10.0
-    kappa = shear_np.clustered(n, 9)
+@pytest.mark.parametrize("n,S", BLOCK_CASES)
+def test_cross_power_over_block_pairs(n, S):
+    angle = 5.0
+    maps = scaled_maps(n, S)
+    with slicer_amd.Slicer(0) as s:
+        for edges in (None, log_edges(n)):
+            cross = check(s, maps, angle, edges, False)
+            if n == 45:  # every pair against the plain double loop over the half plane, on the device's spectra
+                cnt, cl, scale = brute_force_cross([cross["spectra"][k] for k in range(S)], angle,
+                                                   power_np.default_edges(n) if edges is None else edges)
+                assert np.array_equal(cross["counts"], cnt)
+                nz = cnt > 0
+                assert np.array_equal(np.isnan(cross["cl"]), np.isnan(cl))
+                err = np.abs(cross["cl"] - cl)[..., nz]
+                assert np.all(err <= 1e-13 * scale[..., nz]), float((err / (1e-13 * scale[..., nz])).max())
+
+
+def one_large_map(n, seed):
+    angle = 10.0
+    kappa = shear_np.clustered(n, seed)
     with slicer_amd.Slicer(0) as s:
         got = run_power(s, [kappa], angle, False)
     assert np.array_equal(got["counts"], slicer_amd.power_bins(n)["counts"])
@@ -132,6 +162,17 @@ def test_power_16384_one_map():
     bnd = theta ** 2 / float(n) ** 4 * (2 * eps * mag[nz] / counts[nz] + eps * eps) + 1e-13 * np.abs(ref["cl"][0][nz])
     d = np.abs(got["cl"][0][nz] - ref["cl"][0][nz])
     assert np.all(d <= bnd), float((d / bnd).max())
+
+
+@pytest.mark.gpu
+def test_power_16384_one_map():
+    one_large_map(16384, 9)
+
+
+@pytest.mark.gpu
+def test_power_8505_one_map():
+    """8505 = 3^5 5 7: the smallest size whose row transform takes two passes; slicer_power_create plans it itself."""
+    one_large_map(8505, 11)
 
 
 @pytest.mark.gpu

@@ -35,6 +35,55 @@ def brute_force(kappa, angle, edges):
     return np.array(cnt), np.array(mean), np.array(cl)
 
 
+def brute_force_cross(spectra, angle, edges):
+    """Every pair of the half-plane spectra ([n][n // 2 + 1] each) by the same loop: -> counts [B], cl [S][S][B], scale
+    [S][S][B] (theta^2 / n^4 times the bin mean of |khat_s| |khat_t|).  The terms of a bin are summed with math.fsum,
+    so the sums carry no error of their own beyond the rounding of each product."""
+    S, n = len(spectra), spectra[0].shape[0]
+    khat = np.stack(spectra)
+    e2 = [float(r) * float(r) for r in edges]
+    B = len(edges) - 1
+    terms = [[] for _ in range(B)]
+    mags = [[] for _ in range(B)]
+    for i0 in range(n):
+        j0 = i0 if i0 < (n + 1) // 2 else i0 - n
+        for j1 in range(n // 2 + 1):
+            m2 = j0 * j0 + j1 * j1
+            for b in range(B):
+                if e2[b] <= m2 < e2[b + 1] or (b == B - 1 and m2 == e2[B]):
+                    x = khat[:, i0, j1]
+                    terms[b].append(np.outer(x.real, x.real) + np.outer(x.imag, x.imag))
+                    mags[b].append(np.outer(np.abs(x), np.abs(x)))
+                    break
+    norm = math.radians(angle) ** 2 / n ** 4
+    cnt = np.array([len(t) for t in terms])
+    cl, scale = np.full((S, S, B), np.nan), np.full((S, S, B), np.nan)
+    for b in range(B):
+        if cnt[b]:
+            t, m = np.stack(terms[b]), np.stack(mags[b])
+            for s in range(S):
+                for u in range(s, S):
+                    cl[s, u, b] = cl[u, s, b] = norm * (math.fsum(t[:, s, u]) / cnt[b])
+                    scale[s, u, b] = scale[u, s, b] = norm * (math.fsum(m[:, s, u]) / cnt[b])
+    return cnt, cl, scale
+
+
+@pytest.mark.parametrize("n", [3, 6, 15, 16])
+def test_restatement_of_pairs_matches_brute_force(n):
+    rng = np.random.default_rng(70 + n)
+    maps = [rng.standard_normal((n, n)) * (1.0 + s) for s in range(4)]
+    for edges in (power_np.default_edges(n), [0.5, 1.0, 2.0, 2.5, 5.0]):
+        cnt, cl, scale = brute_force_cross([np.fft.rfft2(m) for m in maps], 3.0, edges)
+        ref = power_np.power(maps, 3.0, edges, cross=True)
+        assert np.array_equal(ref["counts"], cnt)
+        assert np.array_equal(np.isnan(cl), np.isnan(ref["cl"]))
+        nz = cnt > 0
+        assert np.all(np.abs(cl - ref["cl"])[..., nz] <= 1e-13 * scale[..., nz])
+        np.testing.assert_allclose(scale[..., nz], ref["scale"][..., nz], rtol=1e-12)
+        for s in range(4):  # the diagonal is the single-map loop above
+            np.testing.assert_allclose(cl[s, s], brute_force(maps[s], 3.0, edges)[2], rtol=1e-12, equal_nan=True)
+
+
 @pytest.mark.parametrize("n", [2, 3, 6, 7, 8, 12, 15])
 def test_restatement_matches_brute_force(n):
     rng = np.random.default_rng(n)

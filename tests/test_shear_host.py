@@ -14,6 +14,29 @@ def test_supported_sizes(n, ok):
     assert slicer_amd.shear_supported(n) == bool(ok)
 
 
+def test_sweep_lists_are_the_supported_sizes():
+    """The size lists of tests/test_gpu_shear.py: every size slicer_shear_supported accepts, none other."""
+    import test_gpu_shear as t
+    every = [n for n in range(0, 16400) if slicer_amd.shear_supported(n)]
+    assert len(every) == 399 and every == [n for n in range(0, 16400) if shear_np.seven_smooth(n)]
+    assert t.SWEEP == [n for n in every if n <= 1200] and len(t.SWEEP) == 151
+    assert t.SWEEP[:12] == [2, 3, 4, 5, 6, 7, 8, 9, 10, 12, 14, 15]
+    assert t.SWEEP_SPLIT == [n for n in every if n <= 200]
+    assert [n for n in every if n % 2 and n > 8192] == [8505, 8575, 9261, 9375, 10125, 10935, 11025, 11907, 12005,
+                                                        13125, 14175, 15309, 15435, 15625]
+
+
+@pytest.mark.parametrize("n,a,b", [(16, 3, 5), (45, -7, 11), (30, 4, 0), (45, 16, 0)])
+def test_device_cosine_cases_agree_with_the_restatement(n, a, b):
+    """cosine_case of tests/test_gpu_shear.py (the hand-made answers the device is held to) against shear_np."""
+    import test_gpu_shear as t
+    kappa, exact = t.cosine_case(n, a, b)
+    out = shear_np.shear(kappa, 4.0)
+    assert np.allclose(out["spectrum"], exact["spectrum"], atol=1e-9 * n * n)
+    for k in ("phi", "gamma1", "gamma2"):
+        assert np.allclose(out[k], exact[k], atol=1e-10 * np.abs(exact[k]).max() + 1e-13), k
+
+
 @pytest.mark.parametrize("n,a,b", [(16, 1, 2), (16, 3, -1), (30, 2, 5), (45, 4, 7), (16, 8, 3), (16, 5, 8)])
 def test_restatement_on_analytic_fields(n, a, b):
     """phi = A cos(2 pi (a i0 + b i1) / n): kappa = 1/2 lap phi, gamma1 = 1/2 (phi_00 - phi_11), gamma2 = phi_01, taken
