@@ -647,6 +647,16 @@ constexpr unsigned kItemRecs = SLICER_ITEM_RECS;
 // ... but a bin of up to kWholeRecs records stays whole: every part pays for zeroing and flushing a tile of its own
 // (536 us against 554 us for the uniform headline case), while only a bin far beyond the usual load needs many hands
 constexpr unsigned kWholeRecs = SLICER_WHOLE_RECS;
+// Integer cells (kF32I / kF64I) count units of 2^(le - 49) with 2^le above the mass: one contribution is below
+// 0.5625 * 2^49 units (TSC centre weight 0.75^2), so the N records a single workgroup may add to one u64 cell must keep
+// N * 0.5625 * 2^49 < 2^64, i.e. N <= 58254.  A launch with integer cells therefore keeps a bin whole only up to
+// kWholeRecsInt records; parts of split bins hold <= kItemRecs.  (f64, fixed-point -- 2^9 times the room -- and count
+// cells keep kWholeRecs.)
+#ifndef SLICER_WHOLE_RECS_INT
+#define SLICER_WHOLE_RECS_INT 32768
+#endif
+constexpr unsigned kWholeRecsInt = SLICER_WHOLE_RECS_INT;
+static_assert(SLICER_ITEM_RECS <= 58254, "a part must fit the integer cells' headroom");
 #ifndef SLICER_MERGE_RECS
 #define SLICER_MERGE_RECS 131072
 #endif
@@ -663,7 +673,7 @@ struct TileItems {
 // Work items of the tile kernel: part 0 of bin b is workgroup b; the further parts of heavy bins are appended to a
 // list with one atomic add per heavy bin (their order does not matter), so that the builder is a plain parallel
 // kernel instead of a single-workgroup scan.
-__global__ __launch_bounds__(256) void k_build_items(PendingList L, int nbins, TileItems I, int whole)
+__global__ __launch_bounds__(256) void k_build_items(PendingList L, int nbins, TileItems I, int whole, unsigned whole_recs)
 {
     const int b = blockIdx.x * 256 + threadIdx.x;
     if (b == 0)
@@ -679,7 +689,7 @@ __global__ __launch_bounds__(256) void k_build_items(PendingList L, int nbins, T
             tot += L.base[c][b + 1] - L.base[c][b];
     }
     // (whole: the launch folds NGP counts file by file inside the tile kernel, which needs every tile in one workgroup)
-    const unsigned np = (whole || tot <= kWholeRecs) ? (tot != 0) : (tot + kItemRecs - 1) / kItemRecs;
+    const unsigned np = (whole || tot <= whole_recs) ? (tot != 0) : (tot + kItemRecs - 1) / kItemRecs;
     I.nparts[b] = np;
     if (np > 1) {
         const unsigned at = atomicAdd(I.n_extra, np - 1);
@@ -784,7 +794,7 @@ __device__ __forceinline__ void tile_accumulate_chunks(const PendingList &L, con
             float m = mconst, sq = smc;
             if (HAS_MASS) {
                 m = cap_mass(mr[u]);
-                sq = __fsqrt_rn(m);
+                sq = sqrt_mass(m);
             }
             const int gx = grid_index<POW2>(xs, P);
             const int gy = grid_index<POW2>(ys, P);
@@ -1036,7 +1046,7 @@ __device__ __forceinline__ void tile_accumulate(const PassParams &P, typename Ac
                 float m = mc.x, sq = mc.y;
                 if (HAS_MASS) {
                     m = cap_mass(cur[u].m);
-                    sq = __fsqrt_rn(m);
+                    sq = sqrt_mass(m);
                 }
                 const int gx = grid_index<POW2>(xs, P);
                 const int gy = grid_index<POW2>(ys, P);
@@ -1148,7 +1158,7 @@ __device__ __forceinline__ void tile_accumulate_merged_chunks(const PendingList 
                     v = reinterpret_cast<const Rec3 *>(sxy)[i];
                 r = make_float2(v.x, v.y);
                 m = cap_mass(v.m);
-                sq = __fsqrt_rn(m);
+                sq = sqrt_mass(m);
             } else if (act) {
                 r = sxy[i];
             }
@@ -1253,7 +1263,7 @@ __device__ __forceinline__ void tile_accumulate_merged(const PendingList &L, con
                     v = reinterpret_cast<const Rec3 *>(sxy)[i];
                 r = make_float2(v.x, v.y);
                 m = cap_mass(v.m);
-                sq = __fsqrt_rn(m);
+                sq = sqrt_mass(m);
             } else if (act) {
                 r = sxy[i];
             }
@@ -1542,7 +1552,7 @@ k_tile_deposit(PendingList L, PassParams P, BinGeom G, Targets T, TileItems I, N
             const uint2 w = s_slow[e];
             if (HAS_MASS) {
                 const Rec3 r = reinterpret_cast<const Rec3 *>(L.sxy[w.x])[w.y];
-                slow_record<ACC, POW2>(r.x, r.y, __fsqrt_rn(cap_mass(r.m)), P, Q, tile, gmap, x0, y0, W);
+                slow_record<ACC, POW2>(r.x, r.y, sqrt_mass(cap_mass(r.m)), P, Q, tile, gmap, x0, y0, W);
             } else {
                 const float2 r = L.sxy[w.x][w.y];
                 slow_record<ACC, POW2>(r.x, r.y, L.sm_const[w.x], P, Q, tile, gmap, x0, y0, W);
@@ -1705,8 +1715,27 @@ hipError_t launch_tile_deposit(const LaunchCfg &cfg, const PassParams &P, const 
     I.next_n_extra = counters + ((epoch + 1u) & 1u);
     I.nparts = counters + 4;
     I.extra = reinterpret_cast<uint2 *>(I.nparts + G.nbins + (G.nbins & 1));
-    k_build_items<<<(G.nbins + 255) / 256, 256, 0, s>>>(L, G.nbins, I, (cfg.mas == kNGP && cfg.acc == kCountU32 && F.on) ? 1 : 0);
     const bool pow2 = P.pow2 != 0;
+    // TSC in the F32 / F64 modes: integer tile cells (int_mode, the handle's option k4_int: 0 keeps the
+    // f64 cells, 2 forces the integer ones).  They pay where the records dominate (2048^2 x 4 planes, 65536 particles per bin: 370 against 622 us);
+    // a launch with few records per tile is mostly tile zeroing and flushing, where the u64 -> float conversion of every
+    // cell costs what the cheaper LDS atomic saves (8192^2 x 4 planes, 4096 per bin: 1242 against 1205 us; 2048 per bin:
+    // equal) -- below 2048 particles per bin the f64 cells stay.
+    // Decided before the work items are built: the cells of the launch set how many records a bin may hold and stay
+    // whole (kWholeRecsInt).  The bound on the extra items (max_items, tile_items_bytes: total_particles / kItemRecs + 1)
+    // holds with either cap, since a bin of t records adds ceil(t / kItemRecs) - 1 <= t / kItemRecs items.
+    bool int_launch = false;
+    if (cfg.mas != kNGP && (cfg.acc == kF32 || cfg.acc == kF64) &&
+        (int_mode == 2 || (int_mode == 1 && total_particles / (uint64_t)G.nbins >= 2048))) {
+        int_launch = cfg.has_mass;  // (per-particle masses: the quantum follows the largest mass the sort kernel saw)
+        if (!cfg.has_mass) {        // one quantum per launch: all pending chunks carry the same constant mass
+            int_launch = L.mconst[0] == P.mconst;
+            for (int c = 1; c < L.n; c++)
+                int_launch = int_launch && L.mconst[c] == L.mconst[0];
+        }
+    }
+    k_build_items<<<(G.nbins + 255) / 256, 256, 0, s>>>(L, G.nbins, I, (cfg.mas == kNGP && cfg.acc == kCountU32 && F.on) ? 1 : 0,
+                                                        int_launch ? kWholeRecsInt : kWholeRecs);
     if (cfg.mas == kNGP) {
         if (cfg.acc == kCountU32) {
             // (has_mass slot of the count kernels: keep the species' own map in the in-tile fold)
@@ -1714,28 +1743,11 @@ hipError_t launch_tile_deposit(const LaunchCfg &cfg, const PassParams &P, const 
         }
         return launch_k4<kNGP, kF32>(pow2, cfg.has_mass, P, G, L, T, I, F, max_items, s);
     }
-    // constant-mass TSC in the F32 / F64 modes: integer tile cells (int_mode, the handle's option k4_int: 0 keeps the
-    // f64 cells, 2 forces the integer ones).  They pay where the records dominate (2048^2 x 4 planes, 65536 particles per bin: 370 against 622 us);
-    // a launch with few records per tile is mostly tile zeroing and flushing, where the u64 -> float conversion of every
-    // cell costs what the cheaper LDS atomic saves (8192^2 x 4 planes, 4096 per bin: 1242 against 1205 us; 2048 per bin:
-    // equal) -- below 2048 particles per bin the f64 cells stay.
-    const bool int_cells = int_mode == 2 || (int_mode == 1 && total_particles / (uint64_t)G.nbins >= 2048);
-    if (int_cells && (cfg.acc == kF32 || cfg.acc == kF64)) {
-        if (cfg.has_mass) {  // the quantum follows the largest mass the sort kernel saw (TileQuantum)
-            *int_cells_used = true;
-            if (cfg.acc == kF32)
-                return launch_k4<kTSC, kF32I>(pow2, true, P, G, L, T, I, F, max_items, s);
-            return launch_k4<kTSC, kF64I>(pow2, true, P, G, L, T, I, F, max_items, s);
-        }
-        bool same_mass = true;  // one quantum per launch: all pending chunks carry the same constant mass
-        for (int c = 1; c < L.n; c++)
-            same_mass = same_mass && L.mconst[c] == L.mconst[0];
-        if (same_mass && L.mconst[0] == P.mconst) {
-            *int_cells_used = true;
-            if (cfg.acc == kF32)
-                return launch_k4<kTSC, kF32I>(pow2, false, P, G, L, T, I, F, max_items, s);
-            return launch_k4<kTSC, kF64I>(pow2, false, P, G, L, T, I, F, max_items, s);
-        }
+    if (int_launch) {
+        *int_cells_used = true;
+        if (cfg.acc == kF32)
+            return launch_k4<kTSC, kF32I>(pow2, cfg.has_mass, P, G, L, T, I, F, max_items, s);
+        return launch_k4<kTSC, kF64I>(pow2, cfg.has_mass, P, G, L, T, I, F, max_items, s);
     }
     switch (cfg.acc) {
     case kF32: return launch_k4<kTSC, kF32>(pow2, cfg.has_mass, P, G, L, T, I, F, max_items, s);

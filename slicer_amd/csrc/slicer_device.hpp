@@ -577,6 +577,13 @@ __device__ __forceinline__ unsigned long long rn_scaled_u64(float w, double scal
 // densitymaps.cpp:367-369: masses above MAX_M (1e3) are zeroed
 __device__ __forceinline__ float cap_mass(float m) { return m > 1000.0f ? 0.0f : m; }
 
+// sqrt of a per-particle mass as the reference's sqrtf: IEEE correctly rounded.  __fsqrt_rn is not -- without the
+// rounded-operations build of the device library it is the hardware's v_sqrt_f32, good to 1 ulp, and whether it got
+// refined differed between instantiations of the tile kernel (integer cells with masses: pixels holding one
+// contribution came out 2-3 ulps low; tests/test_gpu_tile_deposit.py).  Plain sqrtf is correctly rounded under hipcc's
+// default -fhip-fp32-correctly-rounded-divide-sqrt; the single-contribution pixels of those tests hold it to that.
+__device__ __forceinline__ float sqrt_mass(float m) { return sqrtf(m); }
+
 // ---- synthetic boxes: must match slicer_amd/synth.py bit for bit ----
 __device__ __forceinline__ unsigned long long splitmix64(unsigned long long seed, unsigned long long counter)
 {

@@ -91,7 +91,7 @@ __global__ __launch_bounds__(256) void k_direct(const float *__restrict__ pos, c
         float m = P.mconst, sm = P.sm_const;
         if (HAS_MASS) {
             m = cap_mass(mass[i]);
-            sm = __fsqrt_rn(m);
+            sm = sqrt_mass(m);
         }
         for (int p = 0; p < P.n_planes; p++) {
             if (!(z >= P.zlo[p] && z < P.zhi[p]))
@@ -242,7 +242,7 @@ __global__ __launch_bounds__(256) void k_thin_deposit(const float *__restrict__ 
                 if (!((double)u < thr))
                     continue;  // ms = 0: contributes nothing (adds of +0.0f in the reference)
                 const float m = (float)(mfac * (double)m0);  // ms.push_back(pow(2, snopt) * num_float1)
-                deposit_global<MAS, ACC, POW2>(T.acc[0], xs, ys, m, __fsqrt_rn(m), P);
+                deposit_global<MAS, ACC, POW2>(T.acc[0], xs, ys, m, sqrt_mass(m), P);
             }
     }
     // selected-entry counter (all selected entries, kept or not, as totPartxyi counts them)
