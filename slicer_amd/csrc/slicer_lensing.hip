@@ -12,15 +12,11 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdarg>
 #include <cstdint>
-#include <cstdio>
 #include <new>
 #include <vector>
 
-#include "../../include/slicer_amd.h"
-
-extern "C" int slicer_internal_fail(slicer_handle h, int code, const char *msg);  // slicer_capi.cpp (not exported)
+#include "slicer_host.hpp"
 
 namespace {
 
@@ -212,103 +208,39 @@ struct slicer_kappa_s {
     int means_cap = 0;
     int n_added = 0;
     bool finalized = false;
+    DevAllocs mem;  // everything above
 };
-
-namespace {
-
-int kfail(slicer_kappa_handle kh, int code, const char *fmt, ...) __attribute__((format(printf, 3, 4)));
-int kfail(slicer_kappa_handle kh, int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return slicer_internal_fail(kh ? kh->h : nullptr, code, buf);
-}
-
-#define KCHK(kh, expr)                                                                                            \
-    do {                                                                                                          \
-        hipError_t e_ = (expr);                                                                                   \
-        if (e_ != hipSuccess)                                                                                     \
-            return kfail(kh, e_ == hipErrorOutOfMemory ? SLICER_ERR_NOMEM : SLICER_ERR_HIP, "%s failed: %s (%s:%d)", \
-                         #expr, hipGetErrorString(e_), __FILE__, __LINE__);                                       \
-    } while (0)
-
-int stream_of(slicer_kappa_handle kh, hipStream_t *st)
-{
-    void *p = nullptr;
-    if (slicer_get_stream(kh->h, &p) != SLICER_OK)
-        return SLICER_ERR_ARG;
-    *st = (hipStream_t)p;
-    KCHK(kh, hipSetDevice(kh->device));
-    return SLICER_OK;
-}
-
-void release(slicer_kappa_handle kh)
-{
-    (void)hipSetDevice(kh->device);
-    for (double *p : kh->acc)
-        if (p)
-            (void)hipFree(p);
-    for (float *p : kh->kappa)
-        if (p)
-            (void)hipFree(p);
-    for (void *p : {(void *)kh->off, (void *)kh->partials, (void *)kh->means})
-        if (p)
-            (void)hipFree(p);
-    delete kh;
-}
-
-}  // namespace
 
 int slicer_kappa_create(slicer_handle h, int32_t npix, int32_t n_sources, slicer_kappa_handle *out)
 {
     if (!h || !out)
-        return slicer_internal_fail(h, SLICER_ERR_ARG, "slicer_kappa_create: null argument");
+        return fail(h, SLICER_ERR_ARG, "slicer_kappa_create: null argument");
     *out = nullptr;
     if (npix <= 0 || n_sources <= 0)
-        return slicer_internal_fail(h, SLICER_ERR_ARG, "slicer_kappa_create: npix and n_sources must be positive");
+        return fail(h, SLICER_ERR_ARG, "slicer_kappa_create: npix and n_sources must be positive");
     slicer_kappa_handle kh = new (std::nothrow) slicer_kappa_s;
     if (!kh)
-        return slicer_internal_fail(h, SLICER_ERR_NOMEM, "out of host memory");
+        return fail(h, SLICER_ERR_NOMEM, "out of host memory");
     kh->h = h;
     kh->npix = npix;
     kh->n = (uint64_t)npix * (uint64_t)npix;
     kh->n_sources = n_sources;
     kh->nblocks = (unsigned)((kh->n + 4ull * kThreads - 1) / (4ull * kThreads));
     hipStream_t st = nullptr;
-    void *sp = nullptr;
-    int dev = 0;
-    int rc = slicer_get_stream(h, &sp);
-    st = (hipStream_t)sp;
-    if (rc == SLICER_OK && hipStreamGetDevice(st, &dev) != hipSuccess)
-        rc = kfail(kh, SLICER_ERR_HIP, "slicer_kappa_create: the handle's stream has no device");
-    kh->device = dev;
-    auto alloc = [&](void **p, size_t bytes) {
-        if (rc != SLICER_OK)
-            return;
-        hipError_t e = hipMalloc(p, bytes);
-        if (e != hipSuccess)
-            rc = kfail(kh, e == hipErrorOutOfMemory ? SLICER_ERR_NOMEM : SLICER_ERR_HIP,
-                       "slicer_kappa_create: %zu bytes of device memory: %s", bytes, hipGetErrorString(e));
-        else if ((e = hipMemsetAsync(*p, 0, bytes, st)) != hipSuccess)
-            rc = kfail(kh, SLICER_ERR_HIP, "hipMemsetAsync: %s", hipGetErrorString(e));
-    };
-    if (rc == SLICER_OK && hipSetDevice(dev) != hipSuccess)
-        rc = kfail(kh, SLICER_ERR_HIP, "hipSetDevice(%d) failed", dev);
+    const char *who = "slicer_kappa_create";
+    int rc = sub_open(h, who, &st, &kh->device);
     kh->acc.assign(n_sources, nullptr);
     kh->kappa.assign(n_sources, nullptr);
     for (int s = 0; s < n_sources; s++) {
-        alloc((void **)&kh->acc[s], kh->n * sizeof(double));
-        alloc((void **)&kh->kappa[s], kh->n * sizeof(float));
+        rc = kh->mem.alloc(rc, h, who, (void **)&kh->acc[s], kh->n * sizeof(double), &st);
+        rc = kh->mem.alloc(rc, h, who, (void **)&kh->kappa[s], kh->n * sizeof(float), &st);
     }
-    alloc((void **)&kh->off, n_sources * sizeof(double));
-    alloc((void **)&kh->partials, (size_t)kMaxMaps * kh->nblocks * sizeof(double));
+    rc = kh->mem.alloc(rc, h, who, (void **)&kh->off, n_sources * sizeof(double), &st);
+    rc = kh->mem.alloc(rc, h, who, (void **)&kh->partials, (size_t)kMaxMaps * kh->nblocks * sizeof(double), &st);
     kh->means_cap = 1024;
-    alloc((void **)&kh->means, kh->means_cap * sizeof(double));
+    rc = kh->mem.alloc(rc, h, who, (void **)&kh->means, kh->means_cap * sizeof(double), &st);
     if (rc != SLICER_OK) {
-        release(kh);
+        delete kh;
         return rc;
     }
     *out = kh;
@@ -318,25 +250,26 @@ int slicer_kappa_create(slicer_handle h, int32_t npix, int32_t n_sources, slicer
 int slicer_kappa_add(slicer_kappa_handle kh, int32_t n_maps, const float *const *d_maps, const double *coeff)
 {
     if (!kh || !d_maps || !coeff)
-        return kfail(kh, SLICER_ERR_ARG, "slicer_kappa_add: null argument");
+        return fail(kh ? kh->h : nullptr, SLICER_ERR_ARG, "slicer_kappa_add: null argument");
     if (n_maps < 1 || n_maps > kMaxMaps)
-        return kfail(kh, SLICER_ERR_ARG, "slicer_kappa_add: n_maps = %d, expected 1..%d", n_maps, kMaxMaps);
+        return fail(kh->h, SLICER_ERR_ARG, "slicer_kappa_add: n_maps = %d, expected 1..%d", n_maps, kMaxMaps);
     bool aligned = true;
     for (int p = 0; p < n_maps; p++) {
         if (!d_maps[p])
-            return kfail(kh, SLICER_ERR_ARG, "slicer_kappa_add: map %d is null", p);
+            return fail(kh->h, SLICER_ERR_ARG, "slicer_kappa_add: map %d is null", p);
         aligned = aligned && ((uintptr_t)d_maps[p] % 16) == 0;
     }
     hipStream_t st;
-    if (int rc = stream_of(kh, &st))
+    if (int rc = sub_stream(kh->h, kh->device, &st))
         return rc;
     if (kh->n_added + n_maps > kh->means_cap) {  // rare: grow the means array (the copy is ordered on the stream)
         const int cap = std::max(2 * kh->means_cap, kh->n_added + n_maps);
         double *p = nullptr;
-        KCHK(kh, hipMalloc(&p, cap * sizeof(double)));
-        KCHK(kh, hipMemcpyAsync(p, kh->means, kh->n_added * sizeof(double), hipMemcpyDeviceToDevice, st));
-        KCHK(kh, hipStreamSynchronize(st));
-        KCHK(kh, hipFree(kh->means));
+        HIPCHK(kh->h, hipMalloc(&p, cap * sizeof(double)));
+        HIPCHK(kh->h, hipMemcpyAsync(p, kh->means, kh->n_added * sizeof(double), hipMemcpyDeviceToDevice, st));
+        HIPCHK(kh->h, hipStreamSynchronize(st));
+        HIPCHK(kh->h, hipFree(kh->means));
+        kh->mem.replace(kh->means, p);
         kh->means = p;
         kh->means_cap = cap;
     }
@@ -366,7 +299,7 @@ int slicer_kappa_add(slicer_kappa_handle kh, int32_t n_maps, const float *const 
                 hipLaunchKernelGGL(k_kappa_add<true>, dim3(kh->nblocks), dim3(kThreads), 0, st, a);
             else
                 hipLaunchKernelGGL(k_kappa_add<false>, dim3(kh->nblocks), dim3(kThreads), 0, st, a);
-            KCHK(kh, hipGetLastError());
+            HIPCHK(kh->h, hipGetLastError());
         }
         if (a.active || g == 0) {
             m.partials = kh->partials;
@@ -377,7 +310,7 @@ int slicer_kappa_add(slicer_kappa_handle kh, int32_t n_maps, const float *const 
             m.n_maps = n_maps;
             m.compute_means = g == 0;
             hipLaunchKernelGGL(k_kappa_means, dim3(1), dim3(kThreads), 0, st, m);
-            KCHK(kh, hipGetLastError());
+            HIPCHK(kh->h, hipGetLastError());
         }
     }
     kh->n_added += n_maps;
@@ -388,23 +321,23 @@ int slicer_kappa_add(slicer_kappa_handle kh, int32_t n_maps, const float *const 
 int slicer_kappa_plane_means(slicer_kappa_handle kh, double *out, int32_t max)
 {
     if (!kh || (!out && max > 0))
-        return kfail(kh, SLICER_ERR_ARG, "slicer_kappa_plane_means: null argument");
+        return fail(kh ? kh->h : nullptr, SLICER_ERR_ARG, "slicer_kappa_plane_means: null argument");
     hipStream_t st;
-    if (int rc = stream_of(kh, &st))
+    if (int rc = sub_stream(kh->h, kh->device, &st))
         return rc;
     const int k = std::min<int>(std::max<int>(max, 0), kh->n_added);
     if (k > 0)
-        KCHK(kh, hipMemcpyAsync(out, kh->means, k * sizeof(double), hipMemcpyDeviceToHost, st));
-    KCHK(kh, hipStreamSynchronize(st));
+        HIPCHK(kh->h, hipMemcpyAsync(out, kh->means, k * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(kh->h, hipStreamSynchronize(st));
     return SLICER_OK;
 }
 
 int slicer_kappa_finalize(slicer_kappa_handle kh)
 {
     if (!kh)
-        return kfail(kh, SLICER_ERR_ARG, "null kappa handle");
+        return fail(kh ? kh->h : nullptr, SLICER_ERR_ARG, "null kappa handle");
     hipStream_t st;
-    if (int rc = stream_of(kh, &st))
+    if (int rc = sub_stream(kh->h, kh->device, &st))
         return rc;
     const int S = kh->n_sources;
     for (int g = 0; g * kGroup < S; g++) {
@@ -417,7 +350,7 @@ int slicer_kappa_finalize(slicer_kappa_handle kh)
         f.off = kh->off + g * kGroup;
         f.n = kh->n;
         hipLaunchKernelGGL(k_kappa_finalize, dim3(kh->nblocks), dim3(kThreads), 0, st, f);
-        KCHK(kh, hipGetLastError());
+        HIPCHK(kh->h, hipGetLastError());
     }
     kh->finalized = true;
     return SLICER_OK;
@@ -426,11 +359,11 @@ int slicer_kappa_finalize(slicer_kappa_handle kh)
 int slicer_kappa_device_map(slicer_kappa_handle kh, int32_t s, float **d_map)
 {
     if (!kh || !d_map)
-        return kfail(kh, SLICER_ERR_ARG, "slicer_kappa_device_map: null argument");
+        return fail(kh ? kh->h : nullptr, SLICER_ERR_ARG, "slicer_kappa_device_map: null argument");
     if (s < 0 || s >= kh->n_sources)
-        return kfail(kh, SLICER_ERR_ARG, "source %d out of range (%d sources)", s, kh->n_sources);
+        return fail(kh->h, SLICER_ERR_ARG, "source %d out of range (%d sources)", s, kh->n_sources);
     if (!kh->finalized)
-        return kfail(kh, SLICER_ERR_STATE, "kappa maps are available after slicer_kappa_finalize");
+        return fail(kh->h, SLICER_ERR_STATE, "kappa maps are available after slicer_kappa_finalize");
     *d_map = kh->kappa[s];
     return SLICER_OK;
 }
@@ -441,12 +374,12 @@ int slicer_kappa_read(slicer_kappa_handle kh, int32_t s, float *host)
     if (int rc = slicer_kappa_device_map(kh, s, &d))
         return rc;
     if (!host)
-        return kfail(kh, SLICER_ERR_ARG, "slicer_kappa_read: null host pointer");
+        return fail(kh->h, SLICER_ERR_ARG, "slicer_kappa_read: null host pointer");
     hipStream_t st;
-    if (int rc = stream_of(kh, &st))
+    if (int rc = sub_stream(kh->h, kh->device, &st))
         return rc;
-    KCHK(kh, hipMemcpyAsync(host, d, kh->n * sizeof(float), hipMemcpyDeviceToHost, st));
-    KCHK(kh, hipStreamSynchronize(st));
+    HIPCHK(kh->h, hipMemcpyAsync(host, d, kh->n * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(kh->h, hipStreamSynchronize(st));
     return SLICER_OK;
 }
 
@@ -454,11 +387,8 @@ int slicer_kappa_destroy(slicer_kappa_handle kh)
 {
     if (!kh)
         return SLICER_ERR_ARG;
-    void *sp = nullptr;
-    if (slicer_get_stream(kh->h, &sp) == SLICER_OK) {
-        (void)hipSetDevice(kh->device);
-        (void)hipStreamSynchronize((hipStream_t)sp);
-    }
-    release(kh);
+    (void)hipSetDevice(kh->device);
+    (void)hipStreamSynchronize(kh->h->stream);
+    delete kh;
     return SLICER_OK;
 }

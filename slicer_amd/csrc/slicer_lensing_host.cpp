@@ -13,9 +13,7 @@
 #include <cstdio>
 #include <vector>
 
-#include "../../include/slicer_amd.h"
-
-extern "C" int slicer_internal_fail(slicer_handle h, int code, const char *msg);  // slicer_capi.cpp (not exported)
+#include "slicer_host.hpp"
 
 namespace {
 
@@ -146,7 +144,7 @@ int refuse(int code, const char *fmt, double a = 0, double b = 0)
 {
     char buf[256];
     snprintf(buf, sizeof buf, fmt, a, b);
-    return slicer_internal_fail(nullptr, code, buf);
+    return fail(nullptr, code, "%s", buf);
 }
 
 }  // namespace

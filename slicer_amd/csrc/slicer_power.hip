@@ -20,18 +20,12 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdint>
-#include <cstdio>
 #include <new>
 #include <vector>
 
-#include "../../include/slicer_amd.h"
 #include "slicer_fft.hpp"
-
-extern "C" int slicer_internal_fail(slicer_handle h, int code, const char *msg);  // slicer_capi.cpp (not exported)
-extern "C" void *slicer_internal_prof_begin(slicer_handle h, int which);
-extern "C" void slicer_internal_prof_end(void *scope);
+#include "slicer_host.hpp"
 
 namespace {
 
@@ -202,35 +196,6 @@ __global__ void k_power_finish(const double *partial, const int *slice_off, cons
     cl[(size_t)(pair0 + q) * B + b] = nmodes[b] > 0.0 ? sum / nmodes[b] * norm : (double)NAN;
 }
 
-int pfail(slicer_handle h, int code, const char *fmt, ...) __attribute__((format(printf, 3, 4)));
-int pfail(slicer_handle h, int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return slicer_internal_fail(h, code, buf);
-}
-
-#define PCHK(h, expr)                                                                                             \
-    do {                                                                                                          \
-        hipError_t e_ = (expr);                                                                                   \
-        if (e_ != hipSuccess)                                                                                     \
-            return pfail(h, e_ == hipErrorOutOfMemory ? SLICER_ERR_NOMEM : SLICER_ERR_HIP, "%s failed: %s (%s:%d)", \
-                         #expr, hipGetErrorString(e_), __FILE__, __LINE__);                                       \
-    } while (0)
-
-bool smooth(int n)
-{
-    if (n < 2 || n > 16384)
-        return false;
-    for (int p : {2, 3, 5, 7})
-        while (n % p == 0)
-            n /= p;
-    return n == 1;
-}
-
 // The edges, or 0 .. npix-1 for NULL (then n_edges must be npix); "" if they are usable, else why not.
 const char *check_edges(int npix, int n_edges, const double *edges, std::vector<double> &out)
 {
@@ -305,30 +270,11 @@ struct slicer_power_s {
     int4 *slices = nullptr;
     int *slice_off = nullptr;
     bool ran = false;
+    DevAllocs mem;
+    SLICER_FFT_INTERNAL ~slicer_power_s() { slicer_fft_destroy(fft); }
 };
 
 namespace {
-
-void release(slicer_power_handle ph)
-{
-    (void)hipSetDevice(ph->device);
-    slicer_fft_destroy(ph->fft);
-    for (void *p : {(void *)ph->spec, (void *)ph->e2, (void *)ph->partial, (void *)ph->nmodes, (void *)ph->cl,
-                    (void *)ph->slices, (void *)ph->slice_off})
-        if (p)
-            (void)hipFree(p);
-    delete ph;
-}
-
-int stream_of(slicer_power_handle ph, hipStream_t *st)
-{
-    void *p = nullptr;
-    if (slicer_get_stream(ph->h, &p) != SLICER_OK)
-        return SLICER_ERR_ARG;
-    *st = (hipStream_t)p;
-    PCHK(ph->h, hipSetDevice(ph->device));
-    return SLICER_OK;
-}
 
 // Bin the spectra at ph->spec (S of them in cross mode, the one of source `s` in auto mode) into ph->cl.
 int bin_launch(slicer_power_handle ph, hipStream_t st, int s)
@@ -358,11 +304,11 @@ int bin_launch(slicer_power_handle ph, hipStream_t st, int s)
         npairs = 1;
         hipLaunchKernelGGL(k_power_bin<1>, dim3((unsigned)ph->nslices), dim3(kBinThreads), 0, st, a);
     }
-    PCHK(ph->h, hipGetLastError());
+    HIPCHK(ph->h, hipGetLastError());
     const int total = npairs * ph->B, tpb = 256;
     hipLaunchKernelGGL(k_power_finish, dim3((unsigned)((total + tpb - 1) / tpb)), dim3(tpb), 0, st, ph->partial,
                        ph->slice_off, ph->nmodes, ph->cl, npairs, ph->B, ph->nslices, ph->cross ? 0 : s, ph->norm);
-    PCHK(ph->h, hipGetLastError());
+    HIPCHK(ph->h, hipGetLastError());
     return SLICER_OK;
 }
 
@@ -371,11 +317,11 @@ int bin_launch(slicer_power_handle ph, hipStream_t st, int s)
 int slicer_power_bins(int32_t npix, int32_t n_edges, const double *edges, int64_t *counts, double *mean_radius)
 {
     if (npix < 1 || npix > 65536 || !counts || !mean_radius)
-        return slicer_internal_fail(nullptr, SLICER_ERR_ARG, "slicer_power_bins: npix out of 1..65536, or null output");
+        return fail(nullptr, SLICER_ERR_ARG, "slicer_power_bins: npix out of 1..65536, or null output");
     std::vector<double> e;
     const char *why = check_edges(npix, n_edges, edges, e);
     if (*why)
-        return pfail(nullptr, SLICER_ERR_ARG, "slicer_power_bins: %s", why);
+        return fail(nullptr, SLICER_ERR_ARG, "slicer_power_bins: %s", why);
     std::vector<int64_t> c;
     std::vector<double> m;
     bin_modes(npix, e, c, m);
@@ -388,35 +334,30 @@ int slicer_power_create(slicer_handle h, int32_t npix, double angle_deg, int32_t
                         int32_t n_edges, const double *edges, slicer_power_handle *out)
 {
     if (!h || !out)
-        return slicer_internal_fail(h, SLICER_ERR_ARG, "slicer_power_create: null argument");
+        return fail(h, SLICER_ERR_ARG, "slicer_power_create: null argument");
     *out = nullptr;
-    if (!smooth(npix))
-        return pfail(h, SLICER_ERR_UNSUPPORTED,
-                     "slicer_power_create: npix = %d unsupported (2..16384, prime factors 2, 3, 5, 7 only)", npix);
+    if (!fft_size_supported(npix))
+        return fail(h, SLICER_ERR_UNSUPPORTED,
+                    "slicer_power_create: npix = %d unsupported (2..16384, prime factors 2, 3, 5, 7 only)", npix);
     if (n_maps < 1 || n_maps > kMaxMaps)
-        return pfail(h, SLICER_ERR_UNSUPPORTED, "slicer_power_create: n_maps = %d outside 1..%d", n_maps, kMaxMaps);
+        return fail(h, SLICER_ERR_UNSUPPORTED, "slicer_power_create: n_maps = %d outside 1..%d", n_maps, kMaxMaps);
     if (cross != 0 && cross != 1)
-        return pfail(h, SLICER_ERR_ARG, "slicer_power_create: cross = %d, expected 0 or 1", cross);
+        return fail(h, SLICER_ERR_ARG, "slicer_power_create: cross = %d, expected 0 or 1", cross);
     std::vector<double> e;
     const char *why = check_edges(npix, n_edges, edges, e);
     if (*why)
-        return pfail(h, SLICER_ERR_ARG, "slicer_power_create: %s", why);
+        return fail(h, SLICER_ERR_ARG, "slicer_power_create: %s", why);
     if (!std::isfinite(angle_deg) || angle_deg <= 0.0)
-        return pfail(h, SLICER_ERR_ARG, "slicer_power_create: the angle must be positive and finite");
-    int split = 0;
-    if (slicer_get_option(h, "shear_split", &split) != SLICER_OK)
-        return SLICER_ERR_ARG;
-    void *sp = nullptr;
-    if (slicer_get_stream(h, &sp) != SLICER_OK)
-        return SLICER_ERR_ARG;
-    hipStream_t st = (hipStream_t)sp;
+        return fail(h, SLICER_ERR_ARG, "slicer_power_create: the angle must be positive and finite");
+    const char *who = "slicer_power_create";
+    hipStream_t st = nullptr;
     int dev = 0;
-    if (hipStreamGetDevice(st, &dev) != hipSuccess)
-        return pfail(h, SLICER_ERR_HIP, "slicer_power_create: the handle's stream has no device");
+    if (int rc = sub_open(h, who, &st, &dev))
+        return rc;
 
     slicer_power_handle ph = new (std::nothrow) slicer_power_s;
     if (!ph)
-        return slicer_internal_fail(h, SLICER_ERR_NOMEM, "out of host memory");
+        return fail(h, SLICER_ERR_NOMEM, "out of host memory");
     const int n = npix, H = n / 2 + 1, B = n_edges - 1;
     ph->h = h;
     ph->device = dev;
@@ -456,29 +397,19 @@ int slicer_power_create(slicer_handle h, int32_t npix, double angle_deg, int32_t
     off[B] = (int)sl.size();
     ph->nslices = (int)sl.size();
 
-    int rc = hipSetDevice(dev) == hipSuccess ? SLICER_OK : pfail(h, SLICER_ERR_HIP, "hipSetDevice(%d) failed", dev);
-    if (rc == SLICER_OK)
-        rc = slicer_fft_create(h, n, split, st, "slicer_power_create", &ph->fft);
-    auto alloc = [&](void **p, size_t bytes) {
-        if (rc != SLICER_OK)
-            return;
-        hipError_t err = hipMalloc(p, std::max<size_t>(bytes, 8));
-        if (err != hipSuccess)
-            rc = pfail(h, err == hipErrorOutOfMemory ? SLICER_ERR_NOMEM : SLICER_ERR_HIP,
-                       "slicer_power_create: %zu bytes of device memory: %s", bytes, hipGetErrorString(err));
-    };
-    alloc((void **)&ph->spec, (size_t)(cross ? n_maps : 1) * n * H * sizeof(double2));
-    alloc((void **)&ph->e2, (B + 1) * sizeof(double));
-    alloc((void **)&ph->partial, (size_t)(cross ? ph->npairs : 1) * ph->nslices * sizeof(double));
-    alloc((void **)&ph->nmodes, B * sizeof(double));
-    alloc((void **)&ph->cl, (size_t)ph->npairs * B * sizeof(double));
-    alloc((void **)&ph->slices, sl.size() * sizeof(int4));
-    alloc((void **)&ph->slice_off, (B + 1) * sizeof(int));
+    int rc = slicer_fft_create(h, n, h->opt.shear_split, st, dev, who, &ph->fft);
+    rc = ph->mem.alloc(rc, h, who, (void **)&ph->spec, (size_t)(cross ? n_maps : 1) * n * H * sizeof(double2));
+    rc = ph->mem.alloc(rc, h, who, (void **)&ph->e2, (B + 1) * sizeof(double));
+    rc = ph->mem.alloc(rc, h, who, (void **)&ph->partial, (size_t)(cross ? ph->npairs : 1) * ph->nslices * sizeof(double));
+    rc = ph->mem.alloc(rc, h, who, (void **)&ph->nmodes, B * sizeof(double));
+    rc = ph->mem.alloc(rc, h, who, (void **)&ph->cl, (size_t)ph->npairs * B * sizeof(double));
+    rc = ph->mem.alloc(rc, h, who, (void **)&ph->slices, sl.size() * sizeof(int4));
+    rc = ph->mem.alloc(rc, h, who, (void **)&ph->slice_off, (B + 1) * sizeof(int));
     auto up = [&](void *d, const void *hsrc, size_t bytes) {
         if (rc == SLICER_OK && bytes) {
             hipError_t err = hipMemcpyAsync(d, hsrc, bytes, hipMemcpyHostToDevice, st);
             if (err != hipSuccess)
-                rc = pfail(h, SLICER_ERR_HIP, "slicer_power_create: upload: %s", hipGetErrorString(err));
+                rc = fail(h, SLICER_ERR_HIP, "slicer_power_create: upload: %s", hipGetErrorString(err));
         }
     };
     up(ph->e2, e2.data(), (B + 1) * sizeof(double));
@@ -486,9 +417,9 @@ int slicer_power_create(slicer_handle h, int32_t npix, double angle_deg, int32_t
     up(ph->slices, sl.data(), sl.size() * sizeof(int4));
     up(ph->slice_off, off.data(), (B + 1) * sizeof(int));
     if (rc == SLICER_OK && hipStreamSynchronize(st) != hipSuccess)  // the sources are host temporaries
-        rc = pfail(h, SLICER_ERR_HIP, "slicer_power_create: upload failed");
+        rc = fail(h, SLICER_ERR_HIP, "slicer_power_create: upload failed");
     if (rc != SLICER_OK) {
-        release(ph);
+        delete ph;
         return rc;
     }
     *out = ph;
@@ -498,25 +429,21 @@ int slicer_power_create(slicer_handle h, int32_t npix, double angle_deg, int32_t
 int slicer_power_run(slicer_power_handle ph, const float *const *d_maps)
 {
     if (!ph || !d_maps)
-        return pfail(ph ? ph->h : nullptr, SLICER_ERR_ARG, "slicer_power_run: null argument");
+        return fail(ph ? ph->h : nullptr, SLICER_ERR_ARG, "slicer_power_run: null argument");
     for (int s = 0; s < ph->S; s++)
         if (!d_maps[s])
-            return pfail(ph->h, SLICER_ERR_ARG, "slicer_power_run: map %d is null", s);
+            return fail(ph->h, SLICER_ERR_ARG, "slicer_power_run: map %d is null", s);
     hipStream_t st;
-    if (int rc = stream_of(ph, &st))
+    if (int rc = sub_stream(ph->h, ph->device, &st))
         return rc;
     const size_t stride = (size_t)ph->n * ph->H;
     auto forward = [&](int s) {
-        void *scope = slicer_internal_prof_begin(ph->h, 0);
-        const int rc = slicer_fft_forward(ph->fft, st, d_maps[s], ph->spec + (ph->cross ? s * stride : 0));
-        slicer_internal_prof_end(scope);
-        return rc;
+        ProfScope ps(ph->h, KN_POWER_FFT);
+        return slicer_fft_forward(ph->fft, st, d_maps[s], ph->spec + (ph->cross ? s * stride : 0));
     };
     auto binning = [&](int s) {
-        void *scope = slicer_internal_prof_begin(ph->h, 1);
-        const int rc = bin_launch(ph, st, s);
-        slicer_internal_prof_end(scope);
-        return rc;
+        ProfScope ps(ph->h, KN_POWER_BIN);
+        return bin_launch(ph, st, s);
     };
     ph->ran = false;
     if (ph->cross) {
@@ -540,35 +467,35 @@ int slicer_power_run(slicer_power_handle ph, const float *const *d_maps)
 int slicer_power_spectrum(slicer_power_handle ph, int32_t map, double *host)
 {
     if (!ph || !host)
-        return pfail(ph ? ph->h : nullptr, SLICER_ERR_ARG, "slicer_power_spectrum: null argument");
+        return fail(ph ? ph->h : nullptr, SLICER_ERR_ARG, "slicer_power_spectrum: null argument");
     if (map < 0 || map >= ph->S)
-        return pfail(ph->h, SLICER_ERR_ARG, "slicer_power_spectrum: map = %d outside 0..%d", map, ph->S - 1);
+        return fail(ph->h, SLICER_ERR_ARG, "slicer_power_spectrum: map = %d outside 0..%d", map, ph->S - 1);
     if (!ph->ran)
-        return pfail(ph->h, SLICER_ERR_STATE, "slicer_power_spectrum before any slicer_power_run");
+        return fail(ph->h, SLICER_ERR_STATE, "slicer_power_spectrum before any slicer_power_run");
     if (!ph->cross && map != ph->S - 1)
-        return pfail(ph->h, SLICER_ERR_STATE, "slicer_power_spectrum: auto mode keeps only the last map's spectrum");
+        return fail(ph->h, SLICER_ERR_STATE, "slicer_power_spectrum: auto mode keeps only the last map's spectrum");
     hipStream_t st;
-    if (int rc = stream_of(ph, &st))
+    if (int rc = sub_stream(ph->h, ph->device, &st))
         return rc;
     const size_t stride = (size_t)ph->n * ph->H;
-    PCHK(ph->h, hipMemcpyAsync(host, ph->spec + (ph->cross ? map * stride : 0), stride * sizeof(double2),
+    HIPCHK(ph->h, hipMemcpyAsync(host, ph->spec + (ph->cross ? map * stride : 0), stride * sizeof(double2),
                                hipMemcpyDeviceToHost, st));
-    PCHK(ph->h, hipStreamSynchronize(st));
+    HIPCHK(ph->h, hipStreamSynchronize(st));
     return SLICER_OK;
 }
 
 int slicer_power_read(slicer_power_handle ph, double *cl, double *ell_mean, int64_t *counts)
 {
     if (!ph)
-        return pfail(nullptr, SLICER_ERR_ARG, "slicer_power_read: null handle");
+        return fail(nullptr, SLICER_ERR_ARG, "slicer_power_read: null handle");
     if (!ph->ran)
-        return pfail(ph->h, SLICER_ERR_STATE, "slicer_power_read before any slicer_power_run");
+        return fail(ph->h, SLICER_ERR_STATE, "slicer_power_read before any slicer_power_run");
     hipStream_t st;
-    if (int rc = stream_of(ph, &st))
+    if (int rc = sub_stream(ph->h, ph->device, &st))
         return rc;
     if (cl)
-        PCHK(ph->h, hipMemcpyAsync(cl, ph->cl, (size_t)ph->npairs * ph->B * sizeof(double), hipMemcpyDeviceToHost, st));
-    PCHK(ph->h, hipStreamSynchronize(st));
+        HIPCHK(ph->h, hipMemcpyAsync(cl, ph->cl, (size_t)ph->npairs * ph->B * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(ph->h, hipStreamSynchronize(st));
     for (int b = 0; b < ph->B; b++) {
         if (ell_mean)
             ell_mean[b] = ph->ell_f * ph->mean_radius[b];
@@ -582,11 +509,8 @@ int slicer_power_destroy(slicer_power_handle ph)
 {
     if (!ph)
         return SLICER_ERR_ARG;
-    void *sp = nullptr;
-    if (slicer_get_stream(ph->h, &sp) == SLICER_OK) {
-        (void)hipSetDevice(ph->device);
-        (void)hipStreamSynchronize((hipStream_t)sp);
-    }
-    release(ph);
+    (void)hipSetDevice(ph->device);
+    (void)hipStreamSynchronize(ph->h->stream);
+    delete ph;
     return SLICER_OK;
 }

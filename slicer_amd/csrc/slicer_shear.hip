@@ -22,16 +22,12 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdint>
-#include <cstdio>
 #include <new>
 #include <vector>
 
-#include "../../include/slicer_amd.h"
 #include "slicer_fft.hpp"
-
-extern "C" int slicer_internal_fail(slicer_handle h, int code, const char *msg);  // slicer_capi.cpp (not exported)
+#include "slicer_host.hpp"
 
 namespace {
 
@@ -281,16 +277,6 @@ __global__ __launch_bounds__(kThreads) void k_fft_pass(PassArgs a)
     }
 }
 
-bool smooth(int n)
-{
-    if (n < 2 || n > kMaxN)
-        return false;
-    for (int p : {2, 3, 5, 7})
-        while (n % p == 0)
-            n /= p;
-    return n == 1;
-}
-
 // one pass of a chain: radix R (itself split into LDS stages), Ns, lines per workgroup
 struct Pass {
     int R, Ns, C, Rp, nst;
@@ -343,6 +329,7 @@ struct slicer_fft_s {
     std::vector<Pass> row_chain, col_chain;
     double2 *tw = nullptr;
     double2 *A = nullptr, *B = nullptr, *Cb = nullptr;  // complex f64, n * H each: row output, pass intermediates
+    DevAllocs mem;
 };
 
 struct slicer_shear_s {
@@ -352,53 +339,11 @@ struct slicer_shear_s {
     double2 *S = nullptr, *G = nullptr;  // complex f64, n * H each
     float *maps[4] = {nullptr, nullptr, nullptr, nullptr};
     bool ran = false;
+    DevAllocs mem;
+    SLICER_FFT_INTERNAL ~slicer_shear_s() { slicer_fft_destroy(fft); }
 };
 
 namespace {
-
-int sfail(slicer_handle h, int code, const char *fmt, ...) __attribute__((format(printf, 3, 4)));
-int sfail(slicer_handle h, int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    return slicer_internal_fail(h, code, buf);
-}
-
-#define SCHK(h, expr)                                                                                             \
-    do {                                                                                                          \
-        hipError_t e_ = (expr);                                                                                   \
-        if (e_ != hipSuccess)                                                                                     \
-            return sfail(h, e_ == hipErrorOutOfMemory ? SLICER_ERR_NOMEM : SLICER_ERR_HIP, "%s failed: %s (%s:%d)", \
-                         #expr, hipGetErrorString(e_), __FILE__, __LINE__);                                       \
-    } while (0)
-
-int stream_of(slicer_shear_handle sh, hipStream_t *st)
-{
-    void *p = nullptr;
-    if (slicer_get_stream(sh->h, &p) != SLICER_OK)
-        return SLICER_ERR_ARG;
-    *st = (hipStream_t)p;
-    SCHK(sh->h, hipSetDevice(sh->fft->device));
-    return SLICER_OK;
-}
-
-void release(slicer_shear_handle sh)
-{
-    if (sh->fft) {
-        (void)hipSetDevice(sh->fft->device);
-        slicer_fft_destroy(sh->fft);
-    }
-    for (void *p : {(void *)sh->S, (void *)sh->G})
-        if (p)
-            (void)hipFree(p);
-    for (float *p : sh->maps)
-        if (p)
-            (void)hipFree(p);
-    delete sh;
-}
 
 // Where the ends of a chain read and write, and how (see PassArgs).
 struct End {
@@ -451,7 +396,7 @@ int run_chain(slicer_fft_s *f, hipStream_t st, const std::vector<Pass> &passes, 
         const size_t lds = (size_t)ps.C * ps.Rp * sizeof(double2);
         const dim3 grid((unsigned)((a.nlines + ps.C - 1) / ps.C), (unsigned)(a.L / ps.R));
         hipLaunchKernelGGL(k_fft_pass, grid, dim3(kThreads), lds, st, a);
-        SCHK(f->h, hipGetLastError());
+        HIPCHK(f->h, hipGetLastError());
         in = a.out;
     }
     return SLICER_OK;
@@ -459,14 +404,16 @@ int run_chain(slicer_fft_s *f, hipStream_t st, const std::vector<Pass> &passes, 
 
 }  // namespace
 
-int slicer_fft_create(slicer_handle h, int npix, int split, hipStream_t st, const char *who, slicer_fft_s **out)
+int slicer_fft_create(slicer_handle h, int npix, int split, hipStream_t st, int device, const char *who,
+                      slicer_fft_s **out)
 {
     *out = nullptr;
     slicer_fft_s *f = new (std::nothrow) slicer_fft_s;
     if (!f)
-        return slicer_internal_fail(h, SLICER_ERR_NOMEM, "out of host memory");
+        return fail(h, SLICER_ERR_NOMEM, "out of host memory");
     const int n = npix;
     f->h = h;
+    f->device = device;
     f->n = n;
     f->H = n / 2 + 1;
     f->len = n % 2 == 0 ? n / 2 : n;
@@ -476,31 +423,17 @@ int slicer_fft_create(slicer_handle h, int npix, int split, hipStream_t st, cons
     f->col_chain = plan_chain(n, f->H, cap(n, kColCap));
     const size_t passes = std::max(f->row_chain.size(), f->col_chain.size());
 
-    int rc = SLICER_OK, dev = 0;
-    if (hipStreamGetDevice(st, &dev) != hipSuccess)
-        rc = sfail(h, SLICER_ERR_HIP, "%s: the handle's stream has no device", who);
-    f->device = dev;
-    if (rc == SLICER_OK && hipSetDevice(dev) != hipSuccess)
-        rc = sfail(h, SLICER_ERR_HIP, "hipSetDevice(%d) failed", dev);
-    if (rc == SLICER_OK &&
-        hipFuncSetAttribute((const void *)k_fft_pass, hipFuncAttributeMaxDynamicSharedMemorySize,
+    int rc = SLICER_OK;
+    if (hipFuncSetAttribute((const void *)k_fft_pass, hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)((kLdsPoints + kMaxLines) * sizeof(double2))) != hipSuccess)
-        rc = sfail(h, SLICER_ERR_HIP, "%s: cannot raise the LDS limit of the FFT kernel", who);
-    auto alloc = [&](void **p, size_t bytes) {
-        if (rc != SLICER_OK)
-            return;
-        hipError_t e = hipMalloc(p, bytes);
-        if (e != hipSuccess)
-            rc = sfail(h, e == hipErrorOutOfMemory ? SLICER_ERR_NOMEM : SLICER_ERR_HIP,
-                       "%s: %zu bytes of device memory: %s", who, bytes, hipGetErrorString(e));
-    };
+        rc = fail(h, SLICER_ERR_HIP, "%s: cannot raise the LDS limit of the FFT kernel", who);
     const size_t cbytes = (size_t)n * f->H * sizeof(double2);
-    alloc((void **)&f->tw, (size_t)n * sizeof(double2));
-    alloc((void **)&f->A, cbytes);
+    rc = f->mem.alloc(rc, h, who, (void **)&f->tw, (size_t)n * sizeof(double2));
+    rc = f->mem.alloc(rc, h, who, (void **)&f->A, cbytes);
     if (passes >= 2)
-        alloc((void **)&f->B, cbytes);
+        rc = f->mem.alloc(rc, h, who, (void **)&f->B, cbytes);
     if (passes >= 3)
-        alloc((void **)&f->Cb, cbytes);
+        rc = f->mem.alloc(rc, h, who, (void **)&f->Cb, cbytes);
     if (rc == SLICER_OK) {
         std::vector<double2> tw(n);
         const long double two_pi = 6.283185307179586476925286766559005768L;
@@ -512,7 +445,7 @@ int slicer_fft_create(slicer_handle h, int npix, int split, hipStream_t st, cons
         if (e == hipSuccess)
             e = hipStreamSynchronize(st);  // tw is a host temporary
         if (e != hipSuccess)
-            rc = sfail(h, SLICER_ERR_HIP, "%s: twiddle upload: %s", who, hipGetErrorString(e));
+            rc = fail(h, SLICER_ERR_HIP, "%s: twiddle upload: %s", who, hipGetErrorString(e));
     }
     if (rc != SLICER_OK) {
         slicer_fft_destroy(f);
@@ -534,61 +467,40 @@ int slicer_fft_forward(slicer_fft_s *f, hipStream_t st, const float *map, double
     return run_chain(f, st, f->col_chain, true, false, e, proto);
 }
 
-void slicer_fft_destroy(slicer_fft_s *f)
-{
-    if (!f)
-        return;
-    for (void *p : {(void *)f->tw, (void *)f->A, (void *)f->B, (void *)f->Cb})
-        if (p)
-            (void)hipFree(p);
-    delete f;
-}
+void slicer_fft_destroy(slicer_fft_s *f) { delete f; }
 
-int slicer_shear_supported(int32_t n) { return smooth(n) ? 1 : 0; }
+int slicer_shear_supported(int32_t n) { return fft_size_supported(n) ? 1 : 0; }
 
 int slicer_shear_create(slicer_handle h, int32_t npix, double angle_deg, slicer_shear_handle *out)
 {
     if (!h || !out)
-        return slicer_internal_fail(h, SLICER_ERR_ARG, "slicer_shear_create: null argument");
+        return fail(h, SLICER_ERR_ARG, "slicer_shear_create: null argument");
     *out = nullptr;
-    if (!smooth(npix)) {
-        char buf[160];
-        snprintf(buf, sizeof buf, "slicer_shear_create: npix = %d unsupported (2..%d, prime factors 2, 3, 5, 7 only)",
-                 npix, kMaxN);
-        return slicer_internal_fail(h, SLICER_ERR_UNSUPPORTED, buf);
-    }
+    if (!fft_size_supported(npix))
+        return fail(h, SLICER_ERR_UNSUPPORTED,
+                    "slicer_shear_create: npix = %d unsupported (2..%d, prime factors 2, 3, 5, 7 only)", npix, kMaxN);
     if (!std::isfinite(angle_deg) || angle_deg <= 0.0)
-        return slicer_internal_fail(h, SLICER_ERR_ARG, "slicer_shear_create: the angle must be positive and finite");
-    int split = 0;
-    if (slicer_get_option(h, "shear_split", &split) != SLICER_OK)
-        return SLICER_ERR_ARG;
+        return fail(h, SLICER_ERR_ARG, "slicer_shear_create: the angle must be positive and finite");
     slicer_shear_handle sh = new (std::nothrow) slicer_shear_s;
     if (!sh)
-        return slicer_internal_fail(h, SLICER_ERR_NOMEM, "out of host memory");
+        return fail(h, SLICER_ERR_NOMEM, "out of host memory");
     const int n = npix;
     sh->h = h;
     sh->angle = angle_deg;
 
-    void *sp = nullptr;
-    int rc = slicer_get_stream(h, &sp);
-    hipStream_t st = (hipStream_t)sp;
+    const char *who = "slicer_shear_create";
+    hipStream_t st = nullptr;
+    int dev = 0;
+    int rc = sub_open(h, who, &st, &dev);
     if (rc == SLICER_OK)
-        rc = slicer_fft_create(h, n, split, st, "slicer_shear_create", &sh->fft);
-    auto alloc = [&](void **p, size_t bytes) {
-        if (rc != SLICER_OK)
-            return;
-        hipError_t e = hipMalloc(p, bytes);
-        if (e != hipSuccess)
-            rc = sfail(h, e == hipErrorOutOfMemory ? SLICER_ERR_NOMEM : SLICER_ERR_HIP,
-                       "slicer_shear_create: %zu bytes of device memory: %s", bytes, hipGetErrorString(e));
-    };
+        rc = slicer_fft_create(h, n, h->opt.shear_split, st, dev, who, &sh->fft);
     const size_t cbytes = (size_t)n * (n / 2 + 1) * sizeof(double2);
-    alloc((void **)&sh->S, cbytes);
-    alloc((void **)&sh->G, cbytes);
+    rc = sh->mem.alloc(rc, h, who, (void **)&sh->S, cbytes);
+    rc = sh->mem.alloc(rc, h, who, (void **)&sh->G, cbytes);
     for (float *&m : sh->maps)
-        alloc((void **)&m, (size_t)n * n * sizeof(float));
+        rc = sh->mem.alloc(rc, h, who, (void **)&m, (size_t)n * n * sizeof(float));
     if (rc != SLICER_OK) {
-        release(sh);
+        delete sh;
         return rc;
     }
     *out = sh;
@@ -598,9 +510,9 @@ int slicer_shear_create(slicer_handle h, int32_t npix, double angle_deg, slicer_
 int slicer_shear_run(slicer_shear_handle sh, const float *d_kappa)
 {
     if (!sh || !d_kappa)
-        return sfail(sh ? sh->h : nullptr, SLICER_ERR_ARG, "slicer_shear_run: null argument");
+        return fail(sh ? sh->h : nullptr, SLICER_ERR_ARG, "slicer_shear_run: null argument");
     hipStream_t st;
-    if (int rc = stream_of(sh, &st))
+    if (int rc = sub_stream(sh->h, sh->fft->device, &st))
         return rc;
     slicer_fft_s *f = sh->fft;
     const int n = f->n, H = f->H, len = f->len;
@@ -641,25 +553,25 @@ int slicer_shear_run(slicer_shear_handle sh, const float *d_kappa)
 int slicer_shear_spectrum(slicer_shear_handle sh, double *host)
 {
     if (!sh || !host)
-        return sfail(sh ? sh->h : nullptr, SLICER_ERR_ARG, "slicer_shear_spectrum: null argument");
+        return fail(sh ? sh->h : nullptr, SLICER_ERR_ARG, "slicer_shear_spectrum: null argument");
     if (!sh->ran)
-        return sfail(sh->h, SLICER_ERR_STATE, "slicer_shear_spectrum before any slicer_shear_run");
+        return fail(sh->h, SLICER_ERR_STATE, "slicer_shear_spectrum before any slicer_shear_run");
     hipStream_t st;
-    if (int rc = stream_of(sh, &st))
+    if (int rc = sub_stream(sh->h, sh->fft->device, &st))
         return rc;
-    SCHK(sh->h, hipMemcpyAsync(host, sh->S, (size_t)sh->fft->n * sh->fft->H * sizeof(double2), hipMemcpyDeviceToHost, st));
-    SCHK(sh->h, hipStreamSynchronize(st));
+    HIPCHK(sh->h, hipMemcpyAsync(host, sh->S, (size_t)sh->fft->n * sh->fft->H * sizeof(double2), hipMemcpyDeviceToHost, st));
+    HIPCHK(sh->h, hipStreamSynchronize(st));
     return SLICER_OK;
 }
 
 int slicer_shear_device_map(slicer_shear_handle sh, int32_t which, float **d_map)
 {
     if (!sh || !d_map)
-        return sfail(sh ? sh->h : nullptr, SLICER_ERR_ARG, "slicer_shear_device_map: null argument");
+        return fail(sh ? sh->h : nullptr, SLICER_ERR_ARG, "slicer_shear_device_map: null argument");
     if (which < SLICER_SHEAR_PHI || which > SLICER_SHEAR_GAMMA)
-        return sfail(sh->h, SLICER_ERR_ARG, "slicer_shear_device_map: which = %d, expected 0..3", which);
+        return fail(sh->h, SLICER_ERR_ARG, "slicer_shear_device_map: which = %d, expected 0..3", which);
     if (!sh->ran)
-        return sfail(sh->h, SLICER_ERR_STATE, "shear maps are available after slicer_shear_run");
+        return fail(sh->h, SLICER_ERR_STATE, "shear maps are available after slicer_shear_run");
     *d_map = sh->maps[which];
     return SLICER_OK;
 }
@@ -670,12 +582,12 @@ int slicer_shear_read(slicer_shear_handle sh, int32_t which, float *host)
     if (int rc = slicer_shear_device_map(sh, which, &d))
         return rc;
     if (!host)
-        return sfail(sh->h, SLICER_ERR_ARG, "slicer_shear_read: null host pointer");
+        return fail(sh->h, SLICER_ERR_ARG, "slicer_shear_read: null host pointer");
     hipStream_t st;
-    if (int rc = stream_of(sh, &st))
+    if (int rc = sub_stream(sh->h, sh->fft->device, &st))
         return rc;
-    SCHK(sh->h, hipMemcpyAsync(host, d, (size_t)sh->fft->n * sh->fft->n * sizeof(float), hipMemcpyDeviceToHost, st));
-    SCHK(sh->h, hipStreamSynchronize(st));
+    HIPCHK(sh->h, hipMemcpyAsync(host, d, (size_t)sh->fft->n * sh->fft->n * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(sh->h, hipStreamSynchronize(st));
     return SLICER_OK;
 }
 
@@ -683,11 +595,8 @@ int slicer_shear_destroy(slicer_shear_handle sh)
 {
     if (!sh)
         return SLICER_ERR_ARG;
-    void *sp = nullptr;
-    if (slicer_get_stream(sh->h, &sp) == SLICER_OK) {
-        (void)hipSetDevice(sh->fft->device);
-        (void)hipStreamSynchronize((hipStream_t)sp);
-    }
-    release(sh);
+    (void)hipSetDevice(sh->fft->device);
+    (void)hipStreamSynchronize(sh->h->stream);
+    delete sh;
     return SLICER_OK;
 }

@@ -374,7 +374,7 @@ def test_tsc_weights_bitwise_through_fixed_point(S, npix, algo):
     x, y, z = oracle.transform(f["pos"], BOX, RND["sgn"], RND["face"], RND["center"], RND["rcase"])
     xs, ys, ms = oracle.select_project(x, y, z, None, m, ld, ld2, BOX, 0, fov, npix)
     pix, val = npr.tsc_contributions(xs, ys, ms, npix)
-    scale = 2.0 ** (40 - (int(np.floor(np.log2(m))) + 1))  # slicer_capi.cpp pick_fixed_exp
+    scale = 2.0 ** (40 - (int(np.floor(np.log2(m))) + 1))  # pass_plan.cpp pick_fixed_exp
     q = np.rint(val.astype(np.float64) * scale).astype(np.int64)
     acc = np.zeros(npix * npix, np.int64)
     ok = pix >= 0
