@@ -8,7 +8,10 @@ GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def names():
-    return sorted(os.path.splitext(os.path.basename(p))[0] for p in glob.glob(os.path.join(GOLDEN_DIR, "*.npz")))
+    """The oracle vectors of the directory: the archives that hold results (files that hold inputs only, such as
+    k1_edges.npz, are not among them)."""
+    return sorted(os.path.splitext(os.path.basename(p))[0] for p in glob.glob(os.path.join(GOLDEN_DIR, "*.npz"))
+                  if {"nfiles", "tot", "nsel"} <= set(np.load(p, allow_pickle=False).files))
 
 
 def load(name):
