@@ -1,6 +1,31 @@
-// slicer_binned_common.hpp -- helpers shared by the kernels of SLICER_ALGO_BINNED (slicer_project_bin.hip: K1;
-// slicer_binned.hip: K2-K4).  gfx950 only.
+// slicer_binned_common.hpp -- SLICER_ALGO_BINNED: project -> per-tile bins -> LDS-privatised tile deposit.  The overview
+// of the path, and what its kernels share (slicer_project_bin.hip: K1; slicer_sort.hip: K2, K3; slicer_tile_deposit.hip:
+// K4).  gfx950 only.
+//
+// Why: a TSC deposit is 9 read-modify-writes on a random pixel; as global float atomics that is
+// ~0.08 TB/s of added bytes on MI355X (64 lanes in 64 rows; MI355X_MICROARCH.md "Global float
+// atomics"), i.e. ~2e9 particles/s.  Here the scatter is done in LDS instead:
+//
+//   K1 k_project_bin_* : (slicer_project_bin.hip) stream raw POS (12 B/particle, dwordx4 loads), bit-faithful
+//                        transform, slab select, fp64 projection; emits (xs, ys) records + their tile bin, a
+//                        per-workgroup histogram row and the workgroup's record counts.  No global atomics on the
+//                        data path.
+//   K2 k_scan_blocks   : exclusive prefix over (bin-major, workgroup-minor) -> every K1 workgroup's write cursor for
+//                        every bin (radix-partition style; no atomics), plus in-group bin prefixes and group sums
+//                        from which K3 derives the bin bases itself.
+//   K3 k_bin_scatter   : moves each record to its bin's contiguous run: persistent workgroups counting-sort
+//                        the records of one (plane, K1 workgroup) region by tile in LDS and store them in
+//                        tile order (coalesced runs).
+//   K4 k_tile_deposit  : one workgroup per (plane, tile) (more for heavy tiles): tile + 1-pixel halo
+//                        privatised in LDS as 8-byte cells (f64 or integer) or 4-byte NGP counts, one software-pipelined
+//                        walk over all pending chunks, then one shaped (row-contiguous) flush of the non-zero cells;
+//                        NGP counts of whole sub-files are folded into the f32 maps at the file boundaries of the walk.
+//
+// Replaces the CPU loops of gadget2io.cpp:195-274, densitymaps.cpp:355-401 and utilities.cpp:66-95.
 #pragma once
+#include <type_traits>
+#include <utility>
+
 #include "slicer_kernels.hpp"
 
 namespace slicer {
@@ -47,6 +72,22 @@ __device__ __forceinline__ void cell_to_tile(int gx, int gy, int plane, const Bi
     }
     unit = (unsigned)plane * (unsigned)G.units_per_plane + band;
     tile_in_unit = trow * (unsigned)G.ntx + tx;
+}
+
+// Launch `kern` with `lds` bytes of dynamic LDS.  A kernel gets 48 KiB without asking; its limit is raised first where
+// `lds` exceeds `raise_above` (0: always).
+template <typename... Params, typename... Args>
+inline hipError_t launch_with_lds(void (*kern)(Params...), unsigned grid, unsigned block, size_t lds, size_t raise_above,
+                                  hipStream_t s, Args &&...args)
+{
+    if (lds > raise_above) {
+        const hipError_t e =
+            hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess)
+            return e;
+    }
+    kern<<<grid, block, lds, s>>>(std::forward<Args>(args)...);
+    return hipGetLastError();
 }
 
 }  // namespace slicer

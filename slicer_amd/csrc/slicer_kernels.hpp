@@ -93,7 +93,7 @@ hipError_t launch_debug_project(const float *d_pos, uint64_t n, const PassParams
                                 int32_t *d_plane, uint64_t *d_src, uint64_t capacity, unsigned long long *d_count,
                                 int *neg_flag, hipStream_t s);
 
-// ---- SLICER_ALGO_BINNED (slicer_binned.hip) ----
+// ---- SLICER_ALGO_BINNED (slicer_project_bin.hip, slicer_sort.hip, slicer_tile_deposit.hip) ----
 struct BinGeom {
     int tw_log2, th_log2;  // tile width / height in pixels (powers of two)
     int ntx, nty;          // tiles per map row / column

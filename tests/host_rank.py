@@ -4,7 +4,7 @@ It holds what a slicer handle holds after the last file_end() of a pass -- per-s
 accumulator type -- computed with the oracle (selection, projection) and the numpy restatement (bit-exact TSC
 contributions), and answers the same five calls slicer_amd.parallel.reduce_planes makes on a real handle
 (include/slicer_amd.h, "cross-rank sum in the accumulator type").  Slot s = particle type 0..5, slot 6 = the shared
-all-types accumulator.  Accumulator semantics restated from binned_pass.cpp / slicer_binned.hip:
+all-types accumulator.  Accumulator semantics restated from binned_pass.cpp / slicer_tile_deposit.hip:
   f32     per-slot f32 sums (order here: particle order; on the device: atomics)
   f64     per-slot f64 sums of the f32 contributions
   fixed64 per-slot integer sums of rint(c * 2^k), k = 40 - (ilogb(m) + 1): order-independent => bitwise reproducible

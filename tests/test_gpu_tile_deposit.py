@@ -407,6 +407,40 @@ def test_ngp_with_per_particle_masses_against_exact_mass_sums(S):
         assert len(bad) == 0, (ACC_IDS[accum], len(bad), P.upix[bad[:4]], k[bad[:4]], J[bad[:4]])
 
 
+def test_ngp_mass_sums_through_the_wave_pre_reduction(S):
+    """114689 records with per-particle masses in one pixel of one interior tile of a 512^2 map: 8 parts, the fewest
+    that take the heavy-bin walk, whose NGP branch sums the masses of a wave before one lane adds them.  Same bound as
+    above, against the exact sum of the capped masses."""
+    rng = np.random.default_rng(9)
+    n, npix = 114689, 512
+    px, py = 64 + 5, 64 + 7  # tile (1, 1) of 8 x 8
+    pos = place(n, npix, (px + 0.02, px + 0.98, py + 0.02, py + 0.98), rng)
+    m0 = decade_masses(n, rng, top=0.05)
+    xs, ys, ms, _ = forward(pos, m0, 0.0, npix)
+    gx, gy = centre_pixels(xs, ys, npix)
+    assert len(xs) == n and np.all(gx == px) and np.all(gy == py)
+    pix = (gx + npix * gy)[:, None]
+    P = tnp.Pixels(pix, ms[:, None], npix, tnp.mass_le(ms.max()))
+    E, k = P.exact(), P.count()
+    tile = (gy >> TL) * (npix >> TL) + (gx >> TL)
+    J, parts = tnp.addends(P, pix, ms[:, None], tile, np.zeros(n, np.int64), False)
+    assert list(k) == [n] and list(parts.values()) == [8] and n > 100 * J[0]
+    for accum in (F32A, F64A):
+        for opt, v in (("tile_log2", TL), ("tile_h_log2", TL), ("pending", 32), ("k4_int", 2), ("sort2", 0)):
+            S.set_option(opt, v)
+        S.plane_begin(npix, FOV, [LD], [LD2], mas=slicer_amd.MAS_NGP, accum=accum, algo=slicer_amd.ALGO_BINNED, hydro=True)
+        S.file_begin([n, 0, 0, 0, 0, 0], [0.0] * 6, BOX, RND["sgn"], RND["face"], RND["center"], RND["rcase"])
+        S.deposit_host(0, pos, m0)
+        S.file_end()
+        assert (S.algo_mask() & 7) == 1 << slicer_amd.ALGO_BINNED
+        tot, toti, nsel = S.plane_read(0)
+        assert int(nsel[0]) == n and int(nsel.sum()) == n
+        assert np.count_nonzero(toti[0]) == 1 and toti[0][py, px] != 0
+        err = abs(P.units(toti[0]) - E) * (1 << 53)
+        lim = ((2 * J.astype(object) - 1) * (1 << 29) + k.astype(object)) * E
+        assert err[0] <= lim[0], (ACC_IDS[accum], float(err[0]) / float(E[0]) / 2.0 ** 53, J[0])
+
+
 # ---- maps that are not a power of two wide, with masses ---------------------------------------------------------
 @pytest.mark.parametrize("npix", [100, 296, 1000])
 def test_ragged_edge_tiles_with_per_particle_masses(S, npix):
