@@ -360,6 +360,57 @@ int slicer_shear_device_map(slicer_shear_handle sh, int32_t which, float **d_map
 int slicer_shear_read(slicer_shear_handle sh, int32_t which, float *host);
 int slicer_shear_destroy(slicer_shear_handle sh);
 
+/* ---- Deflection maps, and the finite-difference derivatives of a potential map ----
+ * Spectral deflection alpha = grad phi, in the notation of N6 (phihat = -2 khat / k^2, 0 at k = 0):
+ *   alpha1 = irfft2(i K0 phihat);  alpha2 = irfft2(i K1 phihat),  s = (npix, npix), in radians,
+ * computed in f64 and rounded once to f32; irfft2's Hermitian projection of the columns k1 = 0 and k1 = npix/2 decides
+ * what becomes of row and column npix/2, as for the maps of N6.
+ *   slicer_shear_deflection  both maps from the spectrum of the last slicer_shear_run (two inverse transforms, no forward
+ *                            one); enqueued, no synchronisation.  Before any run: SLICER_ERR_STATE.  The two f32 maps
+ *                            are allocated by the first call (SLICER_ERR_NOMEM); the maps of N6 and the spectrum are
+ *                            left as they are.
+ *   slicer_shear_device_map / _read with SLICER_SHEAR_ALPHA1 / _ALPHA2: SLICER_ERR_STATE until slicer_shear_deflection
+ *                            has followed the last slicer_shear_run.  shear_split = 1 gives bitwise the same maps.
+ * Finite differences (the real-space mode of the reference's smr.smr(..., derivative="gradient"); a light-cone map is not
+ * periodic, and these stencils do not wrap its edges).  On a line f of n >= 5 samples of spacing d:
+ *   D1 f[i] = (f[i-2] - 8 f[i-1] + 8 f[i+1] - f[i+2]) / (12 d)                 for 2 <= i <= n-3,
+ *             (f[i+1] - f[i]) / d  at i = 0, 1  and  (f[i] - f[i-1]) / d  at i = n-2, n-1;
+ *   D2 f[i] = (-f[i-2] + 16 f[i-1] - 30 f[i] + 16 f[i+1] - f[i+2]) / (12 d^2)   for 2 <= i <= n-3,
+ *             (2 f[i] - 5 f[i+1] + 4 f[i+2] - f[i+3]) / d^2  at i = 0, 1  and its mirror image at i = n-2, n-1.
+ * From an f32 npix^2 map phi (axis 0 slow, axis 1 contiguous): ALPHA1 = D1 along axis 0, ALPHA2 = D1 along axis 1,
+ * p11 = D2 along axis 0, p22 = D2 along axis 1, p12 = D1 along axis 1 of D1 along axis 0 (equal to the other order),
+ * KAPPA = (p11 + p22) / 2, GAMMA1 = (p11 - p22) / 2, GAMMA2 = p12, GAMMA = sqrt(GAMMA1^2 + GAMMA2^2); everything in f64
+ * from the f32 samples, each output rounded once to f32.  Any npix from 5 to 524288: no restriction on its factors.
+ *   slicer_fd_derivatives    one kernel on the stream of h; enqueued, no synchronisation.  d_out[SLICER_FD_*]: device
+ *                            buffers of npix^2 floats owned by the caller; NULL entries are skipped.  SLICER_ERR_ARG:
+ *                            npix outside 5..524288, a spacing that is not positive and finite, a NULL input, every
+ *                            output NULL, an output equal to the input.  The same input gives bitwise the same maps,
+ *                            wherever the pointers lie and whichever outputs are asked for.
+ *   slicer_shear_fd          the same of the handle's f32 phi of the last slicer_shear_run with d = theta / npix, into six
+ *                            maps of the handle's, allocated by the first call (SLICER_ERR_NOMEM); read with
+ *                            SLICER_SHEAR_FD_ALPHA1 ... _FD_GAMMA under the state rule of the deflection maps.  Before
+ *                            any run: SLICER_ERR_STATE; a handle of npix < 5: SLICER_ERR_UNSUPPORTED.
+ * The `which` codes 4 ... 7 and 10 ... 15 name nothing (SLICER_ERR_ARG). */
+#define SLICER_SHEAR_ALPHA1 8
+#define SLICER_SHEAR_ALPHA2 9
+#define SLICER_FD_ALPHA1 0
+#define SLICER_FD_ALPHA2 1
+#define SLICER_FD_KAPPA 2
+#define SLICER_FD_GAMMA1 3
+#define SLICER_FD_GAMMA2 4
+#define SLICER_FD_GAMMA 5
+#define SLICER_FD_COUNT 6
+#define SLICER_SHEAR_FD_ALPHA1 16 /* SLICER_SHEAR_FD_ALPHA1 + SLICER_FD_*: */
+#define SLICER_SHEAR_FD_ALPHA2 17
+#define SLICER_SHEAR_FD_KAPPA 18
+#define SLICER_SHEAR_FD_GAMMA1 19
+#define SLICER_SHEAR_FD_GAMMA2 20
+#define SLICER_SHEAR_FD_GAMMA 21
+int slicer_shear_deflection(slicer_shear_handle sh);
+int slicer_shear_fd(slicer_shear_handle sh);
+int slicer_fd_derivatives(slicer_handle h, int32_t npix, double spacing, const float *d_phi,
+                          float *const d_out[SLICER_FD_COUNT]);
+
 /* ---- Binned auto and cross power spectra of kappa maps ----
  * For n_maps maps kappa_s of npix^2 pixels (row i0 slow, i1 contiguous) of side theta = angle_deg * pi / 180 radians:
  * khat_s = rfft2(kappa_s) in f64 on the [npix][npix/2+1] half plane (the spectrum of slicer_shear_run).  Mode (i0, i1)

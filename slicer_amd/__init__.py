@@ -7,7 +7,9 @@ from . import _lib, gadget, synth  # noqa: F401
 from .api import (ACC_F32, ACC_F64, ACC_FIXED64, ALGO_AUTO, ALGO_BINNED, ALGO_DIRECT, ELEM_F32, ELEM_F64,  # noqa: F401
                   ELEM_FIXED64, MAS_NGP, MAS_TSC, InputParams, Lens, Random, Slicer, SlicerError, createDensityMaps)
 
-from .lensing import (SHEAR_GAMMA, SHEAR_GAMMA1, SHEAR_GAMMA2, SHEAR_PHI, Kappa, Power, Shear,  # noqa: F401
-                      ell_fundamental, plane_weights, power_bins, shear_supported)
+from .lensing import (FD_ALPHA1, FD_ALPHA2, FD_COUNT, FD_GAMMA, FD_GAMMA1, FD_GAMMA2, FD_KAPPA,  # noqa: F401
+                      SHEAR_ALPHA1, SHEAR_ALPHA2, SHEAR_FD_ALPHA1, SHEAR_FD_ALPHA2, SHEAR_FD_GAMMA, SHEAR_FD_GAMMA1,
+                      SHEAR_FD_GAMMA2, SHEAR_FD_KAPPA, SHEAR_GAMMA, SHEAR_GAMMA1, SHEAR_GAMMA2, SHEAR_PHI, Kappa, Power,
+                      Shear, ell_fundamental, fd_derivatives, fd_run, plane_weights, power_bins, shear_supported)
 
 __version__ = "0.2.0"

@@ -96,6 +96,9 @@ SYMBOLS = {
     "slicer_shear_device_map": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_void_p)]),
     "slicer_shear_read": (C.c_int, [_H, C.c_int32, C.c_void_p]),
     "slicer_shear_destroy": (C.c_int, [_H]),
+    "slicer_shear_deflection": (C.c_int, [_H]),
+    "slicer_shear_fd": (C.c_int, [_H]),
+    "slicer_fd_derivatives": (C.c_int, [_H, C.c_int32, C.c_double, C.c_void_p, C.POINTER(C.c_void_p)]),
     "slicer_power_bins": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "slicer_power_create": (C.c_int, [_H, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                       C.POINTER(C.c_void_p)]),

@@ -15,6 +15,10 @@
 //     --kappa-no-growth drops its linear-growth correction.  Without --kappa the run is unchanged.
 //   * --shear (with --kappa) also writes, per source, the shear maps gamma1, gamma2, |gamma| and the lensing potential
 //     phi computed on device 0 from the kappa map (the reference's Lens/smr.py).
+//   * --deflection (with --shear) also writes the deflection maps alpha1, alpha2 (.alpha1_z, .alpha2_z, the kappa
+//     header); --shear-derivative fft|gradient (with --shear, default fft) chooses where gamma1, gamma2, |gamma| and
+//     the alphas come from: the FFT filters, or smr's derivative="gradient", finite differences of phi that do not
+//     wrap the map's edges.  The phi and kappa files are the same either way.
 //   * --power auto|cross (with --kappa) also writes <directory><simulation>.cl_<npix>_<suffix>.txt: the binned auto
 //     (or auto and cross) power spectra C_l of the kappa maps, computed on device 0 (Lens/smr.py's PS without its
 //     defects); --power-edges r0,r1,... sets the bin edges in units of l_f = 2 pi / ANGLE
@@ -272,7 +276,8 @@ int host_plane_reduce(vector<Rank> &ranks, int npix, int n_planes)
 
 struct Options {
     string inifile, plan_path, devices_spec, reduce_mode = "rccl", reduce_algo = "rooted", kappa_spec;
-    bool kappa_growth = true, shear = false;
+    bool kappa_growth = true, shear = false, deflection = false;
+    string shear_derivative;     // "" (not given: fft), "fft" or "gradient"
     string power;                // "", "auto" or "cross"
     vector<double> power_edges;  // empty: the default edges
     int device = 0, mas = SLICER_MAS_TSC, accum = SLICER_ACC_F32;
@@ -300,6 +305,8 @@ int parse_args(int argc, char **argv, Options &o)
         else if (a == "--kappa" && i + 1 < argc) o.kappa_spec = argv[++i];  // all | z1,z2,...
         else if (a == "--kappa-no-growth") o.kappa_growth = false;
         else if (a == "--shear") o.shear = true;
+        else if (a == "--deflection") o.deflection = true;
+        else if (a == "--shear-derivative" && i + 1 < argc) o.shear_derivative = argv[++i];  // fft | gradient
         else if (a == "--power" && i + 1 < argc) o.power = argv[++i];  // auto | cross
         else if (a == "--power-edges" && i + 1 < argc) {
             for (const string &tok : split(argv[++i])) {
@@ -324,6 +331,18 @@ int parse_args(int argc, char **argv, Options &o)
     }
     if (o.shear && o.kappa_spec.empty()) {
         cerr << "--shear needs --kappa (the shear maps are computed from the kappa maps)" << endl;
+        return 2;
+    }
+    if (o.deflection && !o.shear) {
+        cerr << "--deflection needs --shear (the deflection maps are computed from the spectrum of the shear maps)" << endl;
+        return 2;
+    }
+    if (!o.shear_derivative.empty() && o.shear_derivative != "fft" && o.shear_derivative != "gradient") {
+        cerr << "bad --shear-derivative (fft or gradient)" << endl;
+        return 2;
+    }
+    if (!o.shear_derivative.empty() && !o.shear) {
+        cerr << "--shear-derivative needs --shear" << endl;
         return 2;
     }
     if (!o.power.empty() && o.power != "auto" && o.power != "cross") {
@@ -374,6 +393,10 @@ int plan_cone(const Options &o, Cone &c)
         return 1;
     if (o.shear && !slicer_shear_supported(p.npix)) {
         cerr << "--shear: npix = " << p.npix << " is not supported (2 ... 16384, prime factors 2, 3, 5, 7 only)" << endl;
+        return 2;
+    }
+    if (o.shear_derivative == "gradient" && p.npix < 5) {
+        cerr << "--shear-derivative gradient: npix = " << p.npix << " is not supported (the stencils take at least 5)" << endl;
         return 2;
     }
     if (!o.power.empty() && !slicer_shear_supported(p.npix)) {
@@ -531,6 +554,7 @@ struct LensingOutputs {
     slicer_kappa_handle kh = nullptr;  // nullptr without --kappa
     slicer_shear_handle shh = nullptr;
     slicer_power_handle ph = nullptr;
+    bool deflection = false, gradient = false;  // --deflection; --shear-derivative gradient
     string power_mode{};           // "", "auto" or "cross"
     vector<double> power_edges{};  // empty: 0 .. npix-1
     vector<float *> upload{};  // device buffers for planes read back from their files
@@ -627,11 +651,18 @@ struct LensingOutputs {
         vector<float> map((size_t)p.npix * (size_t)p.npix);
         if (slicer_kappa_finalize(kh) != SLICER_OK)
             return fail(h, "slicer_amd: --kappa");
-        const struct {
-            const char *token;
+        struct Out {
+            const char *what, *token;
             int which;
-        } outs[4] = {{".gamma1_z", SLICER_SHEAR_GAMMA1}, {".gamma2_z", SLICER_SHEAR_GAMMA2},
-                     {".gamma_z", SLICER_SHEAR_GAMMA}, {".phi_z", SLICER_SHEAR_PHI}};
+        };
+        vector<Out> outs = {{"shear", ".gamma1_z", gradient ? SLICER_SHEAR_FD_GAMMA1 : SLICER_SHEAR_GAMMA1},
+                            {"shear", ".gamma2_z", gradient ? SLICER_SHEAR_FD_GAMMA2 : SLICER_SHEAR_GAMMA2},
+                            {"shear", ".gamma_z", gradient ? SLICER_SHEAR_FD_GAMMA : SLICER_SHEAR_GAMMA},
+                            {"shear", ".phi_z", SLICER_SHEAR_PHI}};
+        if (deflection) {
+            outs.push_back({"deflection", ".alpha1_z", gradient ? SLICER_SHEAR_FD_ALPHA1 : SLICER_SHEAR_ALPHA1});
+            outs.push_back({"deflection", ".alpha2_z", gradient ? SLICER_SHEAR_FD_ALPHA2 : SLICER_SHEAR_ALPHA2});
+        }
         for (size_t s = 0; s < zs.size(); s++) {
             char zbuf[32];
             snprintf(zbuf, sizeof zbuf, "%.4f", zs[s]);
@@ -643,8 +674,11 @@ struct LensingOutputs {
             float *d_kappa = nullptr;
             if (slicer_kappa_device_map(kh, (int)s, &d_kappa) != SLICER_OK || slicer_shear_run(shh, d_kappa) != SLICER_OK)
                 return fail(h, "slicer_amd: --kappa");
+            if ((gradient && slicer_shear_fd(shh) != SLICER_OK) ||
+                (deflection && !gradient && slicer_shear_deflection(shh) != SLICER_OK))
+                return fail(h, "slicer_amd: --shear");
             for (const auto &o : outs)
-                if (slicer_shear_read(shh, o.which, map.data()) != SLICER_OK || !save("shear", o.token, zbuf, map, keys))
+                if (slicer_shear_read(shh, o.which, map.data()) != SLICER_OK || !save(o.what, o.token, zbuf, map, keys))
                     return fail(h, "slicer_amd: --kappa");
         }
         return ph ? write_power() : 0;
@@ -851,6 +885,8 @@ int main(int argc, char **argv)
     if (const int rc = ranks.create(devs, c.p.snopt, o.reduce_mode == "rccl"))
         return rc;
     LensingOutputs lensing{ranks.root(), c.p, c.lens, kappa_zs, kappa_c};  // (after `ranks`, see there)
+    lensing.deflection = o.deflection;
+    lensing.gradient = o.shear_derivative == "gradient";
     lensing.power_mode = o.power;
     lensing.power_edges = o.power_edges;
     if (const int rc = lensing.create(o.shear))

@@ -16,6 +16,8 @@
 //   inverse rows     the c2r merge (with irfft's Hermitian projection of columns 0 and n/2) fused into the first row
 //                    load; the last row pass rounds to f32.  gamma1's last pass keeps f64 (aux); gamma2's last pass
 //                    reads it and writes gamma1, gamma2 and |gamma|.
+// The deflection maps (row N8, slicer_shear_deflection) are two more inverses of the kept spectrum: the filter cases
+// alpha1 = i K0 phihat and alpha2 = i K1 phihat, then the same column and row chains with the plain f32 store.
 // Twiddles: one f64 table W_n^j = exp(-2 pi i j / n), j < n, from long-double sincos on the host.  No atomics and
 // no work handed between workgroups: the results are bitwise repeatable.  The plan and the forward chains are shared
 // with the power-spectrum handle (slicer_power.hip) through slicer_fft.hpp.
@@ -53,8 +55,9 @@ struct PassArgs {
     int nlines, C, Rp;   // lines of the chain; lines per workgroup; LDS pitch of a line
     int ls_in, es_in, ls_out, es_out;  // L_COMPLEX / S_COMPLEX strides (line, element), in complex elements
     int load, store, inv, cfast;       // cfast: adjacent threads take adjacent lines (columns)
-    int filt;                          // L_FILTER: SLICER_SHEAR_PHI / _GAMMA1 / _GAMMA2
+    int filt;                          // L_FILTER: SLICER_SHEAR_PHI / _GAMMA1 / _GAMMA2 / _ALPHA1 / _ALPHA2
     double phi_c;                      // L_FILTER phi: -2 / (2 pi / theta)^2
+    double alpha_c;                    // L_FILTER alpha: -2 / (2 pi / theta)
     double scale;                      // S_REAL_* / S_GAMMA_*: 1 / n^2
     int nst;
     int rad[kMaxStages];
@@ -115,8 +118,12 @@ __device__ double2 load_point(const PassArgs &a, int l, int e)
             g = a.phi_c / k2;
         else if (a.filt == SLICER_SHEAR_GAMMA1)
             g = (f0 * f0 - f1 * f1) / k2;
-        else
+        else if (a.filt == SLICER_SHEAR_GAMMA2)
             g = 2.0 * f0 * f1 / k2;
+        else {  // i K_a phihat = i g khat, g = -2 f_a / (l_f k2)
+            g = a.alpha_c * (a.filt == SLICER_SHEAR_ALPHA1 ? f0 : f1) / k2;
+            return make_double2(-s.y * g, s.x * g);
+        }
         return make_double2(s.x * g, s.y * g);
     }
     case L_C2R_EVEN: {  // Z'[e] = (X + Y) + i W_n^-e (X - Y), X = U[l][e], Y = conj U[l][h-e]; irfft keeps Re at 0, h
@@ -338,7 +345,10 @@ struct slicer_shear_s {
     double angle = 0.0;
     double2 *S = nullptr, *G = nullptr;  // complex f64, n * H each
     float *maps[4] = {nullptr, nullptr, nullptr, nullptr};
+    float *alpha[2] = {nullptr, nullptr};  // allocated by the first slicer_shear_deflection
+    float *fd[SLICER_FD_COUNT] = {};       // allocated by the first slicer_shear_fd
     bool ran = false;
+    bool alpha_ok = false, fd_ok = false;  // alpha / fd belong to the last run
     DevAllocs mem;
     SLICER_FFT_INTERNAL ~slicer_shear_s() { slicer_fft_destroy(fft); }
 };
@@ -547,6 +557,68 @@ int slicer_shear_run(slicer_shear_handle sh, const float *d_kappa)
             return rc;
     }
     sh->ran = true;
+    sh->alpha_ok = sh->fd_ok = false;
+    return SLICER_OK;
+}
+
+int slicer_shear_deflection(slicer_shear_handle sh)
+{
+    if (!sh)
+        return fail(nullptr, SLICER_ERR_ARG, "slicer_shear_deflection: null argument");
+    if (!sh->ran)
+        return fail(sh->h, SLICER_ERR_STATE, "slicer_shear_deflection before any slicer_shear_run");
+    hipStream_t st;
+    if (int rc = sub_stream(sh->h, sh->fft->device, &st))
+        return rc;
+    slicer_fft_s *f = sh->fft;
+    const int n = f->n;
+    const bool even = n % 2 == 0;
+    int rc = SLICER_OK;
+    for (float *&m : sh->alpha)
+        if (!m)
+            rc = sh->mem.alloc(rc, sh->h, "slicer_shear_deflection", (void **)&m, (size_t)n * n * sizeof(float));
+    if (rc != SLICER_OK)
+        return rc;
+    sh->alpha_ok = false;
+    PassArgs p{};
+    p.alpha_c = -2.0 / (2.0 * M_PI / (sh->angle * M_PI / 180.0));
+    p.scale = 1.0 / ((double)n * (double)n);
+    // filter + columns S -> A; c2r rows A -> map, as for phi
+    for (int a = 0; a < 2; a++) {
+        p.filt = a == 0 ? SLICER_SHEAR_ALPHA1 : SLICER_SHEAR_ALPHA2;
+        End e{sh->S, f->A, L_FILTER, S_COMPLEX, 0, 0, 1, f->H};
+        if (int r = run_chain(f, st, f->col_chain, true, true, e, p))
+            return r;
+        e = End{f->A, sh->alpha[a], even ? L_C2R_EVEN : L_C2R_PAIR, even ? S_REAL_EVEN : S_REAL_PAIR, 0, 0, 0, 0};
+        if (int r = run_chain(f, st, f->row_chain, false, true, e, p))
+            return r;
+    }
+    sh->alpha_ok = true;
+    return SLICER_OK;
+}
+
+int slicer_shear_fd(slicer_shear_handle sh)
+{
+    if (!sh)
+        return fail(nullptr, SLICER_ERR_ARG, "slicer_shear_fd: null argument");
+    const int n = sh->fft->n;
+    if (n < 5)
+        return fail(sh->h, SLICER_ERR_UNSUPPORTED, "slicer_shear_fd: npix = %d, the stencils take at least 5", n);
+    if (!sh->ran)
+        return fail(sh->h, SLICER_ERR_STATE, "slicer_shear_fd before any slicer_shear_run");
+    hipStream_t st;
+    if (int rc = sub_stream(sh->h, sh->fft->device, &st))
+        return rc;
+    int rc = SLICER_OK;
+    for (float *&m : sh->fd)
+        if (!m)
+            rc = sh->mem.alloc(rc, sh->h, "slicer_shear_fd", (void **)&m, (size_t)n * n * sizeof(float));
+    if (rc != SLICER_OK)
+        return rc;
+    sh->fd_ok = false;
+    if (int r = slicer_fd_derivatives(sh->h, n, sh->angle * M_PI / 180.0 / n, sh->maps[SLICER_SHEAR_PHI], sh->fd))
+        return r;
+    sh->fd_ok = true;
     return SLICER_OK;
 }
 
@@ -568,11 +640,23 @@ int slicer_shear_device_map(slicer_shear_handle sh, int32_t which, float **d_map
 {
     if (!sh || !d_map)
         return fail(sh ? sh->h : nullptr, SLICER_ERR_ARG, "slicer_shear_device_map: null argument");
-    if (which < SLICER_SHEAR_PHI || which > SLICER_SHEAR_GAMMA)
-        return fail(sh->h, SLICER_ERR_ARG, "slicer_shear_device_map: which = %d, expected 0..3", which);
-    if (!sh->ran)
-        return fail(sh->h, SLICER_ERR_STATE, "shear maps are available after slicer_shear_run");
-    *d_map = sh->maps[which];
+    if (which >= SLICER_SHEAR_PHI && which <= SLICER_SHEAR_GAMMA) {
+        if (!sh->ran)
+            return fail(sh->h, SLICER_ERR_STATE, "shear maps are available after slicer_shear_run");
+        *d_map = sh->maps[which];
+    } else if (which == SLICER_SHEAR_ALPHA1 || which == SLICER_SHEAR_ALPHA2) {
+        if (!sh->alpha_ok)
+            return fail(sh->h, SLICER_ERR_STATE,
+                        "deflection maps are available after slicer_shear_deflection of the last slicer_shear_run");
+        *d_map = sh->alpha[which - SLICER_SHEAR_ALPHA1];
+    } else if (which >= SLICER_SHEAR_FD_ALPHA1 && which <= SLICER_SHEAR_FD_GAMMA) {
+        if (!sh->fd_ok)
+            return fail(sh->h, SLICER_ERR_STATE,
+                        "finite-difference maps are available after slicer_shear_fd of the last slicer_shear_run");
+        *d_map = sh->fd[which - SLICER_SHEAR_FD_ALPHA1];
+    } else {
+        return fail(sh->h, SLICER_ERR_ARG, "slicer_shear_device_map: which = %d, expected 0..3, 8, 9 or 16..21", which);
+    }
     return SLICER_OK;
 }
 

@@ -1,10 +1,12 @@
 """Born-approximation convergence (kappa) maps from the lens planes, and the shear and lensing
-potential maps from them (row N6), and the binned auto and cross power spectra of such maps (row N7).
+potential maps from them (row N6), the binned auto and cross power spectra of such maps (row N7), and the deflection
+maps and finite-difference derivatives of the potential (row N8).
 
 plane_weights wraps the host weights of include/slicer_amd.h (slicer_lensing_weights); Kappa is the device accumulator
 (slicer_kappa_*) bound to a Slicer handle: it reads the finalized plane maps where they are, in HBM.  Shear (slicer_shear_*)
-turns one kappa map into phi, gamma1, gamma2 and |gamma| on the same device; Power (slicer_power_*) bins the spectra
-of several of them into C_l.
+turns one kappa map into phi, gamma1, gamma2 and |gamma| on the same device, and on request into the deflection maps
+(Shear.deflection) and the finite-difference alpha, kappa and shear of phi (Shear.fd; fd_derivatives for any device
+map); Power (slicer_power_*) bins the spectra of several of them into C_l.
 """
 import ctypes as C
 import math
@@ -114,6 +116,10 @@ class Kappa:
 
 
 SHEAR_PHI, SHEAR_GAMMA1, SHEAR_GAMMA2, SHEAR_GAMMA = 0, 1, 2, 3
+SHEAR_ALPHA1, SHEAR_ALPHA2 = 8, 9
+FD_ALPHA1, FD_ALPHA2, FD_KAPPA, FD_GAMMA1, FD_GAMMA2, FD_GAMMA = range(6)
+FD_COUNT = 6
+SHEAR_FD_ALPHA1, SHEAR_FD_ALPHA2, SHEAR_FD_KAPPA, SHEAR_FD_GAMMA1, SHEAR_FD_GAMMA2, SHEAR_FD_GAMMA = range(16, 22)
 
 
 def shear_supported(npix):
@@ -163,6 +169,14 @@ class Shear:
         self._s._chk(_L.slicer_shear_spectrum(self._sh, out.ctypes.data))
         return out
 
+    def deflection(self):
+        """The deflection maps of the last run (read / device_map with SHEAR_ALPHA1, SHEAR_ALPHA2)."""
+        self._s._chk(_L.slicer_shear_deflection(self._sh))
+
+    def fd(self):
+        """The finite-difference maps of the last run's phi (read / device_map with SHEAR_FD_*)."""
+        self._s._chk(_L.slicer_shear_fd(self._sh))
+
     def device_map(self, which):
         p = C.c_void_p()
         self._s._chk(_L.slicer_shear_device_map(self._sh, int(which), C.byref(p)))
@@ -172,6 +186,30 @@ class Shear:
         out = np.empty((self.npix, self.npix), np.float32)
         self._s._chk(_L.slicer_shear_read(self._sh, int(which), out.ctypes.data))
         return out
+
+
+def fd_run(slicer: Slicer, d_phi, npix, spacing, ptrs):
+    """slicer_fd_derivatives as it is: ptrs are FD_COUNT device addresses of npix^2 f32 buffers, None to skip one."""
+    arr = (C.c_void_p * FD_COUNT)(*[None if p is None else int(p) for p in ptrs])
+    slicer._chk(_L.slicer_fd_derivatives(slicer._h, int(npix), float(spacing), None if d_phi is None else int(d_phi), arr))
+
+
+def fd_derivatives(slicer: Slicer, d_phi, npix, spacing, which=tuple(range(FD_COUNT))):
+    """Finite-difference derivatives of the f32 npix^2 device map at address d_phi, samples
+    `spacing` apart: {code: f32 [npix, npix] array} for the FD_* codes in `which`."""
+    which = [int(w) for w in which]
+    if any(not 0 <= w < FD_COUNT for w in which):
+        raise ValueError(f"which: FD_* codes 0..{FD_COUNT - 1}")
+    ptrs = [None] * FD_COUNT
+    try:
+        for w in set(which):
+            ptrs[w] = slicer.malloc(4 * int(npix) * int(npix))
+        fd_run(slicer, d_phi, npix, spacing, ptrs)
+        return {w: slicer.to_host(ptrs[w], (int(npix), int(npix)), np.float32) for w in which}
+    finally:
+        for p in ptrs:
+            if p is not None:
+                slicer.free(p)
 
 
 def ell_fundamental(angle_deg):
