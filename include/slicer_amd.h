@@ -445,6 +445,53 @@ int slicer_power_spectrum(slicer_power_handle ph, int32_t map, double *host);
 int slicer_power_read(slicer_power_handle ph, double *cl, double *ell_mean, int64_t *counts);
 int slicer_power_destroy(slicer_power_handle ph);
 
+/* ---- Central moments of a map over a pyramid of 2x2 halvings ----
+ * Level 0 is the caller's f32 map of npix^2 pixels (row-major); level l+1 has n_{l+1} = n_l / 2 (integer division: for odd
+ * n_l the last row and column do not enter it) and, in f32 and in this order (Lens/halve.py),
+ *   y[i][j] = ((x[2i][2j] + x[2i+1][2j]) + x[2i][2j+1]) + x[2i+1][2j+1],
+ * stored as it is (SLICER_HALVE_SUM, for mass planes) or as 0.25f * y (SLICER_HALVE_MEAN, for kappa); no FMA.
+ * Of every level, over ALL its N = n_l^2 pixels (the row and column that halving drops included), about a centre c (f64):
+ *   d_i = (double)x_i - c,  p_2 = d * d,  p_k = p_{k-1} * d,  S_k = sum_i p_k(i)  for k = 2 ... 8  (Lens/moment.py),
+ * each operation rounded once to f64, summed in f64 in a fixed tree, and the mean mu = (sum_i x_i) / N likewise.  No
+ * atomics: the same input gives bitwise the same numbers.  The raw sums are returned, not S_k / N: the moment of F
+ * realisations is m_k = sum_f S_k(f) / (F N), as moment.py averages them.
+ * Centre of level l: centres[l], or the level's own device mean where centres[l] is NaN or centres is NULL.
+ * Pyramid against one level: of slicer_moments_read's fields, `sums`, `centres_used` and `npix_level` of level l are
+ * always bitwise those of a levels = 0 run on the level-l map with the same centre.  `means` of level l is bitwise that
+ * run's too when the levels = 0 run is given no centre (NULL or NaN): the mean of a map comes from a sum pass of its
+ * own, in the order in which a halving pass writes that map.  When the levels = 0 run is GIVEN its centre, the map is
+ * read once, no such pass runs, and its mean is summed along with the S_k, in their tree: `means` then agrees with the
+ * pyramid's within the mean's bound below, not bitwise.  The same holds for level 0 of any run with centres[0] given.
+ * Tree depth: D(n) = slicer_moments_depth(n) is the number of f64 additions on the longest path of either tree of an
+ * n x n level.  With ceil-divisions, T = (n/2) ceil((n/2)/2) + (n odd ? ceil((2n-1)/8) : 0), U = n ceil(n/2):
+ *   D(n) = max( 8 min(8, ceil(T / 256)) + 18 + ceil(ceil(T / 2048) / 256),
+ *               2 min(8, ceil(U / 256)) + 18 + ceil(ceil(U / 2048) / 256) );         D(16384) = 290.
+ * Bounds, u = 2^-53, A_k = sum_i |x_i - c|^k:  |S_k - exact| <= (2k - 1 + D) u (1 + 2^-20) A_k  (the rounding of d
+ * k-fold, k - 1 products, D additions);  |mu - exact| <= (D + 2) u mean|x_i|.
+ *   slicer_moments_depth     D(npix), host only; -1 for npix outside 1..131072 (message through slicer_last_error(NULL))
+ *   slicer_moments_create    on the device and stream of h (create it after any slicer_set_stream, destroy it before
+ *                            h); allocates the level maps.  The numbers are checked before the handle, so that they
+ *                            can be checked without a device: npix < 1, levels outside 0..floor(log2 npix), a mode that
+ *                            is neither SLICER_HALVE_*: SLICER_ERR_ARG; npix > 131072: SLICER_ERR_UNSUPPORTED
+ *   slicer_moments_run       any device f32 npix^2 map (e.g. slicer_kappa_device_map), which is only read; centres:
+ *                            NULL or levels + 1 doubles in host memory, read before the call returns; enqueued, no
+ *                            synchronisation, no host round trip between the levels
+ *   slicer_moments_read      n_l [levels+1], mu_l [levels+1], the centres used [levels+1], S_k [levels+1][7] of the last
+ *                            run (any of them NULL); waits for the stream.  Before any run: SLICER_ERR_STATE
+ *   slicer_moments_device_map / _read_map   level 1 ... levels of the last run (other levels: SLICER_ERR_ARG; before
+ *                            any run: SLICER_ERR_STATE); _read_map waits for the stream */
+typedef struct slicer_moments *slicer_moments_handle;
+#define SLICER_MOMENTS_ORDERS 7 /* k = 2 ... 8 */
+enum { SLICER_HALVE_MEAN = 0, SLICER_HALVE_SUM = 1 };
+int slicer_moments_depth(int32_t npix);
+int slicer_moments_create(slicer_handle h, int32_t npix, int32_t levels, int32_t mode, slicer_moments_handle *out);
+int slicer_moments_run(slicer_moments_handle mh, const float *d_map, const double *centres);
+int slicer_moments_read(slicer_moments_handle mh, int32_t *npix_level, double *means, double *centres_used,
+                        double *sums);
+int slicer_moments_device_map(slicer_moments_handle mh, int32_t level, float **d_map);
+int slicer_moments_read_map(slicer_moments_handle mh, int32_t level, float *host);
+int slicer_moments_destroy(slicer_moments_handle mh);
+
 /* per-kernel HIP-event timing (off by default; adds two event records per launch) */
 int slicer_profile_enable(slicer_handle h, int on);
 int slicer_profile_reset(slicer_handle h);

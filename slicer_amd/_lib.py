@@ -106,6 +106,13 @@ SYMBOLS = {
     "slicer_power_spectrum": (C.c_int, [_H, C.c_int32, C.c_void_p]),
     "slicer_power_read": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p]),
     "slicer_power_destroy": (C.c_int, [_H]),
+    "slicer_moments_depth": (C.c_int, [C.c_int32]),
+    "slicer_moments_create": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "slicer_moments_run": (C.c_int, [_H, C.c_void_p, C.c_void_p]),
+    "slicer_moments_read": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "slicer_moments_device_map": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_void_p)]),
+    "slicer_moments_read_map": (C.c_int, [_H, C.c_int32, C.c_void_p]),
+    "slicer_moments_destroy": (C.c_int, [_H]),
     "slicer_profile_enable": (C.c_int, [_H, C.c_int]),
     "slicer_profile_reset": (C.c_int, [_H]),
     "slicer_profile_get": (C.c_int, [_H, C.POINTER(KernelTime), C.c_int, C.POINTER(C.c_int)]),

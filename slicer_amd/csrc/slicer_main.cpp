@@ -23,6 +23,9 @@
 //     (or auto and cross) power spectra C_l of the kappa maps, computed on device 0 (Lens/smr.py's PS without its
 //     defects); --power-edges r0,r1,... sets the bin edges in units of l_f = 2 pi / ANGLE
 //     (default 0, 1, ..., npix-1).
+//   * --moments (with --kappa) also writes <directory><simulation>.moments_<npix>_<suffix>.txt: the raw central power
+//     sums S_2 ... S_8 and the mean of every kappa map and of --moments-levels L (default 0) successive 2x2 block means
+//     of it, about each level's own mean, computed on device 0 (Lens/moment.py and Lens/halve.py).
 //   * SubFind / halo-catalogue mode (npix == 0) is not supported; with snopt > 0 and several devices every rank thread
 //     draws from its own copy of the libc stream, like the reference's MPI ranks (Ranks::create).
 #include <dlfcn.h>
@@ -280,6 +283,8 @@ struct Options {
     string shear_derivative;     // "" (not given: fft), "fft" or "gradient"
     string power;                // "", "auto" or "cross"
     vector<double> power_edges;  // empty: the default edges
+    bool moments = false, moments_levels_given = false;
+    int moments_levels = 0;
     int device = 0, mas = SLICER_MAS_TSC, accum = SLICER_ACC_F32;
     bool plan_only = false, single_plane = false, reference_counts = false, replication = false;
 };
@@ -319,6 +324,21 @@ int parse_args(int argc, char **argv, Options &o)
                 o.power_edges.push_back(r);
             }
         }
+        else if (a == "--moments") o.moments = true;
+        else if (a == "--moments-levels") {
+            if (i + 1 >= argc) {
+                cerr << "--moments-levels needs a value (the number of halvings below the kappa map)" << endl;
+                return 2;
+            }
+            char *end = nullptr;
+            const long v = strtol(argv[++i], &end, 10);
+            if (end == argv[i] || *end != '\0' || v < -1000 || v > 1000) {
+                cerr << "bad --moments-levels (the number of halvings below the kappa map)" << endl;
+                return 2;
+            }
+            o.moments_levels = (int)v;
+            o.moments_levels_given = true;
+        }
         else if (o.inifile.empty()) o.inifile = a;
         else {
             cerr << "unknown argument " << a << endl;
@@ -355,6 +375,14 @@ int parse_args(int argc, char **argv, Options &o)
     }
     if (!o.power_edges.empty() && o.power.empty()) {
         cerr << "--power-edges needs --power" << endl;
+        return 2;
+    }
+    if (o.moments && o.kappa_spec.empty()) {
+        cerr << "--moments needs --kappa (the moments are those of the kappa maps)" << endl;
+        return 2;
+    }
+    if (o.moments_levels_given && !o.moments) {
+        cerr << "--moments-levels needs --moments" << endl;
         return 2;
     }
     return 0;
@@ -410,6 +438,16 @@ int plan_cone(const Options &o, Cone &c)
         if (slicer_power_bins(p.npix, ne, o.power_edges.empty() ? nullptr : o.power_edges.data(), cnt.data(),
                               mr.data()) != SLICER_OK) {
             cerr << "--power-edges: " << slicer_last_error(nullptr) << endl;
+            return 2;
+        }
+    }
+    if (o.moments) {  // the pyramid's depth, checked on the host before any device work
+        int most = 0;
+        while (p.npix >> (most + 1) > 0)
+            most++;
+        if (p.npix < 1 || o.moments_levels < 0 || o.moments_levels > most) {
+            cerr << "--moments-levels " << o.moments_levels << " is outside 0 ... " << most << " = floor(log2 npix) for npix = "
+                 << p.npix << endl;
             return 2;
         }
     }
@@ -543,9 +581,8 @@ struct Ranks {
     }
 };
 
-// --kappa / --shear / --power: the kappa maps, and the shear maps and power spectra computed from them, on the root
-// handle.  Declared after the
-// Ranks, so that it is released before its parent handle.
+// --kappa / --shear / --power / --moments: the kappa maps, and the shear maps, power spectra and moments computed from
+// them, on the root handle.  Declared after the Ranks, so that it is released before its parent handle.
 struct LensingOutputs {
     const slicer_handle h;
     const InputParams &p;
@@ -554,6 +591,8 @@ struct LensingOutputs {
     slicer_kappa_handle kh = nullptr;  // nullptr without --kappa
     slicer_shear_handle shh = nullptr;
     slicer_power_handle ph = nullptr;
+    slicer_moments_handle mh = nullptr;
+    int moments_levels = -1;  // -1: no --moments
     bool deflection = false, gradient = false;  // --deflection; --shear-derivative gradient
     string power_mode{};           // "", "auto" or "cross"
     vector<double> power_edges{};  // empty: 0 .. npix-1
@@ -563,6 +602,8 @@ struct LensingOutputs {
     {
         for (float *b : upload)
             slicer_device_free(h, b);
+        if (mh)
+            slicer_moments_destroy(mh);
         if (ph)
             slicer_power_destroy(ph);
         if (shh)
@@ -587,6 +628,9 @@ struct LensingOutputs {
                                     power_edges.empty() ? nullptr : power_edges.data(), &ph) != SLICER_OK)
                 return fail(h, "slicer_amd: --power");
         }
+        if (kh && moments_levels >= 0 &&
+            slicer_moments_create(h, p.npix, moments_levels, SLICER_HALVE_MEAN, &mh) != SLICER_OK)
+            return fail(h, "slicer_amd: --moments");
         return 0;
     }
 
@@ -663,16 +707,27 @@ struct LensingOutputs {
             outs.push_back({"deflection", ".alpha1_z", gradient ? SLICER_SHEAR_FD_ALPHA1 : SLICER_SHEAR_ALPHA1});
             outs.push_back({"deflection", ".alpha2_z", gradient ? SLICER_SHEAR_FD_ALPHA2 : SLICER_SHEAR_ALPHA2});
         }
+        const int nlev = moments_levels + 1;  // (0 without --moments)
+        vector<int32_t> mom_npix(nlev);
+        vector<double> mom_mean(zs.size() * nlev), mom_sums(zs.size() * nlev * SLICER_MOMENTS_ORDERS);
         for (size_t s = 0; s < zs.size(); s++) {
             char zbuf[32];
             snprintf(zbuf, sizeof zbuf, "%.4f", zs[s]);
             const FitsKey keys[2] = {{"ZSOURCE", false, 0, zs[s], " "}, {"ANGLE", false, 0, p.fov, " "}};
             if (slicer_kappa_read(kh, (int)s, map.data()) != SLICER_OK || !save("convergence", ".kappa_z", zbuf, map, keys))
                 return fail(h, "slicer_amd: --kappa");
-            if (!shh)
+            if (!shh && !mh)
                 continue;
             float *d_kappa = nullptr;
-            if (slicer_kappa_device_map(kh, (int)s, &d_kappa) != SLICER_OK || slicer_shear_run(shh, d_kappa) != SLICER_OK)
+            if (slicer_kappa_device_map(kh, (int)s, &d_kappa) != SLICER_OK)
+                return fail(h, "slicer_amd: --kappa");
+            if (mh && (slicer_moments_run(mh, d_kappa, nullptr) != SLICER_OK ||
+                       slicer_moments_read(mh, mom_npix.data(), &mom_mean[s * nlev], nullptr,
+                                           &mom_sums[s * nlev * SLICER_MOMENTS_ORDERS]) != SLICER_OK))
+                return fail(h, "slicer_amd: --moments");
+            if (!shh)
+                continue;
+            if (slicer_shear_run(shh, d_kappa) != SLICER_OK)
                 return fail(h, "slicer_amd: --kappa");
             if ((gradient && slicer_shear_fd(shh) != SLICER_OK) ||
                 (deflection && !gradient && slicer_shear_deflection(shh) != SLICER_OK))
@@ -681,7 +736,39 @@ struct LensingOutputs {
                 if (slicer_shear_read(shh, o.which, map.data()) != SLICER_OK || !save(o.what, o.token, zbuf, map, keys))
                     return fail(h, "slicer_amd: --kappa");
         }
-        return ph ? write_power() : 0;
+        if (const int rc = ph ? write_power() : 0)
+            return rc;
+        return mh ? write_moments(mom_npix, mom_mean, mom_sums) : 0;
+    }
+
+    // The moments of the kappa maps, one text file: '#' lines (npix, angle, levels, column names), then per (source,
+    // level) z level npix mean S2 ... S8 (%.17g): the raw sums about the level's own mean
+    int write_moments(const vector<int32_t> &npix_level, const vector<double> &mean, const vector<double> &sums)
+    {
+        const string path = p.directory + p.simulation + ".moments_" + p.snpix + "_" + p.suffix + ".txt";
+        cout << "Saving the moments on: " << path << endl;
+        FILE *f = fopen(path.c_str(), "w");
+        if (!f) {
+            cerr << "It was not possible to create the file: " << path << endl;
+            return 1;
+        }
+        const int nlev = moments_levels + 1;
+        fprintf(f, "# npix %d\n# angle_deg %.17g\n# levels %d\n# z level npix mean", p.npix, p.fov, moments_levels);
+        for (int k = 2; k < 2 + SLICER_MOMENTS_ORDERS; k++)
+            fprintf(f, " S%d", k);
+        fprintf(f, "\n");
+        for (size_t s = 0; s < zs.size(); s++)
+            for (int l = 0; l < nlev; l++) {
+                fprintf(f, "%.17g %d %d %.17g", zs[s], l, (int)npix_level[l], mean[s * nlev + l]);
+                for (int k = 0; k < SLICER_MOMENTS_ORDERS; k++)
+                    fprintf(f, " %.17g", sums[(s * nlev + l) * SLICER_MOMENTS_ORDERS + k]);
+                fprintf(f, "\n");
+            }
+        if (fclose(f) != 0) {
+            cerr << "It was not possible to write the file: " << path << endl;
+            return 1;
+        }
+        return 0;
     }
 
     // The binned spectra of the kappa maps, one text file: '#' lines (npix, angle, source redshifts, column names),
@@ -889,6 +976,7 @@ int main(int argc, char **argv)
     lensing.gradient = o.shear_derivative == "gradient";
     lensing.power_mode = o.power;
     lensing.power_edges = o.power_edges;
+    lensing.moments_levels = o.moments ? o.moments_levels : -1;
     if (const int rc = lensing.create(o.shear))
         return rc;
     const int rc = run_planes(o, c, ranks, lensing);

@@ -1,12 +1,14 @@
 """Born-approximation convergence (kappa) maps from the lens planes, and the shear and lensing
-potential maps from them (row N6), the binned auto and cross power spectra of such maps (row N7), and the deflection
-maps and finite-difference derivatives of the potential (row N8).
+potential maps from them (row N6), the binned auto and cross power spectra of such maps (row N7), the deflection
+maps and finite-difference derivatives of the potential (row N8), and the central moments of such maps over a pyramid
+of 2x2 halvings (row N9).
 
 plane_weights wraps the host weights of include/slicer_amd.h (slicer_lensing_weights); Kappa is the device accumulator
 (slicer_kappa_*) bound to a Slicer handle: it reads the finalized plane maps where they are, in HBM.  Shear (slicer_shear_*)
 turns one kappa map into phi, gamma1, gamma2 and |gamma| on the same device, and on request into the deflection maps
 (Shear.deflection) and the finite-difference alpha, kappa and shear of phi (Shear.fd; fd_derivatives for any device
-map); Power (slicer_power_*) bins the spectra of several of them into C_l.
+map); Power (slicer_power_*) bins the spectra of several of them into C_l; Moments (slicer_moments_*) halves a map
+level by level and sums the powers 2 ... 8 of every level's pixels about a centre.
 """
 import ctypes as C
 import math
@@ -317,3 +319,100 @@ class Power:
             cl = flat
         return {"ell_lo": self.edges[:-1] * self.ell_f, "ell_hi": self.edges[1:] * self.ell_f, "ell": ell,
                 "counts": counts, "cl": cl}
+
+
+HALVE_MEAN, HALVE_SUM = 0, 1
+MOMENTS_ORDERS = 7  # k = 2 ... 8
+
+
+def moments_depth(npix):
+    """D(npix): the f64 additions on the longest path of the summation trees of an npix^2 level (the D of the bounds
+    in include/slicer_amd.h); host only, no device needed."""
+    d = _L.slicer_moments_depth(int(npix))
+    if d < 0:
+        raise SlicerError(2, (_L.slicer_last_error(None) or b"").decode())
+    return d
+
+
+class Moments:
+    """Central moments of orders 2 ... 8 of an npix^2 map and of `levels` successive 2x2 halvings of it, on the device
+    of `slicer`, on its stream.  mode "mean" halves to block means (kappa), "sum" to block sums
+    (mass planes, Lens/halve.py)."""
+
+    def __init__(self, slicer: Slicer, npix, levels=0, mode="mean"):
+        if mode not in ("mean", "sum"):
+            raise ValueError('mode: "mean" or "sum"')
+        self._s = slicer
+        self.npix, self.levels, self.mode = int(npix), int(levels), mode
+        mh = C.c_void_p()
+        slicer._chk(_L.slicer_moments_create(slicer._h, self.npix, self.levels, HALVE_SUM if mode == "sum" else HALVE_MEAN,
+                                             C.byref(mh)))
+        self._mh = mh
+
+    def close(self):
+        if getattr(self, "_mh", None):
+            _L.slicer_moments_destroy(self._mh)
+            self._mh = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def run(self, d_map, centres=None):
+        """d_map: device address of an f32 npix^2 map; centres: None (every level's own mean) or levels + 1 values,
+        NaN where a level is to take its own mean."""
+        c = None
+        if centres is not None:
+            c = np.ascontiguousarray(centres, np.float64).ravel()
+            if c.size != self.levels + 1:
+                raise ValueError(f"expected {self.levels + 1} centres, got {c.size}")
+        self._s._chk(_L.slicer_moments_run(self._mh, int(d_map), _dptr(c)))
+
+    def run_kappa(self, kappa: Kappa, s, centres=None):
+        """The map of source s of a Kappa accumulator, where it is."""
+        self.run(kappa.device_map(s), centres)
+
+    def read(self):
+        """dict: npix [levels+1], mean, centre (the ones used), sums [levels+1, 7] = S_2 ... S_8, moments = sums / npix^2."""
+        n = self.levels + 1
+        npix = np.empty(n, np.int32)
+        mean, centre = np.empty(n, np.float64), np.empty(n, np.float64)
+        sums = np.empty((n, MOMENTS_ORDERS), np.float64)
+        self._s._chk(_L.slicer_moments_read(self._mh, npix.ctypes.data, mean.ctypes.data, centre.ctypes.data,
+                                            sums.ctypes.data))
+        return {"npix": npix, "mean": mean, "centre": centre, "sums": sums,
+                "moments": sums / (npix.astype(np.float64) ** 2)[:, None]}
+
+    def device_map(self, level):
+        p = C.c_void_p()
+        self._s._chk(_L.slicer_moments_device_map(self._mh, int(level), C.byref(p)))
+        return p.value
+
+    def read_map(self, level):
+        n = self.npix >> int(level) if 0 <= int(level) <= self.levels else 1
+        out = np.empty((n, n), np.float32)
+        self._s._chk(_L.slicer_moments_read_map(self._mh, int(level), out.ctypes.data))
+        return out
+
+
+def combine_moments(reads):
+    """m_k of several realisations as Lens/moment.py averages them: sum_f S_k(f) / (F N), [levels+1, 7], from the
+    Moments.read() of every realisation (all run about the same centres)."""
+    reads = list(reads)
+    if not reads:
+        raise ValueError("no reads to combine")
+    npix = reads[0]["npix"]
+    total = np.zeros_like(reads[0]["sums"])
+    for r in reads:
+        if not np.array_equal(r["npix"], npix):
+            raise ValueError("the reads are of different pyramids")
+        total = total + r["sums"]
+    return total / len(reads) / (npix.astype(np.float64) ** 2)[:, None]
