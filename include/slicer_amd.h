@@ -492,6 +492,47 @@ int slicer_moments_device_map(slicer_moments_handle mh, int32_t level, float **d
 int slicer_moments_read_map(slicer_moments_handle mh, int32_t level, float *host);
 int slicer_moments_destroy(slicer_moments_handle mh);
 
+/* ---- One-point PDF histogram and peak / minimum counts of a map ----
+ * The input is any device f32 map of npix^2 pixels (row-major), 1 <= npix <= 131072, which is only read.  The edges
+ * e_0 < e_1 < ... < e_B are f64, finite and strictly ascending, 1 <= B <= SLICER_PEAKS_MAX_BINS.
+ * PDF: every pixel x is widened exactly to f64 and compared in f64 against the f64 edges (the edges are never rounded
+ * to f32).  x is in bin b iff e_b <= x < e_{b+1}; the last bin is closed, x = e_B is in bin B-1 (numpy.histogram's
+ * rule).  x < e_0 or -inf counts as `below`, x > e_B or +inf as `above`, NaN as `nan`; the four kinds sum to npix^2.
+ * Peaks and minima: a candidate is a pixel (i, j) with 1 <= i, j <= npix-2 (the map is a field of view and does not
+ * wrap: border pixels are never candidates, and for npix < 3 there are none).  It is a peak iff it is strictly greater
+ * than each of its 8 neighbours, a minimum iff strictly less than each, compared in f32.  Ties give neither (a plateau
+ * has no peaks); every comparison with a NaN is false, so a NaN pixel and each of its neighbours is neither.  Peaks and
+ * minima are each histogrammed by the pixel's own value over the same edges by the same rule, with `below` and `above`
+ * counts of their own.
+ * All counts are int64 and exact; the same input gives the same numbers on every run; there is no floating-point
+ * accumulation anywhere.  `below` and `above` are indexed 0 = pdf, 1 = peaks, 2 = minima.
+ *   slicer_peaks_edges      host only: e_0 = lo, e_B = hi, e_b = lo + b * ((hi - lo) / B) for 0 < b < B, each operation
+ *                           rounded once to f64, no FMA.  SLICER_ERR_ARG (message through slicer_last_error(NULL)):
+ *                           bins outside 1..1024, lo or hi not finite, a NULL array, edges that are not finite and
+ *                           strictly ascending after rounding
+ *   slicer_peaks_create     on the device and stream of h (create it after any slicer_set_stream, destroy it before h).
+ *                           The numbers are checked before the handle, so that they can be checked without a device:
+ *                           npix < 1, fewer than 2 or more than 1025 edges, an edge that is not finite, edges not
+ *                           strictly ascending: SLICER_ERR_ARG; npix > 131072: SLICER_ERR_UNSUPPORTED.  Device memory:
+ *                           the edges, 8 (3 B + 7) bytes of results and at most max(64, 8 per compute unit) rows of
+ *                           4 (3 B + 7) bytes (SLICER_ERR_NOMEM)
+ *   slicer_peaks_run        any device f32 map of the handle's npix^2 pixels (e.g. slicer_kappa_device_map); enqueued, no
+ *                           synchronisation.  A NULL map: SLICER_ERR_ARG
+ *   slicer_peaks_run_npix   the same of a smaller map of npix^2 pixels, 1 <= npix <= the handle's (others:
+ *                           SLICER_ERR_ARG), so that one handle serves every level of a moments pyramid
+ *                           (slicer_moments_device_map)
+ *   slicer_peaks_read       pdf, peaks, minima [B] each, below [3], above [3], the NaN count, of the last run (any of
+ *                           them NULL); waits for the stream.  Before any run: SLICER_ERR_STATE */
+typedef struct slicer_peaks *slicer_peaks_handle;
+#define SLICER_PEAKS_MAX_BINS 1024
+int slicer_peaks_edges(double lo, double hi, int32_t bins, double *edges);
+int slicer_peaks_create(slicer_handle h, int32_t npix, int32_t n_edges, const double *edges, slicer_peaks_handle *out);
+int slicer_peaks_run(slicer_peaks_handle ph, const float *d_map);
+int slicer_peaks_run_npix(slicer_peaks_handle ph, const float *d_map, int32_t npix);
+int slicer_peaks_read(slicer_peaks_handle ph, int64_t *pdf, int64_t *peaks, int64_t *minima, int64_t *below,
+                      int64_t *above, int64_t *n_nan);
+int slicer_peaks_destroy(slicer_peaks_handle ph);
+
 /* per-kernel HIP-event timing (off by default; adds two event records per launch) */
 int slicer_profile_enable(slicer_handle h, int on);
 int slicer_profile_reset(slicer_handle h);

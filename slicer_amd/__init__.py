@@ -12,5 +12,6 @@ from .lensing import (FD_ALPHA1, FD_ALPHA2, FD_COUNT, FD_GAMMA, FD_GAMMA1, FD_GA
                       SHEAR_FD_GAMMA2, SHEAR_FD_KAPPA, SHEAR_GAMMA, SHEAR_GAMMA1, SHEAR_GAMMA2, SHEAR_PHI, Kappa, Power,
                       Shear, ell_fundamental, fd_derivatives, fd_run, plane_weights, power_bins, shear_supported)
 from .lensing import HALVE_MEAN, HALVE_SUM, MOMENTS_ORDERS, Moments, combine_moments, moments_depth  # noqa: F401
+from .lensing import PEAKS_MAX_BINS, Peaks, peaks_edges  # noqa: F401
 
 __version__ = "0.2.0"

@@ -113,6 +113,12 @@ SYMBOLS = {
     "slicer_moments_device_map": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_void_p)]),
     "slicer_moments_read_map": (C.c_int, [_H, C.c_int32, C.c_void_p]),
     "slicer_moments_destroy": (C.c_int, [_H]),
+    "slicer_peaks_edges": (C.c_int, [C.c_double, C.c_double, C.c_int32, C.c_void_p]),
+    "slicer_peaks_create": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "slicer_peaks_run": (C.c_int, [_H, C.c_void_p]),
+    "slicer_peaks_run_npix": (C.c_int, [_H, C.c_void_p, C.c_int32]),
+    "slicer_peaks_read": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "slicer_peaks_destroy": (C.c_int, [_H]),
     "slicer_profile_enable": (C.c_int, [_H, C.c_int]),
     "slicer_profile_reset": (C.c_int, [_H]),
     "slicer_profile_get": (C.c_int, [_H, C.POINTER(KernelTime), C.c_int, C.POINTER(C.c_int)]),

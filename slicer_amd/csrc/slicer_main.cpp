@@ -26,6 +26,10 @@
 //   * --moments (with --kappa) also writes <directory><simulation>.moments_<npix>_<suffix>.txt: the raw central power
 //     sums S_2 ... S_8 and the mean of every kappa map and of --moments-levels L (default 0) successive 2x2 block means
 //     of it, about each level's own mean, computed on device 0 (Lens/moment.py and Lens/halve.py).
+//   * --peaks lo,hi,bins (with --kappa) also writes <directory><simulation>.peaks_<npix>_<suffix>.txt: the one-point PDF
+//     histogram of every kappa map and the counts of its peaks and minima by height (strictly above / below all 8
+//     neighbours; the map does not wrap), over `bins` (1 ... 1024) uniform bins from lo to hi, computed on device 0;
+//     with --moments also of every level of its pyramid of block means.
 //   * SubFind / halo-catalogue mode (npix == 0) is not supported; with snopt > 0 and several devices every rank thread
 //     draws from its own copy of the libc stream, like the reference's MPI ranks (Ranks::create).
 #include <dlfcn.h>
@@ -285,6 +289,7 @@ struct Options {
     vector<double> power_edges;  // empty: the default edges
     bool moments = false, moments_levels_given = false;
     int moments_levels = 0;
+    vector<double> peaks_edges;  // empty: no --peaks
     int device = 0, mas = SLICER_MAS_TSC, accum = SLICER_ACC_F32;
     bool plan_only = false, single_plane = false, reference_counts = false, replication = false;
 };
@@ -339,6 +344,24 @@ int parse_args(int argc, char **argv, Options &o)
             o.moments_levels = (int)v;
             o.moments_levels_given = true;
         }
+        else if (a == "--peaks") {
+            const vector<string> tok = i + 1 < argc ? split(argv[++i]) : vector<string>{};
+            char *e0 = nullptr, *e1 = nullptr, *e2 = nullptr;
+            const double lo = tok.size() == 3 ? strtod(tok[0].c_str(), &e0) : 0.0;
+            const double hi = tok.size() == 3 ? strtod(tok[1].c_str(), &e1) : 0.0;
+            const long bins = tok.size() == 3 ? strtol(tok[2].c_str(), &e2, 10) : 0;
+            if (tok.size() != 3 || tok[0].empty() || tok[1].empty() || tok[2].empty() || *e0 != '\0' || *e1 != '\0' ||
+                *e2 != '\0' || bins < 1 || bins > SLICER_PEAKS_MAX_BINS) {
+                cerr << "bad --peaks (lo,hi,bins: the first and the last edge and the number of bins, 1 ... "
+                     << SLICER_PEAKS_MAX_BINS << ")" << endl;
+                return 2;
+            }
+            o.peaks_edges.resize(bins + 1);
+            if (slicer_peaks_edges(lo, hi, (int32_t)bins, o.peaks_edges.data()) != SLICER_OK) {
+                cerr << "bad --peaks: " << slicer_last_error(nullptr) << endl;
+                return 2;
+            }
+        }
         else if (o.inifile.empty()) o.inifile = a;
         else {
             cerr << "unknown argument " << a << endl;
@@ -383,6 +406,10 @@ int parse_args(int argc, char **argv, Options &o)
     }
     if (o.moments_levels_given && !o.moments) {
         cerr << "--moments-levels needs --moments" << endl;
+        return 2;
+    }
+    if (!o.peaks_edges.empty() && o.kappa_spec.empty()) {
+        cerr << "--peaks needs --kappa (the histograms and peak counts are those of the kappa maps)" << endl;
         return 2;
     }
     return 0;
@@ -581,8 +608,8 @@ struct Ranks {
     }
 };
 
-// --kappa / --shear / --power / --moments: the kappa maps, and the shear maps, power spectra and moments computed from
-// them, on the root handle.  Declared after the Ranks, so that it is released before its parent handle.
+// --kappa / --shear / --power / --moments / --peaks: the kappa maps, and the shear maps, power spectra, moments and
+// histograms computed from them, on the root handle.  Declared after the Ranks, so that it is released before its parent handle.
 struct LensingOutputs {
     const slicer_handle h;
     const InputParams &p;
@@ -593,6 +620,8 @@ struct LensingOutputs {
     slicer_power_handle ph = nullptr;
     slicer_moments_handle mh = nullptr;
     int moments_levels = -1;  // -1: no --moments
+    slicer_peaks_handle pkh = nullptr;
+    vector<double> peaks_edges{};  // empty: no --peaks
     bool deflection = false, gradient = false;  // --deflection; --shear-derivative gradient
     string power_mode{};           // "", "auto" or "cross"
     vector<double> power_edges{};  // empty: 0 .. npix-1
@@ -602,6 +631,8 @@ struct LensingOutputs {
     {
         for (float *b : upload)
             slicer_device_free(h, b);
+        if (pkh)
+            slicer_peaks_destroy(pkh);
         if (mh)
             slicer_moments_destroy(mh);
         if (ph)
@@ -631,6 +662,9 @@ struct LensingOutputs {
         if (kh && moments_levels >= 0 &&
             slicer_moments_create(h, p.npix, moments_levels, SLICER_HALVE_MEAN, &mh) != SLICER_OK)
             return fail(h, "slicer_amd: --moments");
+        if (kh && !peaks_edges.empty() &&
+            slicer_peaks_create(h, p.npix, (int)peaks_edges.size(), peaks_edges.data(), &pkh) != SLICER_OK)
+            return fail(h, "slicer_amd: --peaks");
         return 0;
     }
 
@@ -710,13 +744,16 @@ struct LensingOutputs {
         const int nlev = moments_levels + 1;  // (0 without --moments)
         vector<int32_t> mom_npix(nlev);
         vector<double> mom_mean(zs.size() * nlev), mom_sums(zs.size() * nlev * SLICER_MOMENTS_ORDERS);
+        const int pk_lev = pkh ? std::max(nlev, 1) : 0;  // levels 0 ... L of the pyramid, level 0 alone without --moments
+        const size_t pk_row = pkh ? 3 * (peaks_edges.size() - 1) + 7 : 0;
+        vector<int64_t> pk_counts(zs.size() * pk_lev * pk_row);
         for (size_t s = 0; s < zs.size(); s++) {
             char zbuf[32];
             snprintf(zbuf, sizeof zbuf, "%.4f", zs[s]);
             const FitsKey keys[2] = {{"ZSOURCE", false, 0, zs[s], " "}, {"ANGLE", false, 0, p.fov, " "}};
             if (slicer_kappa_read(kh, (int)s, map.data()) != SLICER_OK || !save("convergence", ".kappa_z", zbuf, map, keys))
                 return fail(h, "slicer_amd: --kappa");
-            if (!shh && !mh)
+            if (!shh && !mh && !pkh)
                 continue;
             float *d_kappa = nullptr;
             if (slicer_kappa_device_map(kh, (int)s, &d_kappa) != SLICER_OK)
@@ -725,6 +762,16 @@ struct LensingOutputs {
                        slicer_moments_read(mh, mom_npix.data(), &mom_mean[s * nlev], nullptr,
                                            &mom_sums[s * nlev * SLICER_MOMENTS_ORDERS]) != SLICER_OK))
                 return fail(h, "slicer_amd: --moments");
+            for (int l = 0; l < pk_lev; l++) {  // (after the moments: the pyramid's maps are those of this source)
+                float *d_level = d_kappa;
+                if (l > 0 && slicer_moments_device_map(mh, l, &d_level) != SLICER_OK)
+                    return fail(h, "slicer_amd: --peaks");
+                const size_t B = peaks_edges.size() - 1;
+                int64_t *c = &pk_counts[(s * pk_lev + l) * pk_row];  // pdf, peaks, minima [B]; below, above [3]; nan
+                if (slicer_peaks_run_npix(pkh, d_level, p.npix >> l) != SLICER_OK ||
+                    slicer_peaks_read(pkh, c, c + B, c + 2 * B, c + 3 * B, c + 3 * B + 3, c + 3 * B + 6) != SLICER_OK)
+                    return fail(h, "slicer_amd: --peaks");
+            }
             if (!shh)
                 continue;
             if (slicer_shear_run(shh, d_kappa) != SLICER_OK)
@@ -738,7 +785,48 @@ struct LensingOutputs {
         }
         if (const int rc = ph ? write_power() : 0)
             return rc;
-        return mh ? write_moments(mom_npix, mom_mean, mom_sums) : 0;
+        if (const int rc = mh ? write_moments(mom_npix, mom_mean, mom_sums) : 0)
+            return rc;
+        return pkh ? write_peaks(pk_lev, pk_counts) : 0;
+    }
+
+    // The histograms of the kappa maps, one text file: '#' lines (npix, angle, levels, the edges, column names), then per
+    // (source, level) one row per bin: -1 (below the first edge), 0 ... B-1, B (above the last), B+1 (NaN pixels)
+    int write_peaks(int nlev, const vector<int64_t> &counts)
+    {
+        const string path = p.directory + p.simulation + ".peaks_" + p.snpix + "_" + p.suffix + ".txt";
+        cout << "Saving the histograms and peak counts on: " << path << endl;
+        FILE *f = fopen(path.c_str(), "w");
+        if (!f) {
+            cerr << "It was not possible to create the file: " << path << endl;
+            return 1;
+        }
+        const int B = (int)peaks_edges.size() - 1;
+        const size_t row = 3 * (size_t)B + 7;
+        fprintf(f, "# npix %d\n# angle_deg %.17g\n# levels %d\n# edges", p.npix, p.fov, nlev - 1);
+        for (double e : peaks_edges)
+            fprintf(f, " %.17g", e);
+        fprintf(f, "\n# z level npix bin lo hi n_pixels n_peaks n_minima\n");
+        for (size_t s = 0; s < zs.size(); s++)
+            for (int l = 0; l < nlev; l++) {
+                const int64_t *c = &counts[(s * nlev + l) * row];
+                const int64_t *below = c + 3 * B, *above = below + 3;
+                char head[96];
+                snprintf(head, sizeof head, "%.17g %d %d", zs[s], l, p.npix >> l);
+                fprintf(f, "%s -1 -inf %.17g %lld %lld %lld\n", head, peaks_edges[0], (long long)below[0],
+                        (long long)below[1], (long long)below[2]);
+                for (int b = 0; b < B; b++)
+                    fprintf(f, "%s %d %.17g %.17g %lld %lld %lld\n", head, b, peaks_edges[b], peaks_edges[b + 1],
+                            (long long)c[b], (long long)c[B + b], (long long)c[2 * B + b]);
+                fprintf(f, "%s %d %.17g inf %lld %lld %lld\n", head, B, peaks_edges[B], (long long)above[0],
+                        (long long)above[1], (long long)above[2]);
+                fprintf(f, "%s %d nan nan %lld 0 0\n", head, B + 1, (long long)c[3 * B + 6]);
+            }
+        if (fclose(f) != 0) {
+            cerr << "It was not possible to write the file: " << path << endl;
+            return 1;
+        }
+        return 0;
     }
 
     // The moments of the kappa maps, one text file: '#' lines (npix, angle, levels, column names), then per (source,
@@ -977,6 +1065,7 @@ int main(int argc, char **argv)
     lensing.power_mode = o.power;
     lensing.power_edges = o.power_edges;
     lensing.moments_levels = o.moments ? o.moments_levels : -1;
+    lensing.peaks_edges = o.peaks_edges;
     if (const int rc = lensing.create(o.shear))
         return rc;
     const int rc = run_planes(o, c, ranks, lensing);

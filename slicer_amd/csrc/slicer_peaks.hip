@@ -1,0 +1,395 @@
+// slicer_peaks.hip -- on-device one-point PDF histogram and peak / minimum counts of a map.
+//
+// Of an n x n f32 map x (row-major, only read) and f64 edges e_0 < ... < e_B:
+//   pdf[b]     pixels with e_b <= (double)x < e_{b+1}, the last bin closed (x = e_B is in bin B-1): numpy.histogram's rule;
+//              below: x < e_0 or -inf; above: x > e_B or +inf; nan: NaN.  The comparisons are in f64 against the f64 edges.
+//   peaks[b]   pixels 1 <= i, j <= n-2 strictly greater (in f32) than each of their 8 neighbours, binned by their own
+//   minima[b]  value by the same rule; ... strictly less.  The map does not wrap: border pixels are never candidates.
+//              A comparison with a NaN is false, so a NaN and its neighbours are neither; ties give neither.
+// Every count is an integer: nothing here is a floating-point sum, so the results are exact and the same on every run.
+//
+// k_peaks: a workgroup of 256 threads takes tiles of kT0 x kT1 = 16 x 64 pixels (the tile of slicer_fd.hip), stages a
+// tile with a halo of one pixel in LDS as f32 and every thread takes four adjacent pixels of one row.  The window is
+// 18 rows of pitch 72 with the tile's first column at window column 4 (not 18 x 66): the sixteen float4s of a window row
+// then sit on LDS's 16-byte grid, so staging stores and a thread's three row reads are 128-bit accesses; the halo
+// columns are window columns 3 and 68.  Loads: a float4 per four pixels when 4 | n and the map is on the 16-byte grid
+// (k_peaks<true>), scalar loads otherwise (k_peaks<false>); the window, and so the counts, are the same.
+// The grid is fixed: G = min(tiles, max(kMinGroups, w * CUs)) workgroups, w = min(8, what a CU's LDS holds at once),
+// workgroup b takes tiles b, b + G, ..., so a workgroup zeroes and flushes its counters once a launch.  The edges sit
+// in LDS as f64 (at most 8200 B); the bin is the number of e_0 ... e_{B-1} that are <= x, minus one, by a branch-free
+// binary search of ceil(log2 B) + 1 LDS reads -- the rule itself, no guess to correct; e_B only decides `above`, which
+// closes the last bin.  A thread searches its four pixels side by side, so the reads of one step do not wait for one
+// another.  The counters are three u32 histograms of B bins and the 7 outside counts in LDS
+// (at most 12316 B), incremented with LDS integer atomics; peaks and minima reuse the pixel's bin.
+// u32 is enough: a workgroup counts at most ceil(tiles / G) * 1024 pixels, and tiles <= (131072 / 16) * (131072 / 64)
+// = 2^24 with G >= min(tiles, 64) gives at most 2^18 * 2^10 = 2^28 < 2^32.
+// Flush: workgroup b stores its counters as row b of partial[G][3 B + 7]; k_peaks_finish sums the rows of every column
+// into int64.  Every row and every result is stored by every launch: nothing is zeroed between runs, nothing carried
+// over, no global atomics.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <new>
+#include <vector>
+
+#include "slicer_host.hpp"
+
+namespace {
+
+constexpr int kT0 = 16, kT1 = 64;  // tile: rows x columns
+constexpr int kPer = 4;            // adjacent pixels of a thread
+constexpr int kThreads = kT0 * kT1 / kPer;
+constexpr int kRows = kT0 + 2;
+constexpr int kLeft = 4;                  // window column of the tile's first pixel
+constexpr int kPitch = kLeft + kT1 + 4;   // 72 floats: every window row starts on the 16-byte grid
+constexpr int kQuads = kT1 / kPer;        // float4s of a tile row = threads of a tile row
+constexpr int kMaxNpix = 131072;
+constexpr int kMaxBins = SLICER_PEAKS_MAX_BINS;
+constexpr int kOutside = 7;               // below[3], above[3], nan
+constexpr int kPerCu = 8, kMinGroups = 64;     // workgroups per CU at most; fewer where their LDS does not fit
+constexpr size_t kLdsPerCu = 160 * 1024;       // gfx950
+constexpr int kFinCols = 16, kFinRows = 16;  // k_peaks_finish: columns of a workgroup x threads of a column
+
+static_assert(kThreads == 256 && kFinCols * kFinRows == kThreads, "one thread per four pixels of a tile");
+static_assert(((int64_t)kMaxNpix / kT0) * (kMaxNpix / kT1) / kMinGroups * (kT0 * kT1) < (int64_t)1 << 32,
+              "a workgroup's u32 counters hold every pixel it can meet");
+
+struct PeakArgs {
+    const float *x;
+    const double *edges;  // [B + 1]
+    unsigned *partial;    // [gridDim.x][3 B + 7]
+    int n, B;
+    int tiles_x, ntiles;
+};
+
+template <bool VEC>
+__global__ __launch_bounds__(kThreads) void k_peaks(PeakArgs a)
+{
+    __shared__ __attribute__((aligned(16))) float win[kRows * kPitch];
+    extern __shared__ double dyn[];
+    const int n = a.n, B = a.B, nE = B + 1, nC = 3 * B + kOutside, tid = threadIdx.x;
+    double *edge = dyn;
+    unsigned *cnt = reinterpret_cast<unsigned *>(dyn + nE);
+    for (int k = tid; k < nE; k += kThreads)
+        edge[k] = a.edges[k];
+    for (int k = tid; k < nC; k += kThreads)
+        cnt[k] = 0u;
+    const double eB = a.edges[B];
+    const int lr = tid / kQuads, lc = tid % kQuads * kPer;
+    for (int t = blockIdx.x; t < a.ntiles; t += gridDim.x) {
+        const int r0 = t / a.tiles_x * kT0, c0 = t % a.tiles_x * kT1;
+        __syncthreads();  // the previous tile's window has been read (first tile: edges and counters are in place)
+        if (VEC) {        // 4 | n and c0 % 4 == 0: a float4 lies in the map whole or not at all
+            for (int q = tid; q < kRows * kQuads; q += kThreads) {
+                const int wr = q / kQuads, wq = q % kQuads;
+                const int r = r0 - 1 + wr, c = c0 + kPer * wq;
+                float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                if (r >= 0 && r < n && c < n)
+                    v = *reinterpret_cast<const float4 *>(a.x + (size_t)r * n + c);
+                *reinterpret_cast<float4 *>(win + wr * kPitch + kLeft + kPer * wq) = v;
+            }
+            if (tid < 2 * kRows) {  // the two halo columns
+                const int wr = tid / 2, right = tid % 2;
+                const int r = r0 - 1 + wr, c = right ? c0 + kT1 : c0 - 1;
+                win[wr * kPitch + (right ? kLeft + kT1 : kLeft - 1)] =
+                    r >= 0 && r < n && c >= 0 && c < n ? a.x[(size_t)r * n + c] : 0.0f;
+            }
+        } else {
+            for (int q = tid; q < kRows * (kT1 + 2); q += kThreads) {
+                const int wr = q / (kT1 + 2), wc = q % (kT1 + 2);
+                const int r = r0 - 1 + wr, c = c0 - 1 + wc;
+                win[wr * kPitch + kLeft - 1 + wc] = r >= 0 && r < n && c >= 0 && c < n ? a.x[(size_t)r * n + c] : 0.0f;
+            }
+        }
+        __syncthreads();
+        const int i = r0 + lr, j0 = c0 + lc;
+        if (i >= n || j0 >= n)
+            continue;
+        // rows i-1, i, i+1, columns j0-1 ... j0+4 of the map
+        const float *w = win + (lr + 1) * kPitch + kLeft + lc;
+        float nb[3][kPer + 2];
+#pragma unroll
+        for (int d = 0; d < 3; d++) {
+            const float *row = w + (d - 1) * kPitch;
+            const float4 m = *reinterpret_cast<const float4 *>(row);
+            nb[d][0] = row[-1];
+            nb[d][1] = m.x, nb[d][2] = m.y, nb[d][3] = m.z, nb[d][4] = m.w;
+            nb[d][5] = row[kPer];
+        }
+        // pos[q]: how many of e_0 ... e_{B-1} are <= pixel q.  Invariant of the search: every edge before `pos` is
+        // <= x and the answer lies in pos ... pos + len.  The steps depend on B alone, so the wave never diverges, and
+        // the four pixels' reads of a step are independent of one another.  (Pixels past the map's edge are zeros of
+        // the window: searched, never counted.)
+        double xd[kPer];
+        int pos[kPer];
+#pragma unroll
+        for (int q = 0; q < kPer; q++) {
+            xd[q] = (double)nb[1][q + 1];
+            pos[q] = 0;
+        }
+        for (int len = B; len > 1;) {
+            const int half = len / 2;
+#pragma unroll
+            for (int q = 0; q < kPer; q++)
+                pos[q] = edge[pos[q] + half - 1] <= xd[q] ? pos[q] + half : pos[q];
+            len -= half;
+        }
+#pragma unroll
+        for (int q = 0; q < kPer; q++)
+            pos[q] += edge[pos[q]] <= xd[q] ? 1 : 0;
+        const bool row_inside = i >= 1 && i <= n - 2;
+#pragma unroll
+        for (int q = 0; q < kPer; q++) {
+            const int j = j0 + q;
+            if (j >= n)
+                break;
+            const float x = nb[1][q + 1];
+            // the pdf's counter of this pixel, and the distance from it to the peaks' one (the minima's: twice that)
+            int slot, stride = 1;
+            if (x != x) {
+                atomicAdd(&cnt[3 * B + 6], 1u);
+                continue;  // every comparison with it is false: neither a peak nor a minimum
+            } else if (pos[q] == 0) {
+                slot = 3 * B;  // below e_0
+            } else if (xd[q] > eB) {
+                slot = 3 * B + 3;  // above e_B
+            } else {
+                slot = pos[q] - 1;  // e_{B-1} <= x <= e_B gives pos = B: the last bin is closed
+                stride = B;
+            }
+            atomicAdd(&cnt[slot], 1u);
+            if (!row_inside || j < 1 || j > n - 2)
+                continue;
+            const float c00 = nb[0][q], c01 = nb[0][q + 1], c02 = nb[0][q + 2], c10 = nb[1][q], c12 = nb[1][q + 2];
+            const float c20 = nb[2][q], c21 = nb[2][q + 1], c22 = nb[2][q + 2];
+            const bool peak = x > c00 && x > c01 && x > c02 && x > c10 && x > c12 && x > c20 && x > c21 && x > c22;
+            const bool minimum = x < c00 && x < c01 && x < c02 && x < c10 && x < c12 && x < c20 && x < c21 && x < c22;
+            if (peak)
+                atomicAdd(&cnt[slot + stride], 1u);
+            if (minimum)
+                atomicAdd(&cnt[slot + 2 * stride], 1u);
+        }
+    }
+    __syncthreads();
+    unsigned *out = a.partial + (size_t)blockIdx.x * nC;
+    for (int k = tid; k < nC; k += kThreads)
+        out[k] = cnt[k];
+}
+
+// Workgroup v sums columns 16 v ... 16 v + 15 of partial[G][nC]: sixteen threads a column, thread rg of them the rows
+// rg, rg + 16, ...; integer sums, so the order does not matter.
+__global__ __launch_bounds__(kThreads) void k_peaks_finish(const unsigned *partial, int G, int nC, int64_t *res)
+{
+    __shared__ int64_t red[kFinRows][kFinCols];
+    const int cl = threadIdx.x % kFinCols, rg = threadIdx.x / kFinCols, col = (int)blockIdx.x * kFinCols + cl;
+    int64_t acc = 0;
+    if (col < nC) {
+#pragma unroll 8
+        for (int g = rg; g < G; g += kFinRows)
+            acc += (int64_t)partial[(size_t)g * nC + col];
+    }
+    red[rg][cl] = acc;
+    __syncthreads();
+    if (rg != 0 || col >= nC)
+        return;
+    for (int k = 1; k < kFinRows; k++)
+        acc += red[k][cl];
+    res[col] = acc;
+}
+
+size_t peaks_dyn_lds(int B) { return (size_t)(B + 1) * sizeof(double) + (3 * (size_t)B + kOutside) * sizeof(unsigned); }
+
+int64_t tiles_of(int n) { return (int64_t)((n + kT0 - 1) / kT0) * ((n + kT1 - 1) / kT1); }
+
+// 0, or the message of what is wrong with the edges
+const char *edges_fault(int32_t n_edges, const double *edges)
+{
+    for (int k = 0; k < n_edges; k++)
+        if (!std::isfinite(edges[k]))
+            return "edges must be finite";
+    for (int k = 1; k < n_edges; k++)
+        if (!(edges[k - 1] < edges[k]))
+            return "edges must be strictly ascending";
+    return nullptr;
+}
+
+}  // namespace
+
+struct slicer_peaks {
+    slicer_handle h = nullptr;
+    int device = 0;
+    int n = 0, B = 0;
+    int gmax = 0;  // rows of `partial`
+    std::vector<double> edges;
+    double *d_edges = nullptr;
+    unsigned *partial = nullptr;
+    int64_t *res = nullptr;
+    bool ran = false;
+    DevAllocs mem;
+};
+
+extern "C" {
+
+int slicer_peaks_edges(double lo, double hi, int32_t bins, double *edges)
+{
+    if (bins < 1 || bins > kMaxBins)
+        return fail(nullptr, SLICER_ERR_ARG, "slicer_peaks_edges: bins = %d outside 1..%d", bins, kMaxBins);
+    if (!edges)
+        return fail(nullptr, SLICER_ERR_ARG, "slicer_peaks_edges: null argument");
+    if (!std::isfinite(lo) || !std::isfinite(hi))
+        return fail(nullptr, SLICER_ERR_ARG, "slicer_peaks_edges: lo and hi must be finite");
+    const double width = (hi - lo) / (double)bins;
+    edges[0] = lo;
+    for (int b = 1; b < bins; b++)
+        edges[b] = lo + (double)b * width;  // (-ffp-contract=off: the product and the sum are rounded apart)
+    edges[bins] = hi;
+    if (edges_fault(bins + 1, edges))
+        return fail(nullptr, SLICER_ERR_ARG,
+                    "slicer_peaks_edges: the edges of lo = %.17g, hi = %.17g, bins = %d are not finite and strictly ascending",
+                    lo, hi, bins);
+    return SLICER_OK;
+}
+
+int slicer_peaks_create(slicer_handle h, int32_t npix, int32_t n_edges, const double *edges, slicer_peaks_handle *out)
+{
+    // the numbers first: they need no handle, so a caller can have them checked before any device exists
+    if (out)
+        *out = nullptr;
+    if (npix < 1)
+        return fail(h, SLICER_ERR_ARG, "slicer_peaks_create: npix must be positive");
+    if (npix > kMaxNpix)
+        return fail(h, SLICER_ERR_UNSUPPORTED, "slicer_peaks_create: npix = %d above %d", npix, kMaxNpix);
+    if (n_edges < 2)
+        return fail(h, SLICER_ERR_ARG, "slicer_peaks_create: fewer than 2 edges");
+    if (n_edges > kMaxBins + 1)
+        return fail(h, SLICER_ERR_ARG, "slicer_peaks_create: %d edges, at most %d", n_edges, kMaxBins + 1);
+    if (!edges)
+        return fail(h, SLICER_ERR_ARG, "slicer_peaks_create: null argument");
+    if (const char *what = edges_fault(n_edges, edges))
+        return fail(h, SLICER_ERR_ARG, "slicer_peaks_create: %s", what);
+    if (!h || !out)
+        return fail(h, SLICER_ERR_ARG, "slicer_peaks_create: null argument");
+    const char *who = "slicer_peaks_create";
+    hipStream_t st = nullptr;
+    int dev = 0;
+    if (int rc = sub_open(h, who, &st, &dev))
+        return rc;
+    slicer_peaks_handle ph = new (std::nothrow) slicer_peaks;
+    if (!ph)
+        return fail(h, SLICER_ERR_NOMEM, "out of host memory");
+    ph->h = h;
+    ph->device = dev;
+    ph->n = npix;
+    ph->B = n_edges - 1;
+    // as many workgroups as are resident at once: by LDS (the window, the edges, the counters), kPerCu at most
+    const size_t lds = kRows * kPitch * sizeof(float) + peaks_dyn_lds(ph->B);
+    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(kPerCu, kLdsPerCu / lds));
+    ph->gmax = (int)std::min<int64_t>(tiles_of(npix), std::max(kMinGroups, per_cu * h->num_cus));
+    ph->edges.assign(edges, edges + n_edges);
+    const size_t nC = 3 * (size_t)ph->B + kOutside;
+    int rc = SLICER_OK;
+    rc = ph->mem.alloc(rc, h, who, (void **)&ph->d_edges, (size_t)n_edges * sizeof(double));
+    rc = ph->mem.alloc(rc, h, who, (void **)&ph->partial, (size_t)ph->gmax * nC * sizeof(unsigned));
+    rc = ph->mem.alloc(rc, h, who, (void **)&ph->res, nC * sizeof(int64_t));
+    if (rc == SLICER_OK) {
+        // (ph->edges outlives the copy)
+        hipError_t e = hipMemcpyAsync(ph->d_edges, ph->edges.data(), (size_t)n_edges * sizeof(double), hipMemcpyHostToDevice, st);
+        if (e != hipSuccess)
+            rc = fail(h, SLICER_ERR_HIP, "%s: copying the edges: %s", who, hipGetErrorString(e));
+    }
+    if (rc != SLICER_OK) {
+        delete ph;
+        return rc;
+    }
+    *out = ph;
+    return SLICER_OK;
+}
+
+int slicer_peaks_run_npix(slicer_peaks_handle ph, const float *d_map, int32_t npix)
+{
+    if (!ph || !d_map)
+        return fail(ph ? ph->h : nullptr, SLICER_ERR_ARG, "slicer_peaks_run_npix: null argument");
+    if (npix < 1 || npix > ph->n)
+        return fail(ph->h, SLICER_ERR_ARG, "slicer_peaks_run_npix: npix = %d outside 1..%d", npix, ph->n);
+    hipStream_t st;
+    if (int rc = sub_stream(ph->h, ph->device, &st))
+        return rc;
+    ph->ran = false;
+    const int nC = 3 * ph->B + kOutside;
+    PeakArgs a{};
+    a.x = d_map;
+    a.edges = ph->d_edges;
+    a.partial = ph->partial;
+    a.n = npix;
+    a.B = ph->B;
+    a.tiles_x = (npix + kT1 - 1) / kT1;
+    a.ntiles = (int)tiles_of(npix);
+    const int G = std::min(a.ntiles, ph->gmax);
+    const size_t lds = peaks_dyn_lds(ph->B);
+    {
+        ProfScope ps(ph->h, KN_PEAKS);
+        if (npix % 4 == 0 && (uintptr_t)d_map % 16 == 0)
+            hipLaunchKernelGGL(k_peaks<true>, dim3((unsigned)G), dim3(kThreads), lds, st, a);
+        else
+            hipLaunchKernelGGL(k_peaks<false>, dim3((unsigned)G), dim3(kThreads), lds, st, a);
+        HIPCHK(ph->h, hipGetLastError());
+    }
+    {
+        ProfScope ps(ph->h, KN_PEAKS_FINISH);
+        hipLaunchKernelGGL(k_peaks_finish, dim3((unsigned)((nC + kFinCols - 1) / kFinCols)), dim3(kThreads), 0, st,
+                           ph->partial, G, nC, ph->res);
+        HIPCHK(ph->h, hipGetLastError());
+    }
+    ph->ran = true;
+    return SLICER_OK;
+}
+
+int slicer_peaks_run(slicer_peaks_handle ph, const float *d_map)
+{
+    if (!ph || !d_map)
+        return fail(ph ? ph->h : nullptr, SLICER_ERR_ARG, "slicer_peaks_run: null argument");
+    return slicer_peaks_run_npix(ph, d_map, ph->n);
+}
+
+int slicer_peaks_read(slicer_peaks_handle ph, int64_t *pdf, int64_t *peaks, int64_t *minima, int64_t *below,
+                      int64_t *above, int64_t *n_nan)
+{
+    if (!ph)
+        return fail(nullptr, SLICER_ERR_ARG, "slicer_peaks_read: null handle");
+    if (!ph->ran)
+        return fail(ph->h, SLICER_ERR_STATE, "slicer_peaks_read before any slicer_peaks_run");
+    hipStream_t st;
+    if (int rc = sub_stream(ph->h, ph->device, &st))
+        return rc;
+    const size_t B = (size_t)ph->B;
+    std::vector<int64_t> r(3 * B + kOutside);
+    HIPCHK(ph->h, hipMemcpyAsync(r.data(), ph->res, r.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(ph->h, hipStreamSynchronize(st));
+    if (pdf)
+        std::copy_n(&r[0], B, pdf);
+    if (peaks)
+        std::copy_n(&r[B], B, peaks);
+    if (minima)
+        std::copy_n(&r[2 * B], B, minima);
+    if (below)
+        std::copy_n(&r[3 * B], 3, below);
+    if (above)
+        std::copy_n(&r[3 * B + 3], 3, above);
+    if (n_nan)
+        *n_nan = r[3 * B + 6];
+    return SLICER_OK;
+}
+
+int slicer_peaks_destroy(slicer_peaks_handle ph)
+{
+    if (!ph)
+        return SLICER_ERR_ARG;
+    (void)hipSetDevice(ph->device);
+    (void)hipStreamSynchronize(ph->h->stream);
+    delete ph;
+    return SLICER_OK;
+}
+
+}  // extern "C"

@@ -1,14 +1,15 @@
 """Born-approximation convergence (kappa) maps from the lens planes, and the shear and lensing
 potential maps from them (row N6), the binned auto and cross power spectra of such maps (row N7), the deflection
 maps and finite-difference derivatives of the potential (row N8), and the central moments of such maps over a pyramid
-of 2x2 halvings (row N9).
+of 2x2 halvings (row N9), and the one-point PDF histogram and peak / minimum counts of such maps (row N10).
 
 plane_weights wraps the host weights of include/slicer_amd.h (slicer_lensing_weights); Kappa is the device accumulator
 (slicer_kappa_*) bound to a Slicer handle: it reads the finalized plane maps where they are, in HBM.  Shear (slicer_shear_*)
 turns one kappa map into phi, gamma1, gamma2 and |gamma| on the same device, and on request into the deflection maps
 (Shear.deflection) and the finite-difference alpha, kappa and shear of phi (Shear.fd; fd_derivatives for any device
 map); Power (slicer_power_*) bins the spectra of several of them into C_l; Moments (slicer_moments_*) halves a map
-level by level and sums the powers 2 ... 8 of every level's pixels about a centre.
+level by level and sums the powers 2 ... 8 of every level's pixels about a centre; Peaks (slicer_peaks_*) counts a
+map's pixels, peaks and minima by height over a list of edges.
 """
 import ctypes as C
 import math
@@ -416,3 +417,74 @@ def combine_moments(reads):
             raise ValueError("the reads are of different pyramids")
         total = total + r["sums"]
     return total / len(reads) / (npix.astype(np.float64) ** 2)[:, None]
+
+
+PEAKS_MAX_BINS = 1024
+
+
+def peaks_edges(lo, hi, bins):
+    """bins + 1 uniform f64 edges as slicer_peaks_edges rounds them: e_0 = lo, e_B = hi, e_b = lo + b * ((hi - lo) / B)
+    between; host only, no device needed."""
+    bins = int(bins)
+    e = np.zeros(max(bins, 0) + 1, np.float64)
+    rc = _L.slicer_peaks_edges(float(lo), float(hi), bins, e.ctypes.data)
+    if rc:
+        raise SlicerError(rc, (_L.slicer_last_error(None) or b"").decode())
+    return e
+
+
+class Peaks:
+    """One-point PDF histogram and the counts of peaks and minima by height of an npix^2 map over the f64 `edges`, on
+    the device of `slicer`, on its stream.  Every count is an exact int64."""
+
+    def __init__(self, slicer: Slicer, npix, edges):
+        self._s = slicer
+        self.npix = int(npix)
+        self.edges = np.array(edges, np.float64).ravel()
+        self.n_bins = self.edges.size - 1
+        ph = C.c_void_p()
+        slicer._chk(_L.slicer_peaks_create(slicer._h, self.npix, self.edges.size, _dptr(self.edges), C.byref(ph)))
+        self._ph = ph
+
+    def close(self):
+        if getattr(self, "_ph", None):
+            _L.slicer_peaks_destroy(self._ph)
+            self._ph = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def run(self, d_map, npix=None):
+        """d_map: device address of an f32 map of npix^2 pixels (None: the handle's npix; otherwise at most that)."""
+        d = None if d_map is None else int(d_map)
+        if npix is None:
+            self._s._chk(_L.slicer_peaks_run(self._ph, d))
+        else:
+            self._s._chk(_L.slicer_peaks_run_npix(self._ph, d, int(npix)))
+
+    def run_kappa(self, kappa: Kappa, s):
+        """The map of source s of a Kappa accumulator, where it is."""
+        self.run(kappa.device_map(s), kappa.npix)
+
+    def run_level(self, moments: Moments, level):
+        """Level `level` >= 1 of the last run of a Moments pyramid, where it is (level 0 is the caller's own map)."""
+        self.run(moments.device_map(level), moments.npix >> int(level))
+
+    def read(self):
+        """dict: edges [B+1], pdf, peaks, minima (int64 [B]), below, above (int64 [3]: pdf, peaks, minima), nan."""
+        B = self.n_bins
+        pdf, peaks, minima = (np.empty(B, np.int64) for _ in range(3))
+        below, above, nan = np.empty(3, np.int64), np.empty(3, np.int64), np.empty(1, np.int64)
+        self._s._chk(_L.slicer_peaks_read(self._ph, pdf.ctypes.data, peaks.ctypes.data, minima.ctypes.data,
+                                          below.ctypes.data, above.ctypes.data, nan.ctypes.data))
+        return {"edges": self.edges.copy(), "pdf": pdf, "peaks": peaks, "minima": minima, "below": below, "above": above,
+                "nan": int(nan[0])}
