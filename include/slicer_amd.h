@@ -533,6 +533,71 @@ int slicer_peaks_read(slicer_peaks_handle ph, int64_t *pdf, int64_t *peaks, int6
                       int64_t *above, int64_t *n_nan);
 int slicer_peaks_destroy(slicer_peaks_handle ph);
 
+/* ---- Multi-plane ray tracing through the lens planes ----
+ * One ray per pixel of an npix^2 grid (axis 0 slow = component 1, axis 1 contiguous = component 2, as for N6 and N8), on the
+ * device and stream of h (create it after any slicer_set_stream, destroy it before h).  State per ray, 12 f64: position
+ * b = (b1, b2) and direction t = (t1, t2) in pixel units, centred (b = beta / d, d = the spacing in radians per pixel,
+ * h = (npix - 1) / 2), and the 2 x 2 matrices A = d beta / d theta and T = d t / d theta.  Start: the ray of pixel (i, j)
+ * has b = t = (i - h, j - h), A = T = I; the last plane distance is chi = 0.  Every operation below is one IEEE f64
+ * operation rounded once (RN), in this order, with no FMA: a host restatement reproduces the device bit for bit.
+ * Step to the plane at comoving distance chi_k > chi_{k-1}, described by five f32 maps of npix^2 (alpha1, alpha2 in radians,
+ * kappa, gamma1, gamma2: the maps of N6 / N8 of that plane's lens map), with w = RN(RN(chi_k - chi_{k-1}) / chi_k):
+ *   1. b_a <- RN(b_a + RN(w RN(t_a - b_a)));  A_ab <- RN(A_ab + RN(w RN(T_ab - A_ab)))
+ *   2. u_a = RN(b_a + h), i_a = floor(u_a), f_a = RN(u_a - i_a), g_a = RN(1 - f_a).  The cell's corners are i_a mod npix and
+ *      (i_a + 1) mod npix, the mathematical modulo: the grid wraps.  A ray with a u that is not finite or has |u| >= 2^30 in
+ *      either component reads pixel (0, 0) with f1 = f2 = NaN: its state becomes NaN and stays NaN; no other ray is affected.
+ *   3. per map, with the four samples m00 at (i1, i2), m01 at (i1, i2+1), m10 at (i1+1, i2), m11 at (i1+1, i2+1) widened to
+ *      f64:  r0 = RN(RN(g2 m00) + RN(f2 m01)),  r1 = RN(RN(g2 m10) + RN(f2 m11)),  v = RN(RN(g1 r0) + RN(f1 r1))
+ *   4. U11 = RN(v_kappa + v_gamma1), U22 = RN(v_kappa - v_gamma1), U12 = U21 = v_gamma2
+ *   5. t_a <- RN(t_a - RN(v_alpha_a / d))
+ *   6. T_ab <- RN(T_ab - RN(RN(U_a1 A_1b) + RN(U_a2 A_2b)))   with the A of step 1
+ * Observe at chi_s >= chi of the last plane, w_s = RN(RN(chi_s - chi) / chi_s): bs and As are step 1 with w_s (the state is
+ * not changed); six f32 maps, each formed in f64 and rounded once to f32:
+ *   kappa = 1 - RN(0.5 RN(As11 + As22)),  gamma1 = 0.5 RN(As22 - As11),  gamma2 = -0.5 RN(As12 + As21),
+ *   omega = 0.5 RN(As21 - As12),  deflection_a = RN(RN(theta_a - bs_a) d) in radians,  theta = (i - h, j - h),
+ * the convention A = [[1 - kappa - gamma1, -gamma2 - omega], [-gamma2 + omega, 1 - kappa + gamma1]].  The sign and
+ * payload of a NaN result are not part of the contract.
+ *   slicer_rays_create    allocates the twelve state arrays, 96 bytes per ray (SLICER_ERR_NOMEM); launches nothing.  The
+ *                         numbers are checked before the handle, so that they can be checked without a device: npix < 1, a
+ *                         spacing that is not positive and finite: SLICER_ERR_ARG; npix > 131072: SLICER_ERR_UNSUPPORTED
+ *   slicer_rays_reset     back to the start state; nothing launched
+ *   slicer_rays_step      one kernel; enqueued, no synchronisation; the maps are only read.  SLICER_ERR_ARG: chi not finite
+ *                         or not above the last plane's, a NULL map
+ *   slicer_rays_observe   one kernel; enqueued, no synchronisation.  d_out[SLICER_RAYS_*]: device buffers of npix^2 floats
+ *                         owned by the caller, NULL entries are skipped.  Allowed before any step (zeros).  SLICER_ERR_ARG:
+ *                         chi_s not positive and finite or below the last plane's, every output NULL
+ *   slicer_rays_state     the state, [12][npix^2] in the order b1 b2 t1 t2 A11 A12 A21 A22 T11 T12 T21 T22; waits for the
+ *                         stream.  Before any step: the start state
+ *   slicer_rays_planes    the number of steps since create / reset and the last plane's chi (either may be NULL) */
+typedef struct slicer_rays *slicer_rays_handle;
+#define SLICER_RAYS_KAPPA 0
+#define SLICER_RAYS_GAMMA1 1
+#define SLICER_RAYS_GAMMA2 2
+#define SLICER_RAYS_OMEGA 3
+#define SLICER_RAYS_DEFLECTION1 4
+#define SLICER_RAYS_DEFLECTION2 5
+#define SLICER_RAYS_COUNT 6
+int slicer_rays_create(slicer_handle h, int32_t npix, double spacing, slicer_rays_handle *out);
+int slicer_rays_reset(slicer_rays_handle rh);
+int slicer_rays_step(slicer_rays_handle rh, double chi, const float *d_alpha1, const float *d_alpha2,
+                     const float *d_kappa, const float *d_gamma1, const float *d_gamma2);
+int slicer_rays_observe(slicer_rays_handle rh, double chi_s, float *const d_out[SLICER_RAYS_COUNT]);
+int slicer_rays_state(slicer_rays_handle rh, double *host);
+int slicer_rays_planes(slicer_rays_handle rh, int32_t *n_steps, double *chi_last);
+int slicer_rays_destroy(slicer_rays_handle rh);
+/* Zero the accumulators and forget the means: the handle as just created.  Enqueued, no synchronisation. */
+int slicer_kappa_reset(slicer_kappa_handle kh);
+/* Per-plane lensing strengths for the ray tracer, host only; the arguments, the background and the refusals of
+ * slicer_lensing_weights.  strength[p] = 4 pi / (c^2/G) * g_p * (1 + zl_p) * chi(zl_p) / a_p: the lens map of plane p
+ * is L_p = strength[p] (m_p - mean m_p), and Born's c_sp = strength[p] (chi_s - chi_p) / chi_s up to rounding.
+ * chil[p] = chi(zl_p); chis[s] = chi(zs[s]); n_in_front[s] = the number of planes with z(ld2[p]) <= zs[s] + 1e-4 (the rule of
+ * slicer_lensing_weights).  zs = NULL: the far-edge redshifts z(ld2[p]) (n_sources must equal n_planes).  chil, chis and
+ * n_in_front may be NULL. */
+int slicer_lensing_plane_strengths(double omega_m, double omega_lambda, double w0, double wa, double fov_deg, int32_t npix,
+                                   int32_t growth, int32_t physical, int32_t n_planes, const double *ld,
+                                   const double *ld2, const double *zsnap, int32_t n_sources, const double *zs,
+                                   double *strength, double *chil, double *chis, int32_t *n_in_front);
+
 /* per-kernel HIP-event timing (off by default; adds two event records per launch) */
 int slicer_profile_enable(slicer_handle h, int on);
 int slicer_profile_reset(slicer_handle h);

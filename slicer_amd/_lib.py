@@ -119,6 +119,17 @@ SYMBOLS = {
     "slicer_peaks_run_npix": (C.c_int, [_H, C.c_void_p, C.c_int32]),
     "slicer_peaks_read": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "slicer_peaks_destroy": (C.c_int, [_H]),
+    "slicer_rays_create": (C.c_int, [_H, C.c_int32, C.c_double, C.POINTER(C.c_void_p)]),
+    "slicer_rays_reset": (C.c_int, [_H]),
+    "slicer_rays_step": (C.c_int, [_H, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "slicer_rays_observe": (C.c_int, [_H, C.c_double, C.POINTER(C.c_void_p)]),
+    "slicer_rays_state": (C.c_int, [_H, C.c_void_p]),
+    "slicer_rays_planes": (C.c_int, [_H, C.POINTER(C.c_int32), C.POINTER(C.c_double)]),
+    "slicer_rays_destroy": (C.c_int, [_H]),
+    "slicer_kappa_reset": (C.c_int, [_H]),
+    "slicer_lensing_plane_strengths": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32,
+                                                 C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "slicer_profile_enable": (C.c_int, [_H, C.c_int]),
     "slicer_profile_reset": (C.c_int, [_H]),
     "slicer_profile_get": (C.c_int, [_H, C.POINTER(KernelTime), C.c_int, C.POINTER(C.c_int)]),

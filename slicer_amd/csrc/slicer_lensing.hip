@@ -318,6 +318,22 @@ int slicer_kappa_add(slicer_kappa_handle kh, int32_t n_maps, const float *const 
     return SLICER_OK;
 }
 
+int slicer_kappa_reset(slicer_kappa_handle kh)
+{
+    if (!kh)
+        return fail(nullptr, SLICER_ERR_ARG, "null kappa handle");
+    hipStream_t st;
+    if (int rc = sub_stream(kh->h, kh->device, &st))
+        return rc;
+    // what slicer_kappa_create clears, and no more than is ever read before it is written: the accumulators and the offsets
+    for (int s = 0; s < kh->n_sources; s++)
+        HIPCHK(kh->h, hipMemsetAsync(kh->acc[s], 0, kh->n * sizeof(double), st));
+    HIPCHK(kh->h, hipMemsetAsync(kh->off, 0, kh->n_sources * sizeof(double), st));
+    kh->n_added = 0;
+    kh->finalized = false;
+    return SLICER_OK;
+}
+
 int slicer_kappa_plane_means(slicer_kappa_handle kh, double *out, int32_t max)
 {
     if (!kh || (!out && max > 0))

@@ -147,12 +147,10 @@ int refuse(int code, const char *fmt, double a = 0, double b = 0)
     return fail(nullptr, code, "%s", buf);
 }
 
-}  // namespace
-
-int slicer_lensing_weights(double omega_m, double omega_lambda, double w0, double wa, double fov_deg, int32_t npix,
-                           int32_t growth, int32_t physical, int32_t n_planes, const double *ld, const double *ld2,
-                           const double *zsnap, int32_t n_sources, const double *zs, double *coeff, double *zlo,
-                           double *zup, double *zl, double *chil)
+// what slicer_lensing_weights and slicer_lensing_plane_strengths refuse alike; 0 if the arguments pass
+int check_planes(const char *who, double omega_m, double omega_lambda, double fov_deg, int32_t npix, int32_t physical,
+                 int32_t n_planes, const double *ld, const double *ld2, const double *zsnap, int32_t n_sources,
+                 const double *zs, const void *out)
 {
     if (physical)
         return refuse(SLICER_ERR_UNSUPPORTED, "kappa maps: a physical pixel size (one map size per plane) is not supported");
@@ -160,27 +158,56 @@ int slicer_lensing_weights(double omega_m, double omega_lambda, double w0, doubl
         return refuse(SLICER_ERR_UNSUPPORTED, "kappa maps need a flat background (Omega_m = %g, Omega_Lambda = %g)", omega_m,
                       omega_lambda);
     if (!(omega_m > 0) || !(fov_deg > 0 && fov_deg < 180) || npix <= 0 || n_planes <= 0 || !ld || !ld2 || !zsnap ||
-        !coeff || n_sources <= 0 || (!zs && n_sources != n_planes))
-        return refuse(SLICER_ERR_ARG, "slicer_lensing_weights: bad argument");
+        !out || n_sources <= 0 || (!zs && n_sources != n_planes))
+        return fail(nullptr, SLICER_ERR_ARG, "%s: bad argument", who);
     for (int p = 0; p < n_planes; p++)
-        if (!(ld[p] >= 0 && ld2[p] > ld[p]) || !(zsnap[p] >= 0))
-            return refuse(SLICER_ERR_ARG, "slicer_lensing_weights: plane edges %g, %g out of order", ld[p], ld2[p]);
+        if (!(ld[p] >= 0 && ld2[p] > ld[p]) || !(zsnap[p] >= 0)) {
+            char buf[256];
+            snprintf(buf, sizeof buf, "%s: plane edges %g, %g out of order", who, ld[p], ld2[p]);
+            return fail(nullptr, SLICER_ERR_ARG, "%s", buf);
+        }
+    return SLICER_OK;
+}
+
+// per plane: the edge redshifts, the effective lens redshift and its distance, the pixel area and the growth correction
+struct PlaneGeometry {
+    std::vector<double> lo, up, zl, chil, area, g;
+    PlaneGeometry(const Background &bg, double fov_deg, int32_t npix, int32_t growth, int32_t n_planes, const double *ld,
+                  const double *ld2, const double *zsnap)
+        : lo(n_planes), up(n_planes), zl(n_planes), chil(n_planes), area(n_planes), g(n_planes)
+    {
+        const double side = 2.0 * tan(fov_deg * M_PI / 360.0) / npix;  // pixel side per unit distance
+        for (int p = 0; p < n_planes; p++) {
+            lo[p] = bg.z_of_chi(ld[p]);
+            up[p] = bg.z_of_chi(ld2[p]);
+            const double width = (up[p] - lo[p]) / 4;  // at least four panels per plane
+            const double num = kGL.integrate([&](double z) { return z * bg.chi(z); }, lo[p], up[p], width);
+            const double den = kGL.integrate([&](double z) { return bg.chi(z); }, lo[p], up[p], width);
+            zl[p] = num / den;
+            chil[p] = bg.chi(zl[p]);
+            area[p] = (side * chil[p]) * (side * chil[p]);
+            g[p] = growth ? bg.growth(zl[p]) / bg.growth(zsnap[p]) : 1.0;
+        }
+    }
+};
+
+}  // namespace
+
+int slicer_lensing_weights(double omega_m, double omega_lambda, double w0, double wa, double fov_deg, int32_t npix,
+                           int32_t growth, int32_t physical, int32_t n_planes, const double *ld, const double *ld2,
+                           const double *zsnap, int32_t n_sources, const double *zs, double *coeff, double *zlo,
+                           double *zup, double *zl, double *chil)
+{
+    if (int rc = check_planes("slicer_lensing_weights", omega_m, omega_lambda, fov_deg, npix, physical, n_planes, ld, ld2,
+                              zsnap, n_sources, zs, coeff))
+        return rc;
     const Background bg{Cosmology{omega_m, omega_lambda, w0, wa}};
     const double four_pi_g_over_c2 = 4.0 * M_PI / c2_over_g();
-    const double side = 2.0 * tan(fov_deg * M_PI / 360.0) / npix;  // pixel side per unit distance
-    std::vector<double> vlo(n_planes), vup(n_planes), vzl(n_planes), vchil(n_planes), base(n_planes);
-    for (int p = 0; p < n_planes; p++) {
-        vlo[p] = bg.z_of_chi(ld[p]);
-        vup[p] = bg.z_of_chi(ld2[p]);
-        const double width = (vup[p] - vlo[p]) / 4;  // at least four panels per plane
-        const double num = kGL.integrate([&](double z) { return z * bg.chi(z); }, vlo[p], vup[p], width);
-        const double den = kGL.integrate([&](double z) { return bg.chi(z); }, vlo[p], vup[p], width);
-        vzl[p] = num / den;
-        vchil[p] = bg.chi(vzl[p]);
-        const double area = (side * vchil[p]) * (side * vchil[p]);
-        const double g = growth ? bg.growth(vzl[p]) / bg.growth(zsnap[p]) : 1.0;
-        base[p] = four_pi_g_over_c2 * g * (1.0 + vzl[p]) * (1.0 + vzl[p]) / area;
-    }
+    const PlaneGeometry pg(bg, fov_deg, npix, growth, n_planes, ld, ld2, zsnap);
+    const std::vector<double> &vlo = pg.lo, &vup = pg.up, &vzl = pg.zl, &vchil = pg.chil;
+    std::vector<double> base(n_planes);
+    for (int p = 0; p < n_planes; p++)
+        base[p] = four_pi_g_over_c2 * pg.g[p] * (1.0 + vzl[p]) * (1.0 + vzl[p]) / pg.area[p];
     for (int s = 0; s < n_sources; s++) {
         const double z_s = zs ? zs[s] : vup[s];
         const double chi_s = bg.chi(z_s);
@@ -202,6 +229,35 @@ int slicer_lensing_weights(double omega_m, double omega_lambda, double w0, doubl
             zl[p] = vzl[p];
         if (chil)
             chil[p] = vchil[p];
+    }
+    return SLICER_OK;
+}
+
+int slicer_lensing_plane_strengths(double omega_m, double omega_lambda, double w0, double wa, double fov_deg, int32_t npix,
+                                   int32_t growth, int32_t physical, int32_t n_planes, const double *ld,
+                                   const double *ld2, const double *zsnap, int32_t n_sources, const double *zs,
+                                   double *strength, double *chil, double *chis, int32_t *n_in_front)
+{
+    if (int rc = check_planes("slicer_lensing_plane_strengths", omega_m, omega_lambda, fov_deg, npix, physical, n_planes, ld,
+                              ld2, zsnap, n_sources, zs, strength))
+        return rc;
+    const Background bg{Cosmology{omega_m, omega_lambda, w0, wa}};
+    const double four_pi_g_over_c2 = 4.0 * M_PI / c2_over_g();
+    const PlaneGeometry pg(bg, fov_deg, npix, growth, n_planes, ld, ld2, zsnap);
+    for (int p = 0; p < n_planes; p++) {
+        strength[p] = four_pi_g_over_c2 * pg.g[p] * (1.0 + pg.zl[p]) * pg.chil[p] / pg.area[p];
+        if (chil)
+            chil[p] = pg.chil[p];
+    }
+    for (int s = 0; s < n_sources; s++) {
+        const double z_s = zs ? zs[s] : pg.up[s];
+        if (chis)
+            chis[s] = bg.chi(z_s);
+        if (!n_in_front)
+            continue;
+        n_in_front[s] = 0;
+        for (int p = 0; p < n_planes; p++)
+            n_in_front[s] += pg.up[p] <= z_s + 1e-4 ? 1 : 0;
     }
     return SLICER_OK;
 }

@@ -19,6 +19,12 @@
 //     header); --shear-derivative fft|gradient (with --shear, default fft) chooses where gamma1, gamma2, |gamma| and
 //     the alphas come from: the FFT filters, or smr's derivative="gradient", finite differences of phi that do not
 //     wrap the map's edges.  The phi and kappa files are the same either way.
+//   * --raytrace (with --kappa) also shoots one ray per pixel through the planes, near to far, on device 0 (DESIGN.md S8
+//     row N11): every plane's lens map strength_p (m_p - mean m_p) is turned into its deflection, convergence and shear maps
+//     (the device work of --shear --deflection, per plane; --shear-derivative gradient takes the finite-difference maps)
+//     and the rays step through them at chi(zl_p).  Per source, next to the kappa file and with its header:
+//     .rt_kappa_z, .rt_gamma1_z, .rt_gamma2_z, .rt_omega_z (the distortion matrix) and .rt_alpha1_z, .rt_alpha2_z (the
+//     total deflection, radians).  All other files are unchanged.
 //   * --power auto|cross (with --kappa) also writes <directory><simulation>.cl_<npix>_<suffix>.txt: the binned auto
 //     (or auto and cross) power spectra C_l of the kappa maps, computed on device 0 (Lens/smr.py's PS without its
 //     defects); --power-edges r0,r1,... sets the bin edges in units of l_f = 2 pi / ANGLE
@@ -283,7 +289,7 @@ int host_plane_reduce(vector<Rank> &ranks, int npix, int n_planes)
 
 struct Options {
     string inifile, plan_path, devices_spec, reduce_mode = "rccl", reduce_algo = "rooted", kappa_spec;
-    bool kappa_growth = true, shear = false, deflection = false;
+    bool kappa_growth = true, shear = false, deflection = false, raytrace = false;
     string shear_derivative;     // "" (not given: fft), "fft" or "gradient"
     string power;                // "", "auto" or "cross"
     vector<double> power_edges;  // empty: the default edges
@@ -316,6 +322,7 @@ int parse_args(int argc, char **argv, Options &o)
         else if (a == "--kappa-no-growth") o.kappa_growth = false;
         else if (a == "--shear") o.shear = true;
         else if (a == "--deflection") o.deflection = true;
+        else if (a == "--raytrace") o.raytrace = true;
         else if (a == "--shear-derivative" && i + 1 < argc) o.shear_derivative = argv[++i];  // fft | gradient
         else if (a == "--power" && i + 1 < argc) o.power = argv[++i];  // auto | cross
         else if (a == "--power-edges" && i + 1 < argc) {
@@ -376,6 +383,10 @@ int parse_args(int argc, char **argv, Options &o)
         cerr << "--shear needs --kappa (the shear maps are computed from the kappa maps)" << endl;
         return 2;
     }
+    if (o.raytrace && o.kappa_spec.empty()) {
+        cerr << "--raytrace needs --kappa (the rays are observed at the source redshifts of the kappa maps)" << endl;
+        return 2;
+    }
     if (o.deflection && !o.shear) {
         cerr << "--deflection needs --shear (the deflection maps are computed from the spectrum of the shear maps)" << endl;
         return 2;
@@ -384,7 +395,7 @@ int parse_args(int argc, char **argv, Options &o)
         cerr << "bad --shear-derivative (fft or gradient)" << endl;
         return 2;
     }
-    if (!o.shear_derivative.empty() && !o.shear) {
+    if (!o.shear_derivative.empty() && !o.shear && !o.raytrace) {
         cerr << "--shear-derivative needs --shear" << endl;
         return 2;
     }
@@ -448,6 +459,10 @@ int plan_cone(const Options &o, Cone &c)
         return 1;
     if (o.shear && !slicer_shear_supported(p.npix)) {
         cerr << "--shear: npix = " << p.npix << " is not supported (2 ... 16384, prime factors 2, 3, 5, 7 only)" << endl;
+        return 2;
+    }
+    if (o.raytrace && !p.physical && !slicer_shear_supported(p.npix)) {  // (physical: refused with the weights)
+        cerr << "--raytrace: npix = " << p.npix << " is not supported (2 ... 16384, prime factors 2, 3, 5, 7 only)" << endl;
         return 2;
     }
     if (o.shear_derivative == "gradient" && p.npix < 5) {
@@ -550,6 +565,35 @@ int kappa_weights(const Options &o, const Cone &c, vector<double> &zs, vector<do
     return 0;
 }
 
+// --raytrace: the strength and distance of every plane, the distance of every source and the number of planes in front of
+// it (slicer_lensing_plane_strengths), before any GPU work.  0, or the exit status
+struct RayPlan {
+    vector<double> strength, chil, chis;
+    vector<int32_t> in_front;
+};
+int raytrace_plan(const Options &o, const Cone &c, const vector<double> &zs, RayPlan &rp)
+{
+    if (!o.raytrace)
+        return 0;
+    const int P = c.lens.nplanes, S = (int)zs.size();
+    rp.strength.resize(P);
+    rp.chil.resize(P);
+    rp.chis.resize(S);
+    rp.in_front.resize(S);
+    if (slicer_lensing_plane_strengths(c.simdata.om0, c.simdata.oml, c.p.w, 0.0, c.p.fov, c.p.npix, o.kappa_growth,
+                                       c.p.physical, P, c.lens.ld.data(), c.lens.ld2.data(), c.lens.zfromsnap.data(), S,
+                                       zs.data(), rp.strength.data(), rp.chil.data(), rp.chis.data(),
+                                       rp.in_front.data()) != SLICER_OK)
+        return fail(nullptr, "slicer_amd: --raytrace");
+    for (int i = 1; i < P; i++)
+        if (!(rp.chil[i] > rp.chil[i - 1])) {
+            cerr << "--raytrace: the plane distances are not strictly ascending (plane " << i << " at " << rp.chil[i]
+                 << " after " << rp.chil[i - 1] << " Mpc/h)" << endl;
+            return 2;
+        }
+    return 0;
+}
+
 // The ranks of the run: one handle per device, their copies of the libc rand() stream and, with several devices and
 // --reduce rccl, their communicators.  The destructor releases them.
 struct Ranks {
@@ -626,11 +670,27 @@ struct LensingOutputs {
     string power_mode{};           // "", "auto" or "cross"
     vector<double> power_edges{};  // empty: 0 .. npix-1
     vector<float *> upload{};  // device buffers for planes read back from their files
+    bool shear_files = false;  // --shear: the shear handle's maps of every kappa map are written
+    // --raytrace: the plan, a one-source kappa handle that makes a plane's lens map, the rays, their six output buffers,
+    // and the sources in ascending redshift with the position of the next one to observe
+    const RayPlan *rt = nullptr;
+    slicer_kappa_handle lkh = nullptr;
+    slicer_rays_handle rh = nullptr;
+    float *rt_out[SLICER_RAYS_COUNT] = {};
+    vector<size_t> rt_order{};
+    size_t rt_next = 0;
 
     ~LensingOutputs()
     {
         for (float *b : upload)
             slicer_device_free(h, b);
+        for (float *b : rt_out)
+            if (b)
+                slicer_device_free(h, b);
+        if (rh)
+            slicer_rays_destroy(rh);
+        if (lkh)
+            slicer_kappa_destroy(lkh);
         if (pkh)
             slicer_peaks_destroy(pkh);
         if (mh)
@@ -647,7 +707,8 @@ struct LensingOutputs {
     {
         if (!zs.empty() && slicer_kappa_create(h, p.npix, (int)zs.size(), &kh) != SLICER_OK)
             return fail(h, "slicer_amd: --kappa");
-        if (kh && shear && slicer_shear_create(h, p.npix, p.fov, &shh) != SLICER_OK)
+        shear_files = kh && shear;
+        if (kh && (shear || rt) && slicer_shear_create(h, p.npix, p.fov, &shh) != SLICER_OK)
             return fail(h, "slicer_amd: --shear");
         if (kh && !power_mode.empty()) {
             const int ne = power_edges.empty() ? p.npix : (int)power_edges.size();
@@ -665,6 +726,67 @@ struct LensingOutputs {
         if (kh && !peaks_edges.empty() &&
             slicer_peaks_create(h, p.npix, (int)peaks_edges.size(), peaks_edges.data(), &pkh) != SLICER_OK)
             return fail(h, "slicer_amd: --peaks");
+        if (kh && rt) {
+            if (slicer_kappa_create(h, p.npix, 1, &lkh) != SLICER_OK ||
+                slicer_rays_create(h, p.npix, p.fov * M_PI / 180.0 / p.npix, &rh) != SLICER_OK)
+                return fail(h, "slicer_amd: --raytrace");
+            for (float *&b : rt_out)
+                if (slicer_device_malloc(h, (size_t)p.npix * (size_t)p.npix * sizeof(float), (void **)&b) != SLICER_OK)
+                    return fail(h, "slicer_amd: --raytrace");
+            rt_order.resize(zs.size());
+            for (size_t s = 0; s < zs.size(); s++)
+                rt_order[s] = s;
+            std::stable_sort(rt_order.begin(), rt_order.end(), [&](size_t a, size_t b) { return zs[a] < zs[b]; });
+            return observe_sources(0);  // the sources with no plane in front: from the start state
+        }
+        return 0;
+    }
+
+    // --raytrace, plane i of the cone, whose mass map is d_map: its lens map L = strength (m - mean m) from the one-source
+    // kappa handle, the maps of L from the shear handle, one step of the rays, and the sources this plane is the last
+    // in front of.
+    int trace_plane(int i, const float *d_map)
+    {
+        const char *who = "slicer_amd: --raytrace";
+        float *L = nullptr, *m[5] = {};
+        const int spectral[5] = {SLICER_SHEAR_ALPHA1, SLICER_SHEAR_ALPHA2, -1, SLICER_SHEAR_GAMMA1, SLICER_SHEAR_GAMMA2};
+        const int fd[5] = {SLICER_SHEAR_FD_ALPHA1, SLICER_SHEAR_FD_ALPHA2, SLICER_SHEAR_FD_KAPPA, SLICER_SHEAR_FD_GAMMA1,
+                           SLICER_SHEAR_FD_GAMMA2};
+        if (slicer_kappa_add(lkh, 1, &d_map, &rt->strength[i]) != SLICER_OK || slicer_kappa_finalize(lkh) != SLICER_OK ||
+            slicer_kappa_device_map(lkh, 0, &L) != SLICER_OK || slicer_shear_run(shh, L) != SLICER_OK ||
+            (gradient ? slicer_shear_fd(shh) : slicer_shear_deflection(shh)) != SLICER_OK)
+            return fail(h, who);
+        for (int k = 0; k < 5; k++) {
+            const int which = gradient ? fd[k] : spectral[k];
+            if (which < 0)
+                m[k] = L;
+            else if (slicer_shear_device_map(shh, which, &m[k]) != SLICER_OK)
+                return fail(h, who);
+        }
+        if (slicer_rays_step(rh, rt->chil[i], m[0], m[1], m[2], m[3], m[4]) != SLICER_OK ||
+            slicer_kappa_reset(lkh) != SLICER_OK)
+            return fail(h, who);
+        return observe_sources(i + 1);
+    }
+
+    // the sources, in ascending redshift, that have `done` planes in front of them: observed now and written
+    int observe_sources(int done)
+    {
+        static const char *const token[SLICER_RAYS_COUNT] = {".rt_kappa_z",  ".rt_gamma1_z", ".rt_gamma2_z",
+                                                              ".rt_omega_z",  ".rt_alpha1_z", ".rt_alpha2_z"};
+        vector<float> map((size_t)p.npix * (size_t)p.npix);
+        for (; rt_next < rt_order.size() && rt->in_front[rt_order[rt_next]] <= done; rt_next++) {
+            const size_t s = rt_order[rt_next];
+            char zbuf[32];
+            snprintf(zbuf, sizeof zbuf, "%.4f", zs[s]);
+            const FitsKey keys[2] = {{"ZSOURCE", false, 0, zs[s], " "}, {"ANGLE", false, 0, p.fov, " "}};
+            if (slicer_rays_observe(rh, rt->chis[s], rt_out) != SLICER_OK)
+                return fail(h, "slicer_amd: --raytrace");
+            for (int k = 0; k < SLICER_RAYS_COUNT; k++)
+                if (slicer_copy_to_host(h, map.data(), rt_out[k], map.size() * sizeof(float)) != SLICER_OK ||
+                    !save("ray-traced", token[k], zbuf, map, keys))
+                    return fail(h, "slicer_amd: --raytrace");
+        }
         return 0;
     }
 
@@ -709,6 +831,9 @@ struct LensingOutputs {
         }
         if (slicer_kappa_add(kh, (int)maps.size(), maps.data(), c.data()) != SLICER_OK)
             return fail(h, "slicer_amd: --kappa");
+        for (int i = i0; rt && i < i1; i++)
+            if (const int rc = trace_plane(i, maps[i - i0]))
+                return rc;
         return 0;
     }
 
@@ -753,7 +878,7 @@ struct LensingOutputs {
             const FitsKey keys[2] = {{"ZSOURCE", false, 0, zs[s], " "}, {"ANGLE", false, 0, p.fov, " "}};
             if (slicer_kappa_read(kh, (int)s, map.data()) != SLICER_OK || !save("convergence", ".kappa_z", zbuf, map, keys))
                 return fail(h, "slicer_amd: --kappa");
-            if (!shh && !mh && !pkh)
+            if (!shear_files && !mh && !pkh)
                 continue;
             float *d_kappa = nullptr;
             if (slicer_kappa_device_map(kh, (int)s, &d_kappa) != SLICER_OK)
@@ -772,7 +897,7 @@ struct LensingOutputs {
                     slicer_peaks_read(pkh, c, c + B, c + 2 * B, c + 3 * B, c + 3 * B + 3, c + 3 * B + 6) != SLICER_OK)
                     return fail(h, "slicer_amd: --peaks");
             }
-            if (!shh)
+            if (!shear_files)
                 continue;
             if (slicer_shear_run(shh, d_kappa) != SLICER_OK)
                 return fail(h, "slicer_amd: --kappa");
@@ -1050,6 +1175,9 @@ int main(int argc, char **argv)
     vector<double> kappa_zs, kappa_c;
     if (const int rc = kappa_weights(o, c, kappa_zs, kappa_c))
         return rc;
+    RayPlan ray_plan;
+    if (const int rc = raytrace_plan(o, c, kappa_zs, ray_plan))
+        return rc;
     const vector<int> devs = o.devices_spec.empty() ? vector<int>{o.device} : parse_devices(o.devices_spec);
     if (devs.empty() || (o.reduce_mode != "rccl" && o.reduce_mode != "host") ||
         (o.reduce_algo != "rooted" && o.reduce_algo != "direct")) {
@@ -1066,6 +1194,7 @@ int main(int argc, char **argv)
     lensing.power_edges = o.power_edges;
     lensing.moments_levels = o.moments ? o.moments_levels : -1;
     lensing.peaks_edges = o.peaks_edges;
+    lensing.rt = o.raytrace ? &ray_plan : nullptr;
     if (const int rc = lensing.create(o.shear))
         return rc;
     const int rc = run_planes(o, c, ranks, lensing);

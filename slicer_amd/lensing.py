@@ -1,7 +1,8 @@
 """Born-approximation convergence (kappa) maps from the lens planes, and the shear and lensing
 potential maps from them (row N6), the binned auto and cross power spectra of such maps (row N7), the deflection
 maps and finite-difference derivatives of the potential (row N8), and the central moments of such maps over a pyramid
-of 2x2 halvings (row N9), and the one-point PDF histogram and peak / minimum counts of such maps (row N10).
+of 2x2 halvings (row N9), and the one-point PDF histogram and peak / minimum counts of such maps (row N10), and
+multi-plane ray tracing through the lens planes (row N11).
 
 plane_weights wraps the host weights of include/slicer_amd.h (slicer_lensing_weights); Kappa is the device accumulator
 (slicer_kappa_*) bound to a Slicer handle: it reads the finalized plane maps where they are, in HBM.  Shear (slicer_shear_*)
@@ -9,7 +10,8 @@ turns one kappa map into phi, gamma1, gamma2 and |gamma| on the same device, and
 (Shear.deflection) and the finite-difference alpha, kappa and shear of phi (Shear.fd; fd_derivatives for any device
 map); Power (slicer_power_*) bins the spectra of several of them into C_l; Moments (slicer_moments_*) halves a map
 level by level and sums the powers 2 ... 8 of every level's pixels about a centre; Peaks (slicer_peaks_*) counts a
-map's pixels, peaks and minima by height over a list of edges.
+map's pixels, peaks and minima by height over a list of edges; Rays (slicer_rays_*) shoots one ray per pixel through
+the planes' deflection, convergence and shear maps (plane_strengths scales a mass plane to its lens map).
 """
 import ctypes as C
 import math
@@ -49,6 +51,32 @@ def plane_weights(omega_m, omega_lambda, w0, fov_deg, npix, ld, ld2, zsnap, sour
         raise SlicerError(rc, (_L.slicer_last_error(None) or b"").decode())
     out["c"] = coeff
     out["zs"] = out["zup"].copy() if zs is None else zs
+    return out
+
+
+def plane_strengths(omega_m, omega_lambda, w0, fov_deg, npix, ld, ld2, zsnap, sources="all", growth=True, wa=0.0,
+                    physical=False):
+    """The per-plane lensing strengths of the ray tracer (slicer_lensing_plane_strengths), arguments as plane_weights:
+    dict with strength [P] (the lens map of plane p is strength[p] (m_p - mean m_p)), chil [P], zs, chis [S] and
+    n_in_front [S] (the planes in front of every source)."""
+    ld = np.ascontiguousarray(ld, np.float64)
+    ld2 = np.ascontiguousarray(ld2, np.float64)
+    zsnap = np.ascontiguousarray(zsnap, np.float64)
+    P = ld.size
+    assert ld2.size == P and zsnap.size == P
+    zs = None if isinstance(sources, str) and sources == "all" else np.ascontiguousarray(sources, np.float64)
+    S = P if zs is None else zs.size
+    out = {"strength": np.zeros(P, np.float64), "chil": np.zeros(P, np.float64), "chis": np.zeros(S, np.float64),
+           "n_in_front": np.zeros(S, np.int32)}
+    rc = _L.slicer_lensing_plane_strengths(float(omega_m), float(omega_lambda), float(w0), float(wa), float(fov_deg),
+                                           int(npix), int(bool(growth)), int(bool(physical)), P, _dptr(ld), _dptr(ld2),
+                                           _dptr(zsnap), S, _dptr(zs), _dptr(out["strength"]), _dptr(out["chil"]),
+                                           _dptr(out["chis"]), _dptr(out["n_in_front"]))
+    if rc:
+        raise SlicerError(rc, (_L.slicer_last_error(None) or b"").decode())
+    if zs is None:
+        zs = plane_weights(omega_m, omega_lambda, w0, fov_deg, npix, ld, ld2, zsnap, "all", growth, wa, physical)["zs"]
+    out["zs"] = zs
     return out
 
 
@@ -98,6 +126,12 @@ class Kappa:
         self._s._chk(_L.slicer_kappa_finalize(self._kh))
         self._dirty = False
 
+    def reset(self):
+        """Zero the accumulators and forget the means: the handle as just created."""
+        self._s._chk(_L.slicer_kappa_reset(self._kh))
+        self.n_added = 0
+        self._dirty = True
+
     def plane_means(self):
         out = np.zeros(self.n_added, np.float64)
         self._s._chk(_L.slicer_kappa_plane_means(self._kh, out.ctypes.data, self.n_added))
@@ -140,6 +174,7 @@ class Shear:
         sh = C.c_void_p()
         slicer._chk(_L.slicer_shear_create(slicer._h, self.npix, self.angle_deg, C.byref(sh)))
         self._sh = sh
+        self.last_input = None  # the device address handed to the last run
 
     def close(self):
         if getattr(self, "_sh", None):
@@ -161,6 +196,7 @@ class Shear:
     def run(self, d_kappa):
         """d_kappa: device address of an f32 npix^2 map."""
         self._s._chk(_L.slicer_shear_run(self._sh, int(d_kappa)))
+        self.last_input = int(d_kappa)
 
     def run_kappa(self, kappa: Kappa, s):
         """The map of source s of a Kappa accumulator, where it is."""
@@ -488,3 +524,95 @@ class Peaks:
                                           below.ctypes.data, above.ctypes.data, nan.ctypes.data))
         return {"edges": self.edges.copy(), "pdf": pdf, "peaks": peaks, "minima": minima, "below": below, "above": above,
                 "nan": int(nan[0])}
+
+
+RAYS_KAPPA, RAYS_GAMMA1, RAYS_GAMMA2, RAYS_OMEGA, RAYS_DEFLECTION1, RAYS_DEFLECTION2 = range(6)
+RAYS_COUNT = 6
+RAYS_STATE = ("b1", "b2", "t1", "t2", "A11", "A12", "A21", "A22", "T11", "T12", "T21", "T22")
+
+
+class Rays:
+    """One ray per pixel of an npix^2 grid of `spacing` radians per pixel, traced through lens planes on the device of
+    `slicer`, on its stream.  step takes a plane's five device maps; observe gives the
+    distortion (kappa, gamma1, gamma2, omega) and the total deflection at a source distance."""
+
+    def __init__(self, slicer: Slicer, npix, spacing):
+        self._s = slicer
+        self.npix, self.spacing = int(npix), float(spacing)
+        rh = C.c_void_p()
+        slicer._chk(_L.slicer_rays_create(slicer._h, self.npix, self.spacing, C.byref(rh)))
+        self._rh = rh
+
+    def close(self):
+        if getattr(self, "_rh", None):
+            _L.slicer_rays_destroy(self._rh)
+            self._rh = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def reset(self):
+        """Back to the start state."""
+        self._s._chk(_L.slicer_rays_reset(self._rh))
+
+    def step(self, chi, d_alpha1, d_alpha2, d_kappa, d_gamma1, d_gamma2):
+        """Through the plane at comoving distance chi; the five arguments are device addresses of f32 npix^2 maps."""
+        ptrs = [None if p is None else int(p) for p in (d_alpha1, d_alpha2, d_kappa, d_gamma1, d_gamma2)]
+        self._s._chk(_L.slicer_rays_step(self._rh, float(chi), *ptrs))
+
+    def step_shear(self, shear: Shear, chi, gradient=False, d_kappa=None):
+        """The plane whose lens map was the last shear.run(d_kappa), followed by shear.deflection() (spectral maps) or
+        shear.fd() (gradient=True: the finite-difference maps, which bring their own kappa)."""
+        if gradient:
+            maps = [shear.device_map(w) for w in (SHEAR_FD_ALPHA1, SHEAR_FD_ALPHA2, SHEAR_FD_KAPPA, SHEAR_FD_GAMMA1,
+                                                  SHEAR_FD_GAMMA2)]
+        else:
+            if d_kappa is None:
+                d_kappa = shear.last_input
+            if d_kappa is None:
+                raise ValueError("step_shear: the Shear handle has not run")
+            maps = [shear.device_map(SHEAR_ALPHA1), shear.device_map(SHEAR_ALPHA2), d_kappa,
+                    shear.device_map(SHEAR_GAMMA1), shear.device_map(SHEAR_GAMMA2)]
+        self.step(chi, *maps)
+
+    def observe_device(self, chi_s, ptrs):
+        """slicer_rays_observe as it is: ptrs are RAYS_COUNT device addresses of npix^2 f32 buffers, None to skip one."""
+        arr = (C.c_void_p * RAYS_COUNT)(*[None if p is None else int(p) for p in ptrs])
+        self._s._chk(_L.slicer_rays_observe(self._rh, float(chi_s), arr))
+
+    def observe(self, chi_s, which=tuple(range(RAYS_COUNT))):
+        """{code: f32 [npix, npix] array} for the RAYS_* codes in `which`, for a source at comoving distance chi_s."""
+        which = [int(w) for w in which]
+        if any(not 0 <= w < RAYS_COUNT for w in which):
+            raise ValueError(f"which: RAYS_* codes 0..{RAYS_COUNT - 1}")
+        ptrs = [None] * RAYS_COUNT
+        try:
+            for w in set(which):
+                ptrs[w] = self._s.malloc(4 * self.npix * self.npix)
+            self.observe_device(chi_s, ptrs)
+            return {w: self._s.to_host(ptrs[w], (self.npix, self.npix), np.float32) for w in which}
+        finally:
+            for p in ptrs:
+                if p is not None:
+                    self._s.free(p)
+
+    def state(self):
+        """The state, f64 [12, npix, npix] in the order of RAYS_STATE; waits for the stream."""
+        out = np.empty((len(RAYS_STATE), self.npix, self.npix), np.float64)
+        self._s._chk(_L.slicer_rays_state(self._rh, out.ctypes.data))
+        return out
+
+    def planes(self):
+        """(number of steps since the start state, comoving distance of the last plane)."""
+        n, chi = C.c_int32(), C.c_double()
+        self._s._chk(_L.slicer_rays_planes(self._rh, C.byref(n), C.byref(chi)))
+        return n.value, chi.value
