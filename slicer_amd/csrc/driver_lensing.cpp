@@ -1,0 +1,510 @@
+// driver_lensing.cpp -- the lensing outputs of SLICER_amd.  All are opt-in, need --kappa and are computed on device 0;
+// without --kappa the run is unchanged.  The per-source files carry the kappa file's name with another token, and its header.
+//   * --kappa all|z1,z2,...: Born convergence maps, one FITS per source redshift, accumulated from the finalized total
+//     maps of every pass (the reference's post-processing script Lens/kslicer.py);
+//     --kappa-no-growth drops its linear-growth correction.
+//   * --shear: per source the shear maps gamma1, gamma2, |gamma| and the lensing potential phi of the kappa map (the
+//     reference's Lens/smr.py).
+//   * --deflection (with --shear): the deflection maps .alpha1_z, .alpha2_z.  --shear-derivative fft|gradient (with
+//     --shear or --raytrace, default fft) chooses where the gammas and alphas come from: the FFT filters, or smr's
+//     derivative="gradient", finite differences of phi that do not wrap the map's edges.  The
+//     phi and kappa files are the same either way.
+//   * --raytrace: one ray per pixel through the planes, near to far.  Every plane's lens map
+//     strength_p (m_p - mean m_p) is turned into its deflection, convergence and shear maps (the device work of --shear
+//     --deflection, per plane) and the rays step through them at chi(zl_p).  Per source .rt_kappa_z, .rt_gamma1_z,
+//     .rt_gamma2_z, .rt_omega_z (the distortion matrix) and .rt_alpha1_z, .rt_alpha2_z (the total deflection, radians).
+//   * --power auto|cross: <directory><simulation>.cl_<npix>_<suffix>.txt, the binned auto (or auto and cross) power
+//     spectra C_l of the kappa maps (Lens/smr.py's PS without its defects); --power-edges r0,r1,...
+//     sets the bin edges in units of l_f = 2 pi / ANGLE (default 0, 1, ..., npix-1).
+//   * --moments: <directory><simulation>.moments_<npix>_<suffix>.txt, the raw central power sums S_2 ... S_8 and the
+//     mean of every kappa map and of --moments-levels L (default 0) successive 2x2 block means of it, about each level's
+//     own mean (Lens/moment.py and Lens/halve.py).
+//   * --peaks lo,hi,bins: <directory><simulation>.peaks_<npix>_<suffix>.txt, the one-point PDF histogram of every kappa
+//     map and the counts of its peaks and minima by height (strictly above / below all 8 neighbours; the map does not
+//     wrap) over `bins` (1 ... 1024) uniform bins from lo to hi; with --moments also of every level of its pyramid of
+//     block means.
+#include "driver_lensing.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdarg>
+#include <iostream>
+#include <numeric>
+
+using std::cerr;
+using std::cout;
+using std::endl;
+using std::string;
+using std::vector;
+
+namespace slicer_amd {
+
+string plane_label(int pll)
+{
+    char b[16];
+    snprintf(b, sizeof b, "%03d", pll);
+    return b;
+}
+
+vector<string> split(const string &s)
+{
+    vector<string> out;
+    size_t i = 0;
+    for (size_t j; (j = s.find(',', i)) != string::npos; i = j + 1)
+        out.push_back(s.substr(i, j - i));
+    out.push_back(s.substr(i));
+    return out;
+}
+
+static int bad(const string &message)
+{
+    cerr << message << endl;
+    return 2;
+}
+
+// printf onto the end of `text`
+__attribute__((format(printf, 2, 3))) static void add(string &text, const char *fmt, ...)
+{
+    char piece[512];  // (the longest is a histogram row: nine numbers)
+    va_list a;
+    va_start(a, fmt);
+    vsnprintf(piece, sizeof piece, fmt, a);
+    va_end(a);
+    text += piece;
+}
+
+int LensingOptions::parse(int argc, char **argv, int &i)
+{
+    const string a = argv[i];
+    const bool has_value = i + 1 < argc;
+    if (a == "--kappa" && has_value) kappa = argv[++i];
+    else if (a == "--kappa-no-growth") growth = false;
+    else if (a == "--shear") shear = true;
+    else if (a == "--deflection") deflection = true;
+    else if (a == "--raytrace") raytrace = true;
+    else if (a == "--shear-derivative" && has_value) shear_derivative = argv[++i];
+    else if (a == "--power" && has_value) power = argv[++i];
+    else if (a == "--power-edges" && has_value) {
+        for (const string &tok : split(argv[++i])) {
+            char *end = nullptr;
+            const double r = strtod(tok.c_str(), &end);
+            if (tok.empty() || *end != '\0')
+                return bad("bad --power-edges (a comma-separated list of radii in units of l_f)");
+            power_edges.push_back(r);
+        }
+    } else if (a == "--moments") moments = true;
+    else if (a == "--moments-levels") {
+        if (!has_value)
+            return bad("--moments-levels needs a value (the number of halvings below the kappa map)");
+        char *end = nullptr;
+        const long v = strtol(argv[++i], &end, 10);
+        if (end == argv[i] || *end != '\0' || v < -1000 || v > 1000)
+            return bad("bad --moments-levels (the number of halvings below the kappa map)");
+        moments_levels = (int)v;
+        moments_levels_given = true;
+    } else if (a == "--peaks") {
+        const vector<string> tok = has_value ? split(argv[++i]) : vector<string>{};
+        char *e0 = nullptr, *e1 = nullptr, *e2 = nullptr;
+        const double lo = tok.size() == 3 ? strtod(tok[0].c_str(), &e0) : 0.0;
+        const double hi = tok.size() == 3 ? strtod(tok[1].c_str(), &e1) : 0.0;
+        const long bins = tok.size() == 3 ? strtol(tok[2].c_str(), &e2, 10) : 0;
+        if (tok.size() != 3 || tok[0].empty() || tok[1].empty() || tok[2].empty() || *e0 != '\0' || *e1 != '\0' ||
+            *e2 != '\0' || bins < 1 || bins > SLICER_PEAKS_MAX_BINS)
+            return bad("bad --peaks (lo,hi,bins: the first and the last edge and the number of bins, 1 ... " +
+                       std::to_string(SLICER_PEAKS_MAX_BINS) + ")");
+        peaks_edges.resize(bins + 1);
+        if (slicer_peaks_edges(lo, hi, (int32_t)bins, peaks_edges.data()) != SLICER_OK)
+            return bad(string("bad --peaks: ") + slicer_last_error(nullptr));
+    } else
+        return -1;
+    return 0;
+}
+
+int LensingOptions::check() const
+{
+    const bool no_kappa = kappa.empty(), derivative = !shear_derivative.empty(), pw = !power.empty();
+    const std::pair<bool, const char *> rules[] = {
+        {shear && no_kappa, "--shear needs --kappa (the shear maps are computed from the kappa maps)"},
+        {raytrace && no_kappa, "--raytrace needs --kappa (the rays are observed at the source redshifts of the kappa maps)"},
+        {deflection && !shear, "--deflection needs --shear (the deflection maps are computed from the spectrum of the shear maps)"},
+        {derivative && shear_derivative != "fft" && !gradient(), "bad --shear-derivative (fft or gradient)"},
+        {derivative && !shear && !raytrace, "--shear-derivative needs --shear"},
+        {pw && power != "auto" && power != "cross", "bad --power (auto or cross)"},
+        {pw && no_kappa, "--power needs --kappa (the power spectra are those of the kappa maps)"},
+        {!power_edges.empty() && !pw, "--power-edges needs --power"},
+        {moments && no_kappa, "--moments needs --kappa (the moments are those of the kappa maps)"},
+        {moments_levels_given && !moments, "--moments-levels needs --moments"},
+        {!peaks_edges.empty() && no_kappa, "--peaks needs --kappa (the histograms and peak counts are those of the kappa maps)"},
+    };
+    for (const auto &[broken, message] : rules)
+        if (broken)
+            return bad(message);
+    return 0;
+}
+
+int LensingOptions::check_npix(const InputParams &p) const
+{
+    const string npix = "npix = " + std::to_string(p.npix);
+    const string fft_sizes = " is not supported (2 ... 16384, prime factors 2, 3, 5, 7 only)";
+    if (shear && !slicer_shear_supported(p.npix))
+        return bad("--shear: " + npix + fft_sizes);
+    if (raytrace && !p.physical && !slicer_shear_supported(p.npix))  // (physical: refused with the weights)
+        return bad("--raytrace: " + npix + fft_sizes);
+    if (gradient() && p.npix < 5)
+        return bad("--shear-derivative gradient: " + npix + " is not supported (the stencils take at least 5)");
+    if (!power.empty() && !slicer_shear_supported(p.npix))
+        return bad("--power: " + npix + fft_sizes);
+    if (!power.empty()) {  // the edges
+        const int ne = n_power_edges(p.npix);
+        vector<int64_t> cnt(std::max(ne - 1, 1));
+        vector<double> mr(cnt.size());
+        if (slicer_power_bins(p.npix, ne, power_edges_or_null(), cnt.data(), mr.data()) != SLICER_OK)
+            return bad(string("--power-edges: ") + slicer_last_error(nullptr));
+    }
+    if (moments) {  // the pyramid's depth
+        int most = 0;
+        while (p.npix >> (most + 1) > 0)
+            most++;
+        if (p.npix < 1 || moments_levels < 0 || moments_levels > most)
+            return bad("--moments-levels " + std::to_string(moments_levels) + " is outside 0 ... " + std::to_string(most) +
+                       " = floor(log2 npix) for " + npix);
+    }
+    return 0;
+}
+
+int plan_lensing(const LensingOptions &o, const InputParams &p, const Header &simdata, const Lens &lens, LensingPlan &plan)
+{
+    if (o.kappa.empty())
+        return 0;
+    const bool all = o.kappa == "all";  // otherwise z1,z2,...
+    for (const string &tok : all ? vector<string>{} : split(o.kappa)) {
+        char *end = nullptr;
+        plan.zs.push_back(strtod(tok.c_str(), &end));
+        if (tok.empty() || *end != '\0' || !(plan.zs.back() >= 0))
+            return bad("bad --kappa (all, or a comma-separated list of source redshifts)");
+    }
+    const int P = lens.nplanes, S = all ? P : (int)plan.zs.size();
+    vector<double> zup(P);
+    plan.coeff.assign((size_t)S * P, 0.0);
+    if (slicer_lensing_weights(simdata.om0, simdata.oml, p.w, 0.0, p.fov, p.npix, o.growth, p.physical, P, lens.ld.data(),
+                               lens.ld2.data(), lens.zfromsnap.data(), S, all ? nullptr : plan.zs.data(),
+                               plan.coeff.data(), nullptr, zup.data(), nullptr, nullptr) != SLICER_OK)
+        return fail(nullptr, "slicer_amd: --kappa");
+    if (all)
+        plan.zs = zup;
+    if (!o.raytrace)
+        return 0;
+    plan.strength.resize(P);
+    plan.chil.resize(P);
+    plan.chis.resize(S);
+    plan.in_front.resize(S);
+    if (slicer_lensing_plane_strengths(simdata.om0, simdata.oml, p.w, 0.0, p.fov, p.npix, o.growth, p.physical, P,
+                                       lens.ld.data(), lens.ld2.data(), lens.zfromsnap.data(), S, plan.zs.data(),
+                                       plan.strength.data(), plan.chil.data(), plan.chis.data(),
+                                       plan.in_front.data()) != SLICER_OK)
+        return fail(nullptr, "slicer_amd: --raytrace");
+    for (int i = 1; i < P; i++)
+        if (!(plan.chil[i] > plan.chil[i - 1])) {
+            cerr << "--raytrace: the plane distances are not strictly ascending (plane " << i << " at " << plan.chil[i]
+                 << " after " << plan.chil[i - 1] << " Mpc/h)" << endl;
+            return 2;
+        }
+    return 0;
+}
+
+int LensingOutputs::create()
+{
+    const vector<double> &zs = plan.zs;
+    if (zs.empty())
+        return 0;
+    map.resize((size_t)p.npix * (size_t)p.npix);
+    if (slicer_kappa_create(h, p.npix, (int)zs.size(), kh.out()) != SLICER_OK)
+        return fail(h, "slicer_amd: --kappa");
+    if ((o.shear || o.raytrace) && slicer_shear_create(h, p.npix, p.fov, shh.out()) != SLICER_OK)
+        return fail(h, "slicer_amd: --shear");
+    if (!o.power.empty() && zs.size() > 128) {
+        cerr << "slicer_amd: --power: " << zs.size() << " sources, at most 128" << endl;
+        return 2;
+    }
+    if (!o.power.empty() && slicer_power_create(h, p.npix, p.fov, (int)zs.size(), o.power == "cross", o.n_power_edges(p.npix),
+                                                o.power_edges_or_null(), ph.out()) != SLICER_OK)
+        return fail(h, "slicer_amd: --power");
+    if (o.moments && slicer_moments_create(h, p.npix, o.moments_levels, SLICER_HALVE_MEAN, mh.out()) != SLICER_OK)
+        return fail(h, "slicer_amd: --moments");
+    if (!o.peaks_edges.empty() &&
+        slicer_peaks_create(h, p.npix, (int)o.peaks_edges.size(), o.peaks_edges.data(), pkh.out()) != SLICER_OK)
+        return fail(h, "slicer_amd: --peaks");
+    if (!o.raytrace)
+        return 0;
+    if (slicer_kappa_create(h, p.npix, 1, lkh.out()) != SLICER_OK ||
+        slicer_rays_create(h, p.npix, p.fov * M_PI / 180.0 / p.npix, rh.out()) != SLICER_OK)
+        return fail(h, "slicer_amd: --raytrace");
+    for (int k = 0; k < SLICER_RAYS_COUNT; k++)
+        if (!rt_out.add(p.npix))
+            return fail(h, "slicer_amd: --raytrace");
+    rt_order.resize(zs.size());
+    std::iota(rt_order.begin(), rt_order.end(), (size_t)0);
+    std::stable_sort(rt_order.begin(), rt_order.end(), [&](size_t a, size_t b) { return zs[a] < zs[b]; });
+    return observe_sources(0);  // the sources with no plane in front: from the start state
+}
+
+// --raytrace, plane i of the cone, whose mass map is d_map: its lens map L = strength (m - mean m) from the one-source
+// kappa handle, the maps of L from the shear handle, one step of the rays, and the sources this plane is the last in
+// front of.
+int LensingOutputs::trace_plane(int i, const float *d_map)
+{
+    const char *who = "slicer_amd: --raytrace";
+    const bool gradient = o.gradient();
+    float *L = nullptr, *m[5] = {};
+    const int spectral[5] = {SLICER_SHEAR_ALPHA1, SLICER_SHEAR_ALPHA2, -1, SLICER_SHEAR_GAMMA1, SLICER_SHEAR_GAMMA2};
+    const int fd[5] = {SLICER_SHEAR_FD_ALPHA1, SLICER_SHEAR_FD_ALPHA2, SLICER_SHEAR_FD_KAPPA, SLICER_SHEAR_FD_GAMMA1,
+                       SLICER_SHEAR_FD_GAMMA2};
+    if (slicer_kappa_add(lkh, 1, &d_map, &plan.strength[i]) != SLICER_OK || slicer_kappa_finalize(lkh) != SLICER_OK ||
+        slicer_kappa_device_map(lkh, 0, &L) != SLICER_OK || slicer_shear_run(shh, L) != SLICER_OK ||
+        (gradient ? slicer_shear_fd(shh) : slicer_shear_deflection(shh)) != SLICER_OK)
+        return fail(h, who);
+    for (int k = 0; k < 5; k++) {
+        const int which = gradient ? fd[k] : spectral[k];
+        if (which < 0)
+            m[k] = L;
+        else if (slicer_shear_device_map(shh, which, &m[k]) != SLICER_OK)
+            return fail(h, who);
+    }
+    if (slicer_rays_step(rh, plan.chil[i], m[0], m[1], m[2], m[3], m[4]) != SLICER_OK ||
+        slicer_kappa_reset(lkh) != SLICER_OK)
+        return fail(h, who);
+    return observe_sources(i + 1);
+}
+
+// the sources, in ascending redshift, that have `done` planes in front of them: observed now and written
+int LensingOutputs::observe_sources(int done)
+{
+    static const char *const token[SLICER_RAYS_COUNT] = {".rt_kappa_z", ".rt_gamma1_z", ".rt_gamma2_z",
+                                                          ".rt_omega_z", ".rt_alpha1_z", ".rt_alpha2_z"};
+    for (; rt_next < rt_order.size() && plan.in_front[rt_order[rt_next]] <= done; rt_next++) {
+        const size_t s = rt_order[rt_next];
+        if (slicer_rays_observe(rh, plan.chis[s], rt_out.maps.data()) != SLICER_OK)
+            return fail(h, "slicer_amd: --raytrace");
+        for (int k = 0; k < SLICER_RAYS_COUNT; k++)
+            if (slicer_copy_to_host(h, map.data(), rt_out.maps[k], map.size() * sizeof(float)) != SLICER_OK ||
+                !save("ray-traced", token[k], s))
+                return fail(h, "slicer_amd: --raytrace");
+    }
+    return 0;
+}
+
+int LensingOutputs::add_pass(int i0, int i1, const vector<int> &todo)
+{
+    const size_t np2 = (size_t)p.npix * (size_t)p.npix;
+    vector<const float *> maps;
+    vector<double> c;
+    vector<float> host;
+    size_t n_up = 0;
+    for (int i = i0; i < i1; i++) {
+        const auto it = std::find(todo.begin(), todo.end(), i);
+        float *d = nullptr;
+        if (it != todo.end()) {
+            if (slicer_plane_device_maps(h, (int)(it - todo.begin()), &d, nullptr) != SLICER_OK)
+                return fail(h, "slicer_amd");
+        } else {
+            const string path = fileOutput(p, plane_label(lens.pll[i]));
+            host.resize(np2);
+            if (!fits_read_image(path, p.npix, host.data())) {
+                cerr << "slicer_amd: --kappa: cannot read the plane back from " << path << endl;
+                return 1;
+            }
+            if (upload.maps.size() <= n_up && !upload.add(p.npix))
+                return fail(h, "slicer_amd");
+            d = upload.maps[n_up++];
+            // (stream-ordered after the previous batch's kernels, which may still read this buffer)
+            if (slicer_copy_to_device(h, d, host.data(), np2 * sizeof(float)) != SLICER_OK)
+                return fail(h, "slicer_amd");
+        }
+        maps.push_back(d);
+        for (size_t s = 0; s < plan.zs.size(); s++)
+            c.push_back(plan.coeff[s * lens.nplanes + i]);
+    }
+    if (slicer_kappa_add(kh, (int)maps.size(), maps.data(), c.data()) != SLICER_OK)
+        return fail(h, "slicer_amd: --kappa");
+    for (int i = i0; o.raytrace && i < i1; i++)
+        if (const int rc = trace_plane(i, maps[i - i0]))
+            return rc;
+    return 0;
+}
+
+// `map` into <directory><simulation><token><z_s>_<npix>_<suffix>.fits with the keys of kslicer's genericHeader
+bool LensingOutputs::save(const char *what, const char *token, size_t s)
+{
+    char z[32];
+    snprintf(z, sizeof z, "%.4f", plan.zs[s]);
+    const FitsKey keys[2] = {{"ZSOURCE", false, 0, plan.zs[s], " "}, {"ANGLE", false, 0, p.fov, " "}};
+    const string path = p.directory + p.simulation + token + z + "_" + p.snpix + "_" + p.suffix + ".fits";
+    cout << "Saving the " << what << " map on: " << path << endl;
+    if (fits_write_image(path, map.data(), p.npix, keys, 2))
+        return true;
+    cerr << "It was not possible to create the map: " << path << endl;
+    return false;
+}
+
+// Per source the kappa file, then its moments, then the histograms of its pyramid (which the moments of the same source
+// left behind), then the shear files; after the sources the three tables.
+int LensingOutputs::write()
+{
+    if (slicer_kappa_finalize(kh) != SLICER_OK)
+        return fail(h, "slicer_amd: --kappa");
+    for (size_t s = 0; s < plan.zs.size(); s++) {
+        if (slicer_kappa_read(kh, (int)s, map.data()) != SLICER_OK || !save("convergence", ".kappa_z", s))
+            return fail(h, "slicer_amd: --kappa");
+        float *d_kappa = nullptr;
+        if (slicer_kappa_device_map(kh, (int)s, &d_kappa) != SLICER_OK)
+            return fail(h, "slicer_amd: --kappa");
+        if (const int rc = mh ? source_moments(s, d_kappa) : 0)
+            return rc;
+        if (const int rc = pkh ? source_peaks(s, d_kappa) : 0)
+            return rc;
+        if (const int rc = o.shear ? source_shear(s, d_kappa) : 0)
+            return rc;
+    }
+    if (const int rc = ph ? power_spectra() : 0)
+        return rc;
+    if (mh && write_table("moments", ".moments_", moments))
+        return 1;
+    return pkh ? write_table("histograms and peak counts", ".peaks_", peaks) : 0;
+}
+
+// The moments table: '#' lines (npix, angle, levels, column names), then per (source, level) z level npix mean S2 ... S8
+// (%.17g): the raw sums about the level's own mean
+int LensingOutputs::source_moments(size_t s, const float *d_kappa)
+{
+    const int nlev = o.moments_levels + 1;
+    vector<int32_t> npix(nlev);
+    vector<double> mean(nlev), sums(nlev * SLICER_MOMENTS_ORDERS);
+    if (slicer_moments_run(mh, d_kappa, nullptr) != SLICER_OK ||
+        slicer_moments_read(mh, npix.data(), mean.data(), nullptr, sums.data()) != SLICER_OK)
+        return fail(h, "slicer_amd: --moments");
+    if (s == 0) {
+        add(moments, "# npix %d\n# angle_deg %.17g\n# levels %d\n# z level npix mean", p.npix, p.fov, o.moments_levels);
+        for (int k = 2; k < 2 + SLICER_MOMENTS_ORDERS; k++)
+            add(moments, " S%d", k);
+        add(moments, "\n");
+    }
+    for (int l = 0; l < nlev; l++) {
+        add(moments, "%.17g %d %d %.17g", plan.zs[s], l, (int)npix[l], mean[l]);
+        for (int k = 0; k < SLICER_MOMENTS_ORDERS; k++)
+            add(moments, " %.17g", sums[l * SLICER_MOMENTS_ORDERS + k]);
+        add(moments, "\n");
+    }
+    return 0;
+}
+
+// The histogram table: '#' lines (npix, angle, levels, the edges, column names), then per (source, level) one row per
+// bin: -1 (below the first edge), 0 ... B-1, B (above the last), B+1 (NaN pixels).  The levels are those of the pyramid
+// that the moments of this source left behind (level 0 alone without --moments).
+int LensingOutputs::source_peaks(size_t s, float *d_kappa)
+{
+    const vector<double> &e = o.peaks_edges;
+    const int B = (int)e.size() - 1, levels = mh ? o.moments_levels : 0;
+    vector<int64_t> c(3 * B + 7);  // pdf, peaks, minima [B]; below, above [3]; nan
+    const int64_t *below = &c[3 * B], *above = below + 3;
+    if (s == 0) {
+        add(peaks, "# npix %d\n# angle_deg %.17g\n# levels %d\n# edges", p.npix, p.fov, levels);
+        for (double v : e)
+            add(peaks, " %.17g", v);
+        add(peaks, "\n# z level npix bin lo hi n_pixels n_peaks n_minima\n");
+    }
+    for (int l = 0; l <= levels; l++) {
+        float *d_level = d_kappa;
+        if (l > 0 && slicer_moments_device_map(mh, l, &d_level) != SLICER_OK)
+            return fail(h, "slicer_amd: --peaks");
+        if (slicer_peaks_run_npix(pkh, d_level, p.npix >> l) != SLICER_OK ||
+            slicer_peaks_read(pkh, &c[0], &c[B], &c[2 * B], &c[3 * B], &c[3 * B + 3], &c[3 * B + 6]) != SLICER_OK)
+            return fail(h, "slicer_amd: --peaks");
+        const auto row = [&](int bin, double lo, double hi, int64_t n_pixels, int64_t n_peaks, int64_t n_minima) {
+            add(peaks, "%.17g %d %d %d %.17g %.17g %lld %lld %lld\n", plan.zs[s], l, p.npix >> l, bin, lo, hi,
+                (long long)n_pixels, (long long)n_peaks, (long long)n_minima);
+        };
+        row(-1, -INFINITY, e[0], below[0], below[1], below[2]);
+        for (int b = 0; b < B; b++)
+            row(b, e[b], e[b + 1], c[b], c[B + b], c[2 * B + b]);
+        row(B, e[B], INFINITY, above[0], above[1], above[2]);
+        row(B + 1, NAN, NAN, c[3 * B + 6], 0, 0);
+    }
+    return 0;
+}
+
+// smr.smr(kappa file): next to the kappa file, the same name with the .kappa_z token replaced, the same header
+int LensingOutputs::source_shear(size_t s, const float *d_kappa)
+{
+    static const char *const token[6] = {".gamma1_z", ".gamma2_z", ".gamma_z", ".phi_z", ".alpha1_z", ".alpha2_z"};
+    const int spectral[6] = {SLICER_SHEAR_GAMMA1, SLICER_SHEAR_GAMMA2, SLICER_SHEAR_GAMMA,
+                             SLICER_SHEAR_PHI,    SLICER_SHEAR_ALPHA1, SLICER_SHEAR_ALPHA2};
+    const int fd[6] = {SLICER_SHEAR_FD_GAMMA1, SLICER_SHEAR_FD_GAMMA2, SLICER_SHEAR_FD_GAMMA,
+                       SLICER_SHEAR_PHI,       SLICER_SHEAR_FD_ALPHA1, SLICER_SHEAR_FD_ALPHA2};
+    const bool g = o.gradient();
+    if (slicer_shear_run(shh, d_kappa) != SLICER_OK)
+        return fail(h, "slicer_amd: --kappa");
+    if ((g && slicer_shear_fd(shh) != SLICER_OK) || (o.deflection && !g && slicer_shear_deflection(shh) != SLICER_OK))
+        return fail(h, "slicer_amd: --shear");
+    for (int k = 0; k < (o.deflection ? 6 : 4); k++)
+        if (slicer_shear_read(shh, g ? fd[k] : spectral[k], map.data()) != SLICER_OK ||
+            !save(k < 4 ? "shear" : "deflection", token[k], s))
+            return fail(h, "slicer_amd: --kappa");
+    return 0;
+}
+
+// The spectra table: '#' lines (npix, angle, source redshifts, column names), then per bin ell_lo ell_hi ell_mean n_modes
+// and C of every pair (%.17g; nan for an empty bin)
+int LensingOutputs::power_spectra()
+{
+    const int S = (int)plan.zs.size(), B = o.n_power_edges(p.npix) - 1;
+    const bool cross = o.power == "cross";
+    const size_t n_pairs = cross ? (size_t)S * (S + 1) / 2 : S;
+    vector<float *> maps(S);
+    for (int s = 0; s < S; s++)
+        if (slicer_kappa_device_map(kh, s, &maps[s]) != SLICER_OK)
+            return fail(h, "slicer_amd: --power");
+    vector<double> c(n_pairs * B), ell(B);
+    vector<int64_t> counts(B);
+    if (slicer_power_run(ph, maps.data()) != SLICER_OK ||
+        slicer_power_read(ph, c.data(), ell.data(), counts.data()) != SLICER_OK)
+        return fail(h, "slicer_amd: --power");
+    const double ell_f = 2.0 * M_PI / (p.fov * M_PI / 180.0);
+    string cl;
+    add(cl, "# npix %d\n# angle_deg %.17g\n# zs", p.npix, p.fov);
+    for (double z : plan.zs)
+        add(cl, " %.17g", z);
+    add(cl, "\n# ell_lo ell_hi ell_mean n_modes");
+    for (int s = 0; s < S; s++)
+        for (int t = s; t < (cross ? S : s + 1); t++)
+            add(cl, " C_%d_%d", s, t);
+    add(cl, "\n");
+    for (int b = 0; b < B; b++) {
+        const double lo = o.power_edges.empty() ? (double)b : o.power_edges[b];
+        const double hi = o.power_edges.empty() ? (double)(b + 1) : o.power_edges[b + 1];
+        add(cl, "%.17g %.17g %.17g %lld", lo * ell_f, hi * ell_f, ell[b], (long long)counts[b]);
+        for (size_t q = 0; q < n_pairs; q++)
+            add(cl, " %.17g", c[q * B + b]);
+        add(cl, "\n");
+    }
+    return write_table("power spectra", ".cl_", cl);
+}
+
+// "Saving the <what> on:" <directory><simulation><token><npix>_<suffix>.txt, then the file; 0, or 1 after the message
+int LensingOutputs::write_table(const char *what, const char *token, const string &text) const
+{
+    const string path = p.directory + p.simulation + token + p.snpix + "_" + p.suffix + ".txt";
+    cout << "Saving the " << what << " on: " << path << endl;
+    FILE *f = fopen(path.c_str(), "w");
+    if (!f) {
+        cerr << "It was not possible to create the file: " << path << endl;
+        return 1;
+    }
+    fputs(text.c_str(), f);
+    if (fclose(f) != 0) {
+        cerr << "It was not possible to write the file: " << path << endl;
+        return 1;
+    }
+    return 0;
+}
+
+}  // namespace slicer_amd

@@ -1,0 +1,123 @@
+// driver_lensing.hpp -- the lensing outputs of the SLICER_amd driver (slicer_main.cpp): their options, their host
+// planning and the device-0 work behind --kappa, --shear, --deflection, --raytrace, --power, --moments and --peaks
+// (driver_lensing.cpp describes the options), with the small helpers the rest of the driver shares with them.
+#pragma once
+#include <string>
+#include <vector>
+
+#include "fits_writer.hpp"
+#include "subfile_deposit.hpp"
+
+namespace slicer_amd {
+
+std::string plane_label(int pll);                    // slicer-v2.cpp:154-159: pll >= 0, zero-padded to three digits
+std::vector<std::string> split(const std::string &s);  // the pieces of s between commas, empty ones included
+
+struct LensingOptions {
+    std::string kappa;  // "" (no lensing output at all), "all" or "z1,z2,..."
+    bool growth = true, shear = false, deflection = false, raytrace = false;
+    std::string shear_derivative;     // "" (not given: fft), "fft" or "gradient"
+    std::string power;                // "", "auto" or "cross"
+    std::vector<double> power_edges;  // empty: the default edges 0 .. npix-1
+    bool moments = false, moments_levels_given = false;
+    int moments_levels = 0;
+    std::vector<double> peaks_edges;  // empty: no --peaks
+
+    bool gradient() const { return shear_derivative == "gradient"; }
+    int n_power_edges(int npix) const { return power_edges.empty() ? npix : (int)power_edges.size(); }
+    const double *power_edges_or_null() const { return power_edges.empty() ? nullptr : power_edges.data(); }
+
+    // argv[i] with its value if it is one of these options: 0, or 2 after the message of a bad value; otherwise -1
+    int parse(int argc, char **argv, int &i);
+    int check() const;                           // against each other: 0, or 2 after the first broken rule's message
+    int check_npix(const InputParams &p) const;  // against the map size, on the host: 0, or 2 after the message
+};
+
+// What the host works out before any device is opened (0, or the exit status after the message).  Without --kappa,
+// zs stays empty.
+struct LensingPlan {
+    std::vector<double> zs, coeff;  // source redshifts; coeff[s * nplanes + i] = c[s][i] (slicer_lensing_weights)
+    // --raytrace (slicer_lensing_plane_strengths): per plane its strength and distance, per source its distance and the
+    // number of planes in front of it
+    std::vector<double> strength, chil, chis;
+    std::vector<int32_t> in_front;
+};
+int plan_lensing(const LensingOptions &o, const InputParams &p, const Header &simdata, const Lens &lens, LensingPlan &plan);
+
+// A sub-handle of the root handle and the call that releases it.
+template <class H, int (*Destroy)(H)>
+struct Owned {
+    H handle = nullptr;
+    Owned() = default;
+    Owned(const Owned &) = delete;
+    Owned &operator=(const Owned &) = delete;
+    ~Owned() { if (handle) Destroy(handle); }
+    operator H() const { return handle; }
+    H *out() { return &handle; }
+};
+
+// npix^2 f32 device buffers of the root handle, freed in the order they were made
+struct DeviceMaps {
+    const slicer_handle h;
+    std::vector<float *> maps{};
+    explicit DeviceMaps(slicer_handle h_) : h(h_) {}
+    DeviceMaps(const DeviceMaps &) = delete;
+    DeviceMaps &operator=(const DeviceMaps &) = delete;
+    ~DeviceMaps()
+    {
+        for (float *b : maps)
+            slicer_device_free(h, b);
+    }
+    bool add(int npix)  // false: slicer_last_error(h) says why
+    {
+        void *b = nullptr;
+        if (slicer_device_malloc(h, (size_t)npix * (size_t)npix * sizeof(float), &b) == SLICER_OK)
+            maps.push_back((float *)b);
+        return b != nullptr;
+    }
+};
+
+// The kappa maps and what is computed from them, on the root handle.  Declared after the Ranks, so that it is released
+// before its parent handle.  The members are in the order of their creation: they are released last to first.
+struct LensingOutputs {
+    const slicer_handle h;
+    const LensingOptions &o;
+    const LensingPlan &plan;
+    const InputParams &p;
+    const Lens &lens;
+    Owned<slicer_kappa_handle, slicer_kappa_destroy> kh{};  // null without --kappa, and then all below are unused
+    Owned<slicer_shear_handle, slicer_shear_destroy> shh{};  // --shear and --raytrace
+    Owned<slicer_power_handle, slicer_power_destroy> ph{};
+    Owned<slicer_moments_handle, slicer_moments_destroy> mh{};
+    Owned<slicer_peaks_handle, slicer_peaks_destroy> pkh{};
+    // --raytrace: a one-source kappa handle that makes a plane's lens map, the rays, their six output buffers, and the
+    // sources in ascending redshift with the position of the next one to observe
+    Owned<slicer_kappa_handle, slicer_kappa_destroy> lkh{};
+    Owned<slicer_rays_handle, slicer_rays_destroy> rh{};
+    DeviceMaps rt_out{h};
+    std::vector<size_t> rt_order{};
+    size_t rt_next = 0;
+    DeviceMaps upload{h};        // planes read back from their files
+    std::vector<float> map{};    // the host copy of the map that save() writes
+    std::string moments{}, peaks{};  // their tables, which write() gathers source by source
+
+    int create();
+    // The planes i0 .. i1-1 of one pass go into the kappa maps as ONE batch whether they were deposited now (their
+    // finalized maps on the root, plane k of `todo`) or read back from the files a previous run left (resume): the
+    // batches, and with them the roundings, are the same in both cases.
+    int add_pass(int i0, int i1, const std::vector<int> &todo);
+    // every file of the finished kappa maps
+    int write();
+
+private:
+    int trace_plane(int i, const float *d_map);
+    int observe_sources(int done);
+    bool save(const char *what, const char *token, size_t s);
+    int source_moments(size_t s, const float *d_kappa);
+    int source_peaks(size_t s, float *d_kappa);
+    int source_shear(size_t s, const float *d_kappa);
+    int power_spectra();
+    int write_table(const char *what, const char *token, const std::string &text) const;
+};
+
+}  // namespace slicer_amd

@@ -28,74 +28,20 @@ def _dptr(a):
     return a.ctypes.data if a is not None else None
 
 
-def plane_weights(omega_m, omega_lambda, w0, fov_deg, npix, ld, ld2, zsnap, sources="all", growth=True, wa=0.0,
-                  physical=False):
-    """c[s, p] of kappa_s = sum_p c[s, p] (m_p - mean m_p), plus the per-plane zlo, zup, zl, chil and the source list.
-
-    ld, ld2: comoving plane edges in Mpc/h (Lens.ld / ld2); zsnap: snapshot redshift of every plane (Lens.zfromsnap);
-    sources: "all" (the far-edge redshift of every plane) or a sequence of source redshifts."""
-    ld = np.ascontiguousarray(ld, np.float64)
-    ld2 = np.ascontiguousarray(ld2, np.float64)
-    zsnap = np.ascontiguousarray(zsnap, np.float64)
-    P = ld.size
-    assert ld2.size == P and zsnap.size == P
-    zs = None if isinstance(sources, str) and sources == "all" else np.ascontiguousarray(sources, np.float64)
-    S = P if zs is None else zs.size
-    coeff = np.zeros((S, P), np.float64)
-    out = {k: np.zeros(P, np.float64) for k in ("zlo", "zup", "zl", "chil")}
-    rc = _L.slicer_lensing_weights(float(omega_m), float(omega_lambda), float(w0), float(wa), float(fov_deg), int(npix),
-                                   int(bool(growth)), int(bool(physical)), P, _dptr(ld), _dptr(ld2), _dptr(zsnap), S,
-                                   _dptr(zs), _dptr(coeff), _dptr(out["zlo"]), _dptr(out["zup"]), _dptr(out["zl"]),
-                                   _dptr(out["chil"]))
+def _host_chk(rc):
+    """Raise the last error of a call that has no handle."""
     if rc:
         raise SlicerError(rc, (_L.slicer_last_error(None) or b"").decode())
-    out["c"] = coeff
-    out["zs"] = out["zup"].copy() if zs is None else zs
-    return out
 
 
-def plane_strengths(omega_m, omega_lambda, w0, fov_deg, npix, ld, ld2, zsnap, sources="all", growth=True, wa=0.0,
-                    physical=False):
-    """The per-plane lensing strengths of the ray tracer (slicer_lensing_plane_strengths), arguments as plane_weights:
-    dict with strength [P] (the lens map of plane p is strength[p] (m_p - mean m_p)), chil [P], zs, chis [S] and
-    n_in_front [S] (the planes in front of every source)."""
-    ld = np.ascontiguousarray(ld, np.float64)
-    ld2 = np.ascontiguousarray(ld2, np.float64)
-    zsnap = np.ascontiguousarray(zsnap, np.float64)
-    P = ld.size
-    assert ld2.size == P and zsnap.size == P
-    zs = None if isinstance(sources, str) and sources == "all" else np.ascontiguousarray(sources, np.float64)
-    S = P if zs is None else zs.size
-    out = {"strength": np.zeros(P, np.float64), "chil": np.zeros(P, np.float64), "chis": np.zeros(S, np.float64),
-           "n_in_front": np.zeros(S, np.int32)}
-    rc = _L.slicer_lensing_plane_strengths(float(omega_m), float(omega_lambda), float(w0), float(wa), float(fov_deg),
-                                           int(npix), int(bool(growth)), int(bool(physical)), P, _dptr(ld), _dptr(ld2),
-                                           _dptr(zsnap), S, _dptr(zs), _dptr(out["strength"]), _dptr(out["chil"]),
-                                           _dptr(out["chis"]), _dptr(out["n_in_front"]))
-    if rc:
-        raise SlicerError(rc, (_L.slicer_last_error(None) or b"").decode())
-    if zs is None:
-        zs = plane_weights(omega_m, omega_lambda, w0, fov_deg, npix, ld, ld2, zsnap, "all", growth, wa, physical)["zs"]
-    out["zs"] = zs
-    return out
-
-
-class Kappa:
-    """n_sources kappa maps of npix^2 pixels accumulated on the device of `slicer`, on its stream."""
-
-    def __init__(self, slicer: Slicer, npix, n_sources):
-        self._s = slicer
-        self.npix, self.n_sources = int(npix), int(n_sources)
-        self.n_added = 0
-        self._dirty = True
-        kh = C.c_void_p()
-        slicer._chk(_L.slicer_kappa_create(slicer._h, self.npix, self.n_sources, C.byref(kh)))
-        self._kh = kh
+class _SubHandle:
+    """A handle made from a Slicer's: the attribute named by _handle holds it, the C call named by _destroy frees it."""
+    _handle = _destroy = None
 
     def close(self):
-        if getattr(self, "_kh", None):
-            _L.slicer_kappa_destroy(self._kh)
-            self._kh = None
+        if getattr(self, self._handle, None):
+            getattr(_L, self._destroy)(getattr(self, self._handle))
+            setattr(self, self._handle, None)
 
     def __del__(self):
         try:
@@ -108,6 +54,84 @@ class Kappa:
 
     def __exit__(self, *a):
         self.close()
+
+
+def _plane_args(ld, ld2, zsnap, sources):
+    """(ld, ld2, zsnap, zs, P, S) as slicer_lensing_* take them; zs is None for sources "all", and then S = P."""
+    ld, ld2, zsnap = (np.ascontiguousarray(a, np.float64) for a in (ld, ld2, zsnap))
+    P = ld.size
+    assert ld2.size == P and zsnap.size == P
+    zs = None if isinstance(sources, str) and sources == "all" else np.ascontiguousarray(sources, np.float64)
+    return ld, ld2, zsnap, zs, P, P if zs is None else zs.size
+
+
+def _read_outputs(slicer, npix, which, count, codes, run):
+    """{code: f32 [npix, npix] array} for the codes 0 .. count-1 in `which`: their device buffers are allocated, filled
+    by run(ptrs) (None where a code is not asked for), copied back and freed."""
+    which = [int(w) for w in which]
+    if any(not 0 <= w < count for w in which):
+        raise ValueError(f"which: {codes} codes 0..{count - 1}")
+    ptrs = [None] * count
+    try:
+        for w in set(which):
+            ptrs[w] = slicer.malloc(4 * npix * npix)
+        run(ptrs)
+        return {w: slicer.to_host(ptrs[w], (npix, npix), np.float32) for w in which}
+    finally:
+        for p in ptrs:
+            if p is not None:
+                slicer.free(p)
+
+
+def plane_weights(omega_m, omega_lambda, w0, fov_deg, npix, ld, ld2, zsnap, sources="all", growth=True, wa=0.0,
+                  physical=False):
+    """c[s, p] of kappa_s = sum_p c[s, p] (m_p - mean m_p), plus the per-plane zlo, zup, zl, chil and the source list.
+
+    ld, ld2: comoving plane edges in Mpc/h (Lens.ld / ld2); zsnap: snapshot redshift of every plane (Lens.zfromsnap);
+    sources: "all" (the far-edge redshift of every plane) or a sequence of source redshifts."""
+    ld, ld2, zsnap, zs, P, S = _plane_args(ld, ld2, zsnap, sources)
+    coeff = np.zeros((S, P), np.float64)
+    out = {k: np.zeros(P, np.float64) for k in ("zlo", "zup", "zl", "chil")}
+    _host_chk(_L.slicer_lensing_weights(float(omega_m), float(omega_lambda), float(w0), float(wa), float(fov_deg),
+                                        int(npix), int(bool(growth)), int(bool(physical)), P, _dptr(ld), _dptr(ld2),
+                                        _dptr(zsnap), S, _dptr(zs), _dptr(coeff), _dptr(out["zlo"]), _dptr(out["zup"]),
+                                        _dptr(out["zl"]), _dptr(out["chil"])))
+    out["c"] = coeff
+    out["zs"] = out["zup"].copy() if zs is None else zs
+    return out
+
+
+def plane_strengths(omega_m, omega_lambda, w0, fov_deg, npix, ld, ld2, zsnap, sources="all", growth=True, wa=0.0,
+                    physical=False):
+    """The per-plane lensing strengths of the ray tracer (slicer_lensing_plane_strengths), arguments as plane_weights:
+    dict with strength [P] (the lens map of plane p is strength[p] (m_p - mean m_p)), chil [P], zs, chis [S] and
+    n_in_front [S] (the planes in front of every source)."""
+    ld, ld2, zsnap, zs, P, S = _plane_args(ld, ld2, zsnap, sources)
+    out = {"strength": np.zeros(P, np.float64), "chil": np.zeros(P, np.float64), "chis": np.zeros(S, np.float64),
+           "n_in_front": np.zeros(S, np.int32)}
+    _host_chk(_L.slicer_lensing_plane_strengths(float(omega_m), float(omega_lambda), float(w0), float(wa),
+                                                float(fov_deg), int(npix), int(bool(growth)), int(bool(physical)), P,
+                                                _dptr(ld), _dptr(ld2), _dptr(zsnap), S, _dptr(zs),
+                                                _dptr(out["strength"]), _dptr(out["chil"]), _dptr(out["chis"]),
+                                                _dptr(out["n_in_front"])))
+    if zs is None:
+        zs = plane_weights(omega_m, omega_lambda, w0, fov_deg, npix, ld, ld2, zsnap, "all", growth, wa, physical)["zs"]
+    out["zs"] = zs
+    return out
+
+
+class Kappa(_SubHandle):
+    """n_sources kappa maps of npix^2 pixels accumulated on the device of `slicer`, on its stream."""
+    _handle, _destroy = "_kh", "slicer_kappa_destroy"
+
+    def __init__(self, slicer: Slicer, npix, n_sources):
+        self._s = slicer
+        self.npix, self.n_sources = int(npix), int(n_sources)
+        self.n_added = 0
+        self._dirty = True
+        kh = C.c_void_p()
+        slicer._chk(_L.slicer_kappa_create(slicer._h, self.npix, self.n_sources, C.byref(kh)))
+        self._kh = kh
 
     def add_device(self, ptrs, coeff):
         """ptrs: device addresses of n_maps f32 maps; coeff: [n_maps][n_sources] weights."""
@@ -164,9 +188,10 @@ def shear_supported(npix):
     return bool(_L.slicer_shear_supported(int(npix)))
 
 
-class Shear:
+class Shear(_SubHandle):
     """Lensing potential phi and shear gamma1, gamma2, |gamma| of npix^2 kappa maps of side angle_deg degrees,
     computed on the device of `slicer`, on its stream.  read / device_map take SHEAR_*."""
+    _handle, _destroy = "_sh", "slicer_shear_destroy"
 
     def __init__(self, slicer: Slicer, npix, angle_deg):
         self._s = slicer
@@ -175,23 +200,6 @@ class Shear:
         slicer._chk(_L.slicer_shear_create(slicer._h, self.npix, self.angle_deg, C.byref(sh)))
         self._sh = sh
         self.last_input = None  # the device address handed to the last run
-
-    def close(self):
-        if getattr(self, "_sh", None):
-            _L.slicer_shear_destroy(self._sh)
-            self._sh = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
     def run(self, d_kappa):
         """d_kappa: device address of an f32 npix^2 map."""
@@ -236,19 +244,8 @@ def fd_run(slicer: Slicer, d_phi, npix, spacing, ptrs):
 def fd_derivatives(slicer: Slicer, d_phi, npix, spacing, which=tuple(range(FD_COUNT))):
     """Finite-difference derivatives of the f32 npix^2 device map at address d_phi, samples
     `spacing` apart: {code: f32 [npix, npix] array} for the FD_* codes in `which`."""
-    which = [int(w) for w in which]
-    if any(not 0 <= w < FD_COUNT for w in which):
-        raise ValueError(f"which: FD_* codes 0..{FD_COUNT - 1}")
-    ptrs = [None] * FD_COUNT
-    try:
-        for w in set(which):
-            ptrs[w] = slicer.malloc(4 * int(npix) * int(npix))
-        fd_run(slicer, d_phi, npix, spacing, ptrs)
-        return {w: slicer.to_host(ptrs[w], (int(npix), int(npix)), np.float32) for w in which}
-    finally:
-        for p in ptrs:
-            if p is not None:
-                slicer.free(p)
+    return _read_outputs(slicer, int(npix), which, FD_COUNT, "FD_*",
+                         lambda ptrs: fd_run(slicer, d_phi, npix, spacing, ptrs))
 
 
 def ell_fundamental(angle_deg):
@@ -277,16 +274,15 @@ def power_bins(npix, edges=None):
     B = max(n_edges - 1, 0)
     counts = np.zeros(B, np.int64)
     mean = np.zeros(B, np.float64)
-    rc = _L.slicer_power_bins(int(npix), n_edges, _dptr(e), counts.ctypes.data, mean.ctypes.data)
-    if rc:
-        raise SlicerError(rc, (_L.slicer_last_error(None) or b"").decode())
+    _host_chk(_L.slicer_power_bins(int(npix), n_edges, _dptr(e), counts.ctypes.data, mean.ctypes.data))
     return {"counts": counts, "mean_radius": mean}
 
 
-class Power:
+class Power(_SubHandle):
     """Binned power spectra C_l of n_maps npix^2 maps of side angle_deg degrees, on the device of `slicer`, on its
     stream.  cross=False: the auto-spectra; cross=True: every pair.  edges in units of
     l_f = 2 pi / theta (None: 0, 1, ..., npix - 1), or ell_edges in multipoles."""
+    _handle, _destroy = "_ph", "slicer_power_destroy"
 
     def __init__(self, slicer: Slicer, npix, angle_deg, n_maps, cross=False, edges=None, ell_edges=None):
         self._s = slicer
@@ -300,23 +296,6 @@ class Power:
         slicer._chk(_L.slicer_power_create(slicer._h, self.npix, self.angle_deg, self.n_maps, int(self.cross), n_edges,
                                            _dptr(e), C.byref(ph)))
         self._ph = ph
-
-    def close(self):
-        if getattr(self, "_ph", None):
-            _L.slicer_power_destroy(self._ph)
-            self._ph = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
     def run(self, ptrs):
         """ptrs: device addresses of the n_maps f32 npix^2 maps."""
@@ -366,15 +345,15 @@ def moments_depth(npix):
     """D(npix): the f64 additions on the longest path of the summation trees of an npix^2 level (the D of the bounds
     in include/slicer_amd.h); host only, no device needed."""
     d = _L.slicer_moments_depth(int(npix))
-    if d < 0:
-        raise SlicerError(2, (_L.slicer_last_error(None) or b"").decode())
+    _host_chk(2 if d < 0 else 0)
     return d
 
 
-class Moments:
+class Moments(_SubHandle):
     """Central moments of orders 2 ... 8 of an npix^2 map and of `levels` successive 2x2 halvings of it, on the device
     of `slicer`, on its stream.  mode "mean" halves to block means (kappa), "sum" to block sums
     (mass planes, Lens/halve.py)."""
+    _handle, _destroy = "_mh", "slicer_moments_destroy"
 
     def __init__(self, slicer: Slicer, npix, levels=0, mode="mean"):
         if mode not in ("mean", "sum"):
@@ -385,23 +364,6 @@ class Moments:
         slicer._chk(_L.slicer_moments_create(slicer._h, self.npix, self.levels, HALVE_SUM if mode == "sum" else HALVE_MEAN,
                                              C.byref(mh)))
         self._mh = mh
-
-    def close(self):
-        if getattr(self, "_mh", None):
-            _L.slicer_moments_destroy(self._mh)
-            self._mh = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
     def run(self, d_map, centres=None):
         """d_map: device address of an f32 npix^2 map; centres: None (every level's own mean) or levels + 1 values,
@@ -463,15 +425,14 @@ def peaks_edges(lo, hi, bins):
     between; host only, no device needed."""
     bins = int(bins)
     e = np.zeros(max(bins, 0) + 1, np.float64)
-    rc = _L.slicer_peaks_edges(float(lo), float(hi), bins, e.ctypes.data)
-    if rc:
-        raise SlicerError(rc, (_L.slicer_last_error(None) or b"").decode())
+    _host_chk(_L.slicer_peaks_edges(float(lo), float(hi), bins, e.ctypes.data))
     return e
 
 
-class Peaks:
+class Peaks(_SubHandle):
     """One-point PDF histogram and the counts of peaks and minima by height of an npix^2 map over the f64 `edges`, on
     the device of `slicer`, on its stream.  Every count is an exact int64."""
+    _handle, _destroy = "_ph", "slicer_peaks_destroy"
 
     def __init__(self, slicer: Slicer, npix, edges):
         self._s = slicer
@@ -481,23 +442,6 @@ class Peaks:
         ph = C.c_void_p()
         slicer._chk(_L.slicer_peaks_create(slicer._h, self.npix, self.edges.size, _dptr(self.edges), C.byref(ph)))
         self._ph = ph
-
-    def close(self):
-        if getattr(self, "_ph", None):
-            _L.slicer_peaks_destroy(self._ph)
-            self._ph = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
     def run(self, d_map, npix=None):
         """d_map: device address of an f32 map of npix^2 pixels (None: the handle's npix; otherwise at most that)."""
@@ -531,10 +475,11 @@ RAYS_COUNT = 6
 RAYS_STATE = ("b1", "b2", "t1", "t2", "A11", "A12", "A21", "A22", "T11", "T12", "T21", "T22")
 
 
-class Rays:
+class Rays(_SubHandle):
     """One ray per pixel of an npix^2 grid of `spacing` radians per pixel, traced through lens planes on the device of
     `slicer`, on its stream.  step takes a plane's five device maps; observe gives the
     distortion (kappa, gamma1, gamma2, omega) and the total deflection at a source distance."""
+    _handle, _destroy = "_rh", "slicer_rays_destroy"
 
     def __init__(self, slicer: Slicer, npix, spacing):
         self._s = slicer
@@ -542,23 +487,6 @@ class Rays:
         rh = C.c_void_p()
         slicer._chk(_L.slicer_rays_create(slicer._h, self.npix, self.spacing, C.byref(rh)))
         self._rh = rh
-
-    def close(self):
-        if getattr(self, "_rh", None):
-            _L.slicer_rays_destroy(self._rh)
-            self._rh = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
 
     def reset(self):
         """Back to the start state."""
@@ -591,19 +519,8 @@ class Rays:
 
     def observe(self, chi_s, which=tuple(range(RAYS_COUNT))):
         """{code: f32 [npix, npix] array} for the RAYS_* codes in `which`, for a source at comoving distance chi_s."""
-        which = [int(w) for w in which]
-        if any(not 0 <= w < RAYS_COUNT for w in which):
-            raise ValueError(f"which: RAYS_* codes 0..{RAYS_COUNT - 1}")
-        ptrs = [None] * RAYS_COUNT
-        try:
-            for w in set(which):
-                ptrs[w] = self._s.malloc(4 * self.npix * self.npix)
-            self.observe_device(chi_s, ptrs)
-            return {w: self._s.to_host(ptrs[w], (self.npix, self.npix), np.float32) for w in which}
-        finally:
-            for p in ptrs:
-                if p is not None:
-                    self._s.free(p)
+        return _read_outputs(self._s, self.npix, which, RAYS_COUNT, "RAYS_*",
+                             lambda ptrs: self.observe_device(chi_s, ptrs))
 
     def state(self):
         """The state, f64 [12, npix, npix] in the order of RAYS_STATE; waits for the stream."""

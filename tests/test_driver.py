@@ -1,4 +1,5 @@
-"""SLICER_amd driver (slicer_amd/csrc/slicer_main.cpp + planner.cpp): planning on CPU, full run on the GPU.
+"""SLICER_amd driver (slicer_amd/csrc/slicer_main.cpp + driver_lensing.cpp + planner.cpp): planning on CPU, full run on
+the GPU.
 
 The planner restates readInput / readRedList / buildPlanes / randomizeBox / testFov (densitymaps.cpp:9-283,
 data.cpp:8-87, gadget2io.cpp:613-661).  GSL is absent, so spline-interpolated values are unpinned against GSL; what
