@@ -598,6 +598,53 @@ int slicer_lensing_plane_strengths(double omega_m, double omega_lambda, double w
                                    const double *ld2, const double *zsnap, int32_t n_sources, const double *zs,
                                    double *strength, double *chil, double *chis, int32_t *n_in_front);
 
+/* ---- Gaussian and aperture-mass smoothing of a map ----
+ * The input is any device f32 map x of npix^2 pixels (row-major), 1 <= npix <= 131072, which is only read; the output is one
+ * f32 map of npix^2 pixels owned by the handle.  Scale s = sigma_pix in pixels (f64, finite, > 0), truncation t (f64,
+ * 1 <= t <= 8).  Radius R = floor(t s + 0.5), the rule of scipy.ndimage.gaussian_filter, 1 <= R <= SLICER_SMOOTH_MAX_RADIUS.
+ * Weights, for k = 0 ... R, in f64, each operation rounded once (RN), no FMA: q_k = RN(RN(k k) / RN(2 RN(s s))),
+ * g_k = exp(-q_k) (libm's), h_k = RN(q_k g_k); g_0 = 1 and h_0 = 0.
+ * Line operator L_w along one axis, for a table w, on f64 values v, samples outside 0 ... npix-1 taken as +0.0:
+ *   acc_0 = RN(w_0 v[i]);  acc_k = RN(acc_{k-1} + RN(w_k RN(v[i-k] + v[i+k])))  for k = 1 ... R, from the centre outwards.
+ * SLICER_SMOOTH_GAUSS: x widened exactly to f64; T = L_g along axis 1 (kept in f64); A = L_g of T along axis 0; N[i] = L_g of
+ *   a line of npix ones; out[i][j] = RN32(RN(A / RN(N[i] N[j]))).  The filter does not wrap: near an edge it is renormalised
+ *   by the weight that fell inside the map, so a constant map stays constant.
+ * SLICER_SMOOTH_MAP: the aperture mass with U(r) = (1 - r^2 / 2 s^2) exp(-r^2 / 2 s^2) / (2 pi s^2), r in pixels (van Waerbeke
+ *   1998), on the grid g x g - h x g - g x h: G = L_g and H = L_h along axis 1; D = RN(G - H); a = L_g of D and b = L_h of G
+ *   along axis 0; c = RN(1 / RN(RN(RN(2 pi) s) s)); out = RN32(RN(c RN(a - b))).  Not renormalised: pixels nearer than R to an
+ *   edge see a truncated aperture (crop by the radius).  The truncated, sampled filter is compensated only approximately
+ *   (DESIGN.md): take t = 5 where that matters.
+ * NaN and +-inf pixels propagate by IEEE through exactly the (2R+1)^2 outputs whose window holds them, clipped to the map;
+ * NaN payloads and the sign of a zero result are not part of the contract.  The same input gives the same bits on every
+ * run; a numpy restatement fed with slicer_smooth_weights reproduces every output value.
+ *   slicer_smooth_weights     host only: the radius and the tables g, h [radius + 1] (any of the three may be NULL).
+ *                             SLICER_ERR_ARG (message through slicer_last_error(NULL)): s or t not finite or out of range,
+ *                             R < 1; SLICER_ERR_UNSUPPORTED: R > 128 (run a wider filter on a level of the moments pyramid)
+ *   slicer_smooth_create      on the device and stream of h (create it after any slicer_set_stream, destroy it before h).
+ *                             The numbers are checked before the handle, so that they can be checked without a device:
+ *                             npix < 1, an unknown kind and the refusals of slicer_smooth_weights; npix > 131072:
+ *                             SLICER_ERR_UNSUPPORTED.  Device memory: 4 bytes a pixel of output, 8 (GAUSS) or 16 (MAP) of
+ *                             f64 intermediate, 8 npix of N and the tables (SLICER_ERR_NOMEM)
+ *   slicer_smooth_run         any device f32 map of the handle's npix^2 pixels; enqueued, no synchronisation.
+ *                             SLICER_ERR_ARG: a NULL map, a map that overlaps the handle's own output (a second handle
+ *                             smooths a smoothed map)
+ *   slicer_smooth_run_npix    the same of a smaller map of npix^2 pixels, 1 <= npix <= the handle's (others:
+ *                             SLICER_ERR_ARG), with the N of that npix; nothing is carried over between runs
+ *   slicer_smooth_device_map  the output of the last run, npix^2 floats of that run, valid until the next run or destroy
+ *   slicer_smooth_read        the same to the host; waits for the stream.  Both before any run: SLICER_ERR_STATE */
+typedef struct slicer_smooth *slicer_smooth_handle;
+#define SLICER_SMOOTH_GAUSS 0
+#define SLICER_SMOOTH_MAP 1
+#define SLICER_SMOOTH_MAX_RADIUS 128
+int slicer_smooth_weights(double sigma_pix, double truncate, int32_t *radius, double *g, double *h);
+int slicer_smooth_create(slicer_handle h, int32_t npix, int32_t kind, double sigma_pix, double truncate,
+                         slicer_smooth_handle *out);
+int slicer_smooth_run(slicer_smooth_handle sh, const float *d_map);
+int slicer_smooth_run_npix(slicer_smooth_handle sh, const float *d_map, int32_t npix);
+int slicer_smooth_device_map(slicer_smooth_handle sh, float **d_out);
+int slicer_smooth_read(slicer_smooth_handle sh, float *out);
+int slicer_smooth_destroy(slicer_smooth_handle sh);
+
 /* per-kernel HIP-event timing (off by default; adds two event records per launch) */
 int slicer_profile_enable(slicer_handle h, int on);
 int slicer_profile_reset(slicer_handle h);

@@ -23,6 +23,12 @@
 //     map and the counts of its peaks and minima by height (strictly above / below all 8 neighbours; the map does not
 //     wrap) over `bins` (1 ... 1024) uniform bins from lo to hi; with --moments also of every level of its pyramid of
 //     block means.
+//   * --smooth gauss|map:a1,a2,...: per source and per scale a_k (arcminutes; sigma = a_k npix / (60 ANGLE) pixels)
+//     the kappa map smoothed with a Gaussian truncated at 4 sigma (gauss) or turned into the aperture mass of the filter
+//     built from it (map), .<kind><k>_kappa_z..., with the kappa file's header and the keys SCALE (arcminutes) and RADIUS
+//     (the filter's reach in pixels: the rim of a map file that saw a truncated aperture).  With --moments and / or
+//     --peaks also .smooth_moments_ and .smooth_peaks_: the tables above of every smoothed map and of its pyramid, with
+//     a leading column `scale` = k.
 #include "driver_lensing.hpp"
 
 #include <algorithm>
@@ -38,6 +44,8 @@ using std::string;
 using std::vector;
 
 namespace slicer_amd {
+
+constexpr double kSmoothTruncate = 4.0;  // --smooth: the filters reach to 4 sigma
 
 string plane_label(int pll)
 {
@@ -115,6 +123,21 @@ int LensingOptions::parse(int argc, char **argv, int &i)
         peaks_edges.resize(bins + 1);
         if (slicer_peaks_edges(lo, hi, (int32_t)bins, peaks_edges.data()) != SLICER_OK)
             return bad(string("bad --peaks: ") + slicer_last_error(nullptr));
+    } else if (a == "--smooth") {
+        const string v = has_value ? argv[++i] : "";
+        const size_t colon = v.find(':');
+        smooth_kind = v.substr(0, colon);
+        smooth_arcmin.clear();
+        for (const string &tok : colon == string::npos ? vector<string>{} : split(v.substr(colon + 1))) {
+            char *end = nullptr;
+            smooth_arcmin.push_back(strtod(tok.c_str(), &end));
+            if (tok.empty() || *end != '\0' || !std::isfinite(smooth_arcmin.back()) || !(smooth_arcmin.back() > 0))
+                smooth_arcmin.clear();
+            if (smooth_arcmin.empty())
+                break;
+        }
+        if ((smooth_kind != "gauss" && smooth_kind != "map") || smooth_arcmin.empty())
+            return bad("bad --smooth (gauss:a1,a2,... or map:a1,a2,...: positive scales in arcminutes)");
     } else
         return -1;
     return 0;
@@ -135,6 +158,7 @@ int LensingOptions::check() const
         {moments && no_kappa, "--moments needs --kappa (the moments are those of the kappa maps)"},
         {moments_levels_given && !moments, "--moments-levels needs --moments"},
         {!peaks_edges.empty() && no_kappa, "--peaks needs --kappa (the histograms and peak counts are those of the kappa maps)"},
+        {!smooth_kind.empty() && no_kappa, "--smooth needs --kappa (the smoothed maps are those of the kappa maps)"},
     };
     for (const auto &[broken, message] : rules)
         if (broken)
@@ -169,6 +193,11 @@ int LensingOptions::check_npix(const InputParams &p) const
             return bad("--moments-levels " + std::to_string(moments_levels) + " is outside 0 ... " + std::to_string(most) +
                        " = floor(log2 npix) for " + npix);
     }
+    if (!smooth_kind.empty() && p.physical)
+        return bad("--smooth: the scales are angles, and the maps of a physical run have none");
+    for (size_t k = 0; k < smooth_arcmin.size(); k++)  // the radius of every scale
+        if (slicer_smooth_weights(smooth_sigma_pix(k, p.npix, p.fov), kSmoothTruncate, nullptr, nullptr, nullptr) != SLICER_OK)
+            return bad("--smooth: scale " + std::to_string(k) + " for " + npix + ": " + slicer_last_error(nullptr));
     return 0;
 }
 
@@ -234,6 +263,14 @@ int LensingOutputs::create()
     if (!o.peaks_edges.empty() &&
         slicer_peaks_create(h, p.npix, (int)o.peaks_edges.size(), o.peaks_edges.data(), pkh.out()) != SLICER_OK)
         return fail(h, "slicer_amd: --peaks");
+    for (size_t k = 0; k < o.smooth_arcmin.size(); k++) {
+        const double sigma = o.smooth_sigma_pix(k, p.npix, p.fov);
+        smooth_radius.push_back(0);
+        if (slicer_smooth_weights(sigma, kSmoothTruncate, &smooth_radius.back(), nullptr, nullptr) != SLICER_OK ||
+            slicer_smooth_create(h, p.npix, o.smooth_kind == "map" ? SLICER_SMOOTH_MAP : SLICER_SMOOTH_GAUSS, sigma,
+                                 kSmoothTruncate, smh.emplace_back().out()) != SLICER_OK)
+            return fail(h, "slicer_amd: --smooth");
+    }
     if (!o.raytrace)
         return 0;
     if (slicer_kappa_create(h, p.npix, 1, lkh.out()) != SLICER_OK ||
@@ -333,21 +370,23 @@ int LensingOutputs::add_pass(int i0, int i1, const vector<int> &todo)
 }
 
 // `map` into <directory><simulation><token><z_s>_<npix>_<suffix>.fits with the keys of kslicer's genericHeader
-bool LensingOutputs::save(const char *what, const char *token, size_t s)
+bool LensingOutputs::save(const char *what, const string &token, size_t s, const vector<FitsKey> &more)
 {
     char z[32];
     snprintf(z, sizeof z, "%.4f", plan.zs[s]);
-    const FitsKey keys[2] = {{"ZSOURCE", false, 0, plan.zs[s], " "}, {"ANGLE", false, 0, p.fov, " "}};
+    vector<FitsKey> keys = {{"ZSOURCE", false, 0, plan.zs[s], " "}, {"ANGLE", false, 0, p.fov, " "}};
+    keys.insert(keys.end(), more.begin(), more.end());
     const string path = p.directory + p.simulation + token + z + "_" + p.snpix + "_" + p.suffix + ".fits";
     cout << "Saving the " << what << " map on: " << path << endl;
-    if (fits_write_image(path, map.data(), p.npix, keys, 2))
+    if (fits_write_image(path, map.data(), p.npix, keys.data(), (int)keys.size()))
         return true;
     cerr << "It was not possible to create the map: " << path << endl;
     return false;
 }
 
 // Per source the kappa file, then its moments, then the histograms of its pyramid (which the moments of the same source
-// left behind), then the shear files; after the sources the three tables.
+// left behind), then the shear files, then the smoothed maps with their moments and histograms; after the sources the
+// tables.
 int LensingOutputs::write()
 {
     if (slicer_kappa_finalize(kh) != SLICER_OK)
@@ -358,41 +397,85 @@ int LensingOutputs::write()
         float *d_kappa = nullptr;
         if (slicer_kappa_device_map(kh, (int)s, &d_kappa) != SLICER_OK)
             return fail(h, "slicer_amd: --kappa");
-        if (const int rc = mh ? source_moments(s, d_kappa) : 0)
+        if (const int rc = mh ? source_moments(s, d_kappa, moments) : 0)
             return rc;
-        if (const int rc = pkh ? source_peaks(s, d_kappa) : 0)
+        if (const int rc = pkh ? source_peaks(s, d_kappa, peaks) : 0)
             return rc;
         if (const int rc = o.shear ? source_shear(s, d_kappa) : 0)
+            return rc;
+        if (const int rc = source_smooth(s, d_kappa))
             return rc;
     }
     if (const int rc = ph ? power_spectra() : 0)
         return rc;
     if (mh && write_table("moments", ".moments_", moments))
         return 1;
-    return pkh ? write_table("histograms and peak counts", ".peaks_", peaks) : 0;
+    if (pkh && write_table("histograms and peak counts", ".peaks_", peaks))
+        return 1;
+    if (mh && !smh.empty() && write_table("moments of the smoothed maps", ".smooth_moments_", smooth_moments))
+        return 1;
+    return pkh && !smh.empty()
+               ? write_table("histograms and peak counts of the smoothed maps", ".smooth_peaks_", smooth_peaks)
+               : 0;
+}
+
+// --smooth: per scale k the smoothed kappa map of source s, .<kind><k>_kappa_z, and its rows of the two tables
+int LensingOutputs::source_smooth(size_t s, const float *d_kappa)
+{
+    if (smh.empty())
+        return 0;
+    string head;  // of both tables
+    add(head, "# smooth %s\n# scales_arcmin", o.smooth_kind.c_str());
+    for (double a : o.smooth_arcmin)
+        add(head, " %.17g", a);
+    add(head, "\n# sigma_pix");
+    for (size_t k = 0; k < smh.size(); k++)
+        add(head, " %.17g", o.smooth_sigma_pix(k, p.npix, p.fov));
+    add(head, "\n# radius");
+    for (int32_t r : smooth_radius)
+        add(head, " %d", (int)r);
+    add(head, "\n");
+    for (size_t k = 0; k < smh.size(); k++) {
+        float *d_smooth = nullptr;
+        if (slicer_smooth_run(smh[k], d_kappa) != SLICER_OK || slicer_smooth_read(smh[k], map.data()) != SLICER_OK ||
+            slicer_smooth_device_map(smh[k], &d_smooth) != SLICER_OK)
+            return fail(h, "slicer_amd: --smooth");
+        const vector<FitsKey> keys = {{"SCALE", false, 0, o.smooth_arcmin[k], " "}, {"RADIUS", true, smooth_radius[k], 0.0, " "}};
+        if (!save("smoothed convergence", "." + o.smooth_kind + std::to_string(k) + "_kappa_z", s, keys))
+            return fail(h, "slicer_amd: --smooth");
+        if (const int rc = mh ? source_moments(s, d_smooth, smooth_moments, head, (int)k) : 0)
+            return rc;
+        if (const int rc = pkh ? source_peaks(s, d_smooth, smooth_peaks, head, (int)k) : 0)
+            return rc;
+    }
+    return 0;
 }
 
 // The moments table: '#' lines (npix, angle, levels, column names), then per (source, level) z level npix mean S2 ... S8
-// (%.17g): the raw sums about the level's own mean
-int LensingOutputs::source_moments(size_t s, const float *d_kappa)
+// (%.17g): the raw sums about the level's own mean.  The table of the smoothed maps: `head` before the column names, and
+// the scale's index in front of every row.
+int LensingOutputs::source_moments(size_t s, const float *d_map, string &text, const string &head, int scale)
 {
+    const string lead = scale < 0 ? "" : std::to_string(scale) + " ";
     const int nlev = o.moments_levels + 1;
     vector<int32_t> npix(nlev);
     vector<double> mean(nlev), sums(nlev * SLICER_MOMENTS_ORDERS);
-    if (slicer_moments_run(mh, d_kappa, nullptr) != SLICER_OK ||
+    if (slicer_moments_run(mh, d_map, nullptr) != SLICER_OK ||
         slicer_moments_read(mh, npix.data(), mean.data(), nullptr, sums.data()) != SLICER_OK)
         return fail(h, "slicer_amd: --moments");
-    if (s == 0) {
-        add(moments, "# npix %d\n# angle_deg %.17g\n# levels %d\n# z level npix mean", p.npix, p.fov, o.moments_levels);
+    if (text.empty()) {
+        add(text, "# npix %d\n# angle_deg %.17g\n# levels %d\n", p.npix, p.fov, o.moments_levels);
+        text += head + (scale < 0 ? "# z level npix mean" : "# scale z level npix mean");
         for (int k = 2; k < 2 + SLICER_MOMENTS_ORDERS; k++)
-            add(moments, " S%d", k);
-        add(moments, "\n");
+            add(text, " S%d", k);
+        add(text, "\n");
     }
     for (int l = 0; l < nlev; l++) {
-        add(moments, "%.17g %d %d %.17g", plan.zs[s], l, (int)npix[l], mean[l]);
+        text += lead;
+        add(text, "%.17g %d %d %.17g", plan.zs[s], l, (int)npix[l], mean[l]);
         for (int k = 0; k < SLICER_MOMENTS_ORDERS; k++)
-            add(moments, " %.17g", sums[l * SLICER_MOMENTS_ORDERS + k]);
-        add(moments, "\n");
+            add(text, " %.17g", sums[l * SLICER_MOMENTS_ORDERS + k]);
+        add(text, "\n");
     }
     return 0;
 }
@@ -400,27 +483,29 @@ int LensingOutputs::source_moments(size_t s, const float *d_kappa)
 // The histogram table: '#' lines (npix, angle, levels, the edges, column names), then per (source, level) one row per
 // bin: -1 (below the first edge), 0 ... B-1, B (above the last), B+1 (NaN pixels).  The levels are those of the pyramid
 // that the moments of this source left behind (level 0 alone without --moments).
-int LensingOutputs::source_peaks(size_t s, float *d_kappa)
+int LensingOutputs::source_peaks(size_t s, float *d_map, string &text, const string &head, int scale)
 {
+    const string lead = scale < 0 ? "" : std::to_string(scale) + " ";
     const vector<double> &e = o.peaks_edges;
     const int B = (int)e.size() - 1, levels = mh ? o.moments_levels : 0;
     vector<int64_t> c(3 * B + 7);  // pdf, peaks, minima [B]; below, above [3]; nan
     const int64_t *below = &c[3 * B], *above = below + 3;
-    if (s == 0) {
-        add(peaks, "# npix %d\n# angle_deg %.17g\n# levels %d\n# edges", p.npix, p.fov, levels);
+    if (text.empty()) {
+        add(text, "# npix %d\n# angle_deg %.17g\n# levels %d\n# edges", p.npix, p.fov, levels);
         for (double v : e)
-            add(peaks, " %.17g", v);
-        add(peaks, "\n# z level npix bin lo hi n_pixels n_peaks n_minima\n");
+            add(text, " %.17g", v);
+        text += "\n" + head + (scale < 0 ? "# " : "# scale ") + "z level npix bin lo hi n_pixels n_peaks n_minima\n";
     }
     for (int l = 0; l <= levels; l++) {
-        float *d_level = d_kappa;
+        float *d_level = d_map;
         if (l > 0 && slicer_moments_device_map(mh, l, &d_level) != SLICER_OK)
             return fail(h, "slicer_amd: --peaks");
         if (slicer_peaks_run_npix(pkh, d_level, p.npix >> l) != SLICER_OK ||
             slicer_peaks_read(pkh, &c[0], &c[B], &c[2 * B], &c[3 * B], &c[3 * B + 3], &c[3 * B + 6]) != SLICER_OK)
             return fail(h, "slicer_amd: --peaks");
         const auto row = [&](int bin, double lo, double hi, int64_t n_pixels, int64_t n_peaks, int64_t n_minima) {
-            add(peaks, "%.17g %d %d %d %.17g %.17g %lld %lld %lld\n", plan.zs[s], l, p.npix >> l, bin, lo, hi,
+            text += lead;
+            add(text, "%.17g %d %d %d %.17g %.17g %lld %lld %lld\n", plan.zs[s], l, p.npix >> l, bin, lo, hi,
                 (long long)n_pixels, (long long)n_peaks, (long long)n_minima);
         };
         row(-1, -INFINITY, e[0], below[0], below[1], below[2]);

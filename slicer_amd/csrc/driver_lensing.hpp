@@ -1,7 +1,8 @@
 // driver_lensing.hpp -- the lensing outputs of the SLICER_amd driver (slicer_main.cpp): their options, their host
-// planning and the device-0 work behind --kappa, --shear, --deflection, --raytrace, --power, --moments and --peaks
-// (driver_lensing.cpp describes the options), with the small helpers the rest of the driver shares with them.
+// planning and the device-0 work behind --kappa, --shear, --deflection, --raytrace, --power, --moments, --peaks and
+// --smooth (driver_lensing.cpp describes the options), with the small helpers the rest of the driver shares with them.
 #pragma once
+#include <deque>
 #include <string>
 #include <vector>
 
@@ -22,10 +23,14 @@ struct LensingOptions {
     bool moments = false, moments_levels_given = false;
     int moments_levels = 0;
     std::vector<double> peaks_edges;  // empty: no --peaks
+    std::string smooth_kind;             // "" (no --smooth), "gauss" or "map"
+    std::vector<double> smooth_arcmin;   // its scales
 
     bool gradient() const { return shear_derivative == "gradient"; }
     int n_power_edges(int npix) const { return power_edges.empty() ? npix : (int)power_edges.size(); }
     const double *power_edges_or_null() const { return power_edges.empty() ? nullptr : power_edges.data(); }
+    // scale k of --smooth in pixels of a map of npix pixels and angle_deg degrees a side
+    double smooth_sigma_pix(size_t k, int npix, double angle_deg) const { return smooth_arcmin[k] * npix / (60.0 * angle_deg); }
 
     // argv[i] with its value if it is one of these options: 0, or 2 after the message of a bad value; otherwise -1
     int parse(int argc, char **argv, int &i);
@@ -90,6 +95,8 @@ struct LensingOutputs {
     Owned<slicer_power_handle, slicer_power_destroy> ph{};
     Owned<slicer_moments_handle, slicer_moments_destroy> mh{};
     Owned<slicer_peaks_handle, slicer_peaks_destroy> pkh{};
+    std::deque<Owned<slicer_smooth_handle, slicer_smooth_destroy>> smh{};  // --smooth: one per scale
+    std::vector<int32_t> smooth_radius{};
     // --raytrace: a one-source kappa handle that makes a plane's lens map, the rays, their six output buffers, and the
     // sources in ascending redshift with the position of the next one to observe
     Owned<slicer_kappa_handle, slicer_kappa_destroy> lkh{};
@@ -100,6 +107,7 @@ struct LensingOutputs {
     DeviceMaps upload{h};        // planes read back from their files
     std::vector<float> map{};    // the host copy of the map that save() writes
     std::string moments{}, peaks{};  // their tables, which write() gathers source by source
+    std::string smooth_moments{}, smooth_peaks{};  // the same of the smoothed maps, scale by scale
 
     int create();
     // The planes i0 .. i1-1 of one pass go into the kappa maps as ONE batch whether they were deposited now (their
@@ -112,9 +120,12 @@ struct LensingOutputs {
 private:
     int trace_plane(int i, const float *d_map);
     int observe_sources(int done);
-    bool save(const char *what, const char *token, size_t s);
-    int source_moments(size_t s, const float *d_kappa);
-    int source_peaks(size_t s, float *d_kappa);
+    bool save(const char *what, const std::string &token, size_t s, const std::vector<FitsKey> &more = {});
+    // The rows of source s for the map at d_map onto the end of `text`, led by its '#' lines while it is empty.
+    // Smoothed maps: `head` goes between the '#' lines and the column names, `scale` (>= 0) in front of every row.
+    int source_moments(size_t s, const float *d_map, std::string &text, const std::string &head = "", int scale = -1);
+    int source_peaks(size_t s, float *d_map, std::string &text, const std::string &head = "", int scale = -1);
+    int source_smooth(size_t s, const float *d_kappa);
     int source_shear(size_t s, const float *d_kappa);
     int power_spectra();
     int write_table(const char *what, const char *token, const std::string &text) const;

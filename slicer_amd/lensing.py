@@ -2,7 +2,7 @@
 potential maps from them (row N6), the binned auto and cross power spectra of such maps (row N7), the deflection
 maps and finite-difference derivatives of the potential (row N8), and the central moments of such maps over a pyramid
 of 2x2 halvings (row N9), and the one-point PDF histogram and peak / minimum counts of such maps (row N10), and
-multi-plane ray tracing through the lens planes (row N11).
+multi-plane ray tracing through the lens planes (row N11), and Gaussian and aperture-mass smoothing of such maps (row N12).
 
 plane_weights wraps the host weights of include/slicer_amd.h (slicer_lensing_weights); Kappa is the device accumulator
 (slicer_kappa_*) bound to a Slicer handle: it reads the finalized plane maps where they are, in HBM.  Shear (slicer_shear_*)
@@ -11,7 +11,8 @@ turns one kappa map into phi, gamma1, gamma2 and |gamma| on the same device, and
 map); Power (slicer_power_*) bins the spectra of several of them into C_l; Moments (slicer_moments_*) halves a map
 level by level and sums the powers 2 ... 8 of every level's pixels about a centre; Peaks (slicer_peaks_*) counts a
 map's pixels, peaks and minima by height over a list of edges; Rays (slicer_rays_*) shoots one ray per pixel through
-the planes' deflection, convergence and shear maps (plane_strengths scales a mass plane to its lens map).
+the planes' deflection, convergence and shear maps (plane_strengths scales a mass plane to its lens map); Smooth
+(slicer_smooth_*) filters a map with a truncated Gaussian or with the aperture-mass filter built from it.
 """
 import ctypes as C
 import math
@@ -468,6 +469,71 @@ class Peaks(_SubHandle):
                                           below.ctypes.data, above.ctypes.data, nan.ctypes.data))
         return {"edges": self.edges.copy(), "pdf": pdf, "peaks": peaks, "minima": minima, "below": below, "above": above,
                 "nan": int(nan[0])}
+
+
+SMOOTH_GAUSS, SMOOTH_MAP = 0, 1
+SMOOTH_MAX_RADIUS = 128
+_SMOOTH_KINDS = {"gauss": SMOOTH_GAUSS, "map": SMOOTH_MAP}
+
+
+def smooth_weights(sigma_pix, truncate=4.0):
+    """(R, g, h) as slicer_smooth_weights makes them: the radius floor(truncate sigma_pix + 0.5) and the f64 tables
+    g_k = exp(-q_k), h_k = q_k g_k, q_k = k^2 / (2 sigma_pix^2), k = 0 ... R; host only, no device needed."""
+    R = C.c_int32()
+    _host_chk(_L.slicer_smooth_weights(float(sigma_pix), float(truncate), C.byref(R), None, None))
+    g, h = np.empty(R.value + 1, np.float64), np.empty(R.value + 1, np.float64)
+    _host_chk(_L.slicer_smooth_weights(float(sigma_pix), float(truncate), None, g.ctypes.data, h.ctypes.data))
+    return R.value, g, h
+
+
+class Smooth(_SubHandle):
+    """An npix^2 map filtered with a Gaussian of sigma_pix pixels truncated at `truncate` sigma and renormalised at the
+    map's edges (kind "gauss"), or with the aperture-mass filter (1 - r^2 / 2 s^2) exp(-r^2 / 2 s^2) / (2 pi s^2) built
+    from it (kind "map"), on the device of `slicer`, on its stream (DESIGN.md S8 row N12).  The map does not wrap;
+    radius is the filter's reach in pixels."""
+    _handle, _destroy = "_sh", "slicer_smooth_destroy"
+
+    def __init__(self, slicer: Slicer, npix, kind="gauss", sigma_pix=1.0, truncate=4.0):
+        if kind not in _SMOOTH_KINDS:
+            raise ValueError('kind: "gauss" or "map"')
+        self._s = slicer
+        self.npix, self.kind, self.sigma_pix, self.truncate = int(npix), kind, float(sigma_pix), float(truncate)
+        self.last_npix = None  # of the last run
+        sh = C.c_void_p()
+        slicer._chk(_L.slicer_smooth_create(slicer._h, self.npix, _SMOOTH_KINDS[kind], self.sigma_pix, self.truncate,
+                                            C.byref(sh)))
+        self._sh = sh
+        self.radius = smooth_weights(self.sigma_pix, self.truncate)[0]
+
+    def run(self, d_map, npix=None):
+        """d_map: device address of an f32 map of npix^2 pixels (None: the handle's npix; otherwise at most that)."""
+        d = None if d_map is None else int(d_map)
+        if npix is None:
+            self._s._chk(_L.slicer_smooth_run(self._sh, d))
+        else:
+            self._s._chk(_L.slicer_smooth_run_npix(self._sh, d, int(npix)))
+        self.last_npix = self.npix if npix is None else int(npix)
+
+    def run_kappa(self, kappa: Kappa, s):
+        """The map of source s of a Kappa accumulator, where it is."""
+        self.run(kappa.device_map(s), kappa.npix)
+
+    def run_level(self, moments: Moments, level):
+        """Level `level` >= 1 of the last run of a Moments pyramid, where it is (level 0 is the caller's own map)."""
+        self.run(moments.device_map(level), moments.npix >> int(level))
+
+    def device_map(self):
+        """Device address of the last run's output, f32 [n, n] for the n of that run."""
+        p = C.c_void_p()
+        self._s._chk(_L.slicer_smooth_device_map(self._sh, C.byref(p)))
+        return p.value
+
+    def read(self):
+        """The last run's output, f32 [n, n] for the n of that run; waits for the stream."""
+        n = self.last_npix or 1
+        out = np.empty((n, n), np.float32)
+        self._s._chk(_L.slicer_smooth_read(self._sh, out.ctypes.data))
+        return out
 
 
 RAYS_KAPPA, RAYS_GAMMA1, RAYS_GAMMA2, RAYS_OMEGA, RAYS_DEFLECTION1, RAYS_DEFLECTION2 = range(6)
