@@ -645,6 +645,62 @@ int slicer_smooth_device_map(slicer_smooth_handle sh, float **d_out);
 int slicer_smooth_read(slicer_smooth_handle sh, float *out);
 int slicer_smooth_destroy(slicer_smooth_handle sh);
 
+/* ---- shape noise for a map, counter-based ----
+ * Generator: Philox4x32-10 (Salmon et al. 2011): multipliers M0 = 0xD2511F53, M1 = 0xCD9E8D57, Weyl key increments
+ * 0x9E3779B9, 0xBB67AE85, ten rounds, the key bumped between rounds; a round maps (c0, c1, c2, c3) to
+ * (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)).
+ * Addressing: a map is a flat array of npix^2 f32 values, p = i npix + j; block b (u64) is the pixels 4 b ... 4 b + 3 of the
+ * flat index (blocks straddle rows when 4 does not divide npix) and draws once: counter (b & 0xffffffff, b >> 32, realisation,
+ * stream), key (seed & 0xffffffff, seed >> 32) -> words w0 ... w3.  The value at a pixel depends on (seed, stream,
+ * realisation, p) and on nothing else.
+ * Normals, all in f64: u(w) = (w + 0.5) 2^-32, exact and inside (0, 1); R_a = sqrt(-2 log u(w0)), R_b = sqrt(-2 log u(w2));
+ * z0 = R_a cospi(2 u(w1)), z1 = R_a sinpi(2 u(w1)), z2 = R_b cospi(2 u(w3)), z3 = R_b sinpi(2 u(w3)); 2 u is exact, so
+ * the argument reduction is; |z| <= 6.77.
+ * Output: out[p] = RN32(RN64(x[p] + RN64(sigma z))), x widened exactly, no FMA; x == NULL (pure noise): RN32(RN64(sigma z)).
+ * z is never rounded to f32 on its own.  The words are exact, the same bits on the host and on the device.  log and sincospi
+ * are not correctly rounded, so the values carry a bound, against ref evaluated exactly from the same words:
+ *   |out - ref| <= 2^-24 |ref| (1 + 2^-20) + 8 2^-53 sigma R,  R the sample's own R_a or R_b   (DESIGN.md counts the 8).
+ * Bitwise: two runs are equal; both load paths; any partition of a map into run_at pieces is one run; a smaller run_npix map
+ * is the first npix^2 flat values of a larger one; sigma = 0 returns x as values; NaN and +-inf in x stay in their own pixel.
+ *   slicer_noise_words          host only: the four words of one block
+ *   slicer_noise_sigma_pix      host only: sigma_pix = sigma_e / sqrt(n_gal A_pix), A_pix = (60 angle_deg / npix)^2 arcmin^2,
+ *                               in f64 as RN(sigma_e / sqrt(RN(n_gal RN(side side)))), side = RN(RN(60 angle_deg) / npix).
+ *                               sigma_e is the ellipticity dispersion PER COMPONENT (the total dispersion of both components
+ *                               is sqrt(2) times it); n_gal per arcmin^2.  SLICER_ERR_ARG: a non-finite or non-positive argument
+ *   slicer_smooth_noise_gain    host only: the rms of slicer_smooth_*'s output for white noise of unit variance, at a pixel at
+ *                               least the radius away from every edge, in long double from slicer_smooth_weights' tables:
+ *                               GAUSS sum g^2 / (sum g)^2, MAP c sqrt(sum_ij (g_i g_j - h_i g_j - g_i h_j)^2), sums over
+ *                               -R ... R.  sigma_smoothed = sigma_pix gain.  Refusals: those of slicer_smooth_weights
+ *   slicer_noise_create         on the device and stream of h (create it after any slicer_set_stream, destroy it before h);
+ *                               one f32 npix^2 output owned by the handle.  The numbers are checked before the handle:
+ *                               npix < 1 SLICER_ERR_ARG, npix > 131072 SLICER_ERR_UNSUPPORTED
+ *   slicer_noise_run            d_map: any device f32 map of the handle's npix^2 pixels, or NULL; enqueued, no synchronisation.
+ *                               d_map may be the handle's own output (a second layer of noise); any other overlap with it:
+ *                               SLICER_ERR_ARG.  sigma finite and >= 0 (checked before the handle)
+ *   slicer_noise_run_npix       the same of a smaller map, 1 <= npix <= the handle's
+ *   slicer_noise_run_at         the 1-D form the other two call: pixels first_pixel ... first_pixel + count - 1 of the flat
+ *                               index, first_pixel a multiple of 4 (any u64), 1 <= count <= the handle's npix^2; d_map[0] and
+ *                               the output's first value both are pixel first_pixel
+ *   slicer_noise_words_device   the words of blocks first_block ... first_block + n_blocks - 1 (1 <= n_blocks <= 2^32) into the
+ *                               device buffer d_out, 4 words per block
+ *   slicer_noise_device_map     the output of the last run (its count of floats), valid until the next run or destroy
+ *   slicer_noise_read           the same to the host; waits for the stream.  Both before any run: SLICER_ERR_STATE */
+typedef struct slicer_noise *slicer_noise_handle;
+int slicer_noise_words(uint64_t seed, uint32_t stream, uint32_t realisation, uint64_t block, uint32_t out[4]);
+int slicer_noise_sigma_pix(double sigma_e, double ngal_arcmin2, double angle_deg, int32_t npix, double *sigma_pix);
+int slicer_smooth_noise_gain(int32_t kind, double sigma_pix, double truncate, double *gain);
+int slicer_noise_create(slicer_handle h, int32_t npix, uint64_t seed, slicer_noise_handle *out);
+int slicer_noise_run(slicer_noise_handle nh, const float *d_map, double sigma, uint32_t stream, uint32_t realisation);
+int slicer_noise_run_npix(slicer_noise_handle nh, const float *d_map, int32_t npix, double sigma, uint32_t stream,
+                          uint32_t realisation);
+int slicer_noise_run_at(slicer_noise_handle nh, const float *d_map, uint64_t first_pixel, uint64_t count, double sigma,
+                        uint32_t stream, uint32_t realisation);
+int slicer_noise_words_device(slicer_noise_handle nh, uint64_t first_block, uint64_t n_blocks, uint32_t stream,
+                              uint32_t realisation, uint32_t *d_out);
+int slicer_noise_device_map(slicer_noise_handle nh, float **d_out);
+int slicer_noise_read(slicer_noise_handle nh, float *out);
+int slicer_noise_destroy(slicer_noise_handle nh);
+
 /* per-kernel HIP-event timing (off by default; adds two event records per launch) */
 int slicer_profile_enable(slicer_handle h, int on);
 int slicer_profile_reset(slicer_handle h);

@@ -126,6 +126,17 @@ SYMBOLS = {
     "slicer_smooth_device_map": (C.c_int, [_H, C.POINTER(C.c_void_p)]),
     "slicer_smooth_read": (C.c_int, [_H, C.c_void_p]),
     "slicer_smooth_destroy": (C.c_int, [_H]),
+    "slicer_noise_words": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p]),
+    "slicer_noise_sigma_pix": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_int32, C.POINTER(C.c_double)]),
+    "slicer_smooth_noise_gain": (C.c_int, [C.c_int32, C.c_double, C.c_double, C.POINTER(C.c_double)]),
+    "slicer_noise_create": (C.c_int, [_H, C.c_int32, C.c_uint64, C.POINTER(C.c_void_p)]),
+    "slicer_noise_run": (C.c_int, [_H, C.c_void_p, C.c_double, C.c_uint32, C.c_uint32]),
+    "slicer_noise_run_npix": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_double, C.c_uint32, C.c_uint32]),
+    "slicer_noise_run_at": (C.c_int, [_H, C.c_void_p, C.c_uint64, C.c_uint64, C.c_double, C.c_uint32, C.c_uint32]),
+    "slicer_noise_words_device": (C.c_int, [_H, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "slicer_noise_device_map": (C.c_int, [_H, C.POINTER(C.c_void_p)]),
+    "slicer_noise_read": (C.c_int, [_H, C.c_void_p]),
+    "slicer_noise_destroy": (C.c_int, [_H]),
     "slicer_rays_create": (C.c_int, [_H, C.c_int32, C.c_double, C.POINTER(C.c_void_p)]),
     "slicer_rays_reset": (C.c_int, [_H]),
     "slicer_rays_step": (C.c_int, [_H, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -29,11 +29,24 @@
 //     (the filter's reach in pixels: the rim of a map file that saw a truncated aperture).  With --moments and / or
 //     --peaks also .smooth_moments_ and .smooth_peaks_: the tables above of every smoothed map and of its pyramid, with
 //     a leading column `scale` = k.
+//   * --shape-noise sigma_e,ngal[,seed[,nreal]]: per source and per realisation r = 0 ... nreal-1 (1 ... 1024, default 1)
+//     the kappa map plus white Gaussian shape noise of sigma_pix = sigma_e / sqrt(ngal A_pix) a pixel (sigma_e per
+//     ellipticity component, ngal per arcmin^2, A_pix the pixel's area in arcmin^2), .noisy<r>_kappa_z..., with the kappa
+//     file's header and the keys SIGMAE, NGAL, SIGMAPIX, SEED, REALIS.  The noise is a pure function of (seed, the
+//     source's rank in ascending redshift, r, pixel): counter-based, so the same on every run, rank count and order of
+//     the --kappa list.  With --moments and / or --peaks also .noisy_moments_ and .noisy_peaks_ (a leading column
+//     `real`).  With --smooth every scale of the NOISY map, .noisy<r>_<kind><k>_kappa_z..., with the keys above, SCALE,
+//     RADIUS and NOISESIG = sigma_pix times the filter's gain on white noise (the sigma that signal-to-noise heights are
+//     in units of), and the tables .noisy_smooth_moments_ and .noisy_smooth_peaks_ (leading columns `real scale`, a
+//     '# noise_sigma' line of the per-scale NOISESIG).  Refused for physical runs, whose pixels have no angle (DESIGN.md
+//     S8 row N13).
 #include "driver_lensing.hpp"
 
 #include <algorithm>
+#include <cerrno>
 #include <cmath>
 #include <cstdarg>
+#include <cstdint>
 #include <iostream>
 #include <numeric>
 
@@ -138,6 +151,28 @@ int LensingOptions::parse(int argc, char **argv, int &i)
         }
         if ((smooth_kind != "gauss" && smooth_kind != "map") || smooth_arcmin.empty())
             return bad("bad --smooth (gauss:a1,a2,... or map:a1,a2,...: positive scales in arcminutes)");
+    } else if (a == "--shape-noise") {
+        const vector<string> tok = has_value ? split(argv[++i]) : vector<string>{};
+        const char *usage = "bad --shape-noise (sigma_e,ngal[,seed[,nreal]]: the ellipticity dispersion per component and the "
+                            "galaxies per arcmin^2, both positive; seed 0 ... 2^63-1; nreal 1 ... 1024)";
+        if (tok.size() < 2 || tok.size() > 4)
+            return bad(usage);
+        for (const string &t : tok)
+            if (t.empty() || t[0] == '-' || t[0] == '+' || isspace((unsigned char)t[0]))
+                return bad(usage);
+        char *e0 = nullptr, *e1 = nullptr, *e2 = nullptr, *e3 = nullptr;
+        noise_sigma_e = strtod(tok[0].c_str(), &e0);
+        noise_ngal = strtod(tok[1].c_str(), &e1);
+        errno = 0;
+        const unsigned long long seed = tok.size() > 2 ? strtoull(tok[2].c_str(), &e2, 10) : 0;
+        const bool seed_ok = tok.size() <= 2 || (*e2 == '\0' && errno == 0 && seed <= (unsigned long long)INT64_MAX);
+        const long nreal = tok.size() > 3 ? strtol(tok[3].c_str(), &e3, 10) : 1;
+        if (*e0 != '\0' || *e1 != '\0' || !seed_ok || (tok.size() > 3 && *e3 != '\0') || nreal < 1 || nreal > 1024 ||
+            !std::isfinite(noise_sigma_e) || !(noise_sigma_e > 0) || !std::isfinite(noise_ngal) || !(noise_ngal > 0))
+            return bad(usage);
+        noise_seed = seed;
+        noise_nreal = (int)nreal;
+        shape_noise = true;
     } else
         return -1;
     return 0;
@@ -159,6 +194,7 @@ int LensingOptions::check() const
         {moments_levels_given && !moments, "--moments-levels needs --moments"},
         {!peaks_edges.empty() && no_kappa, "--peaks needs --kappa (the histograms and peak counts are those of the kappa maps)"},
         {!smooth_kind.empty() && no_kappa, "--smooth needs --kappa (the smoothed maps are those of the kappa maps)"},
+        {shape_noise && no_kappa, "--shape-noise needs --kappa (the noise is added to the kappa maps)"},
     };
     for (const auto &[broken, message] : rules)
         if (broken)
@@ -198,6 +234,11 @@ int LensingOptions::check_npix(const InputParams &p) const
     for (size_t k = 0; k < smooth_arcmin.size(); k++)  // the radius of every scale
         if (slicer_smooth_weights(smooth_sigma_pix(k, p.npix, p.fov), kSmoothTruncate, nullptr, nullptr, nullptr) != SLICER_OK)
             return bad("--smooth: scale " + std::to_string(k) + " for " + npix + ": " + slicer_last_error(nullptr));
+    if (shape_noise && p.physical)
+        return bad("--shape-noise: the galaxy density is per angle, and the pixels of a physical run have none");
+    double sigma_pix = 0.0;
+    if (shape_noise && slicer_noise_sigma_pix(noise_sigma_e, noise_ngal, p.fov, p.npix, &sigma_pix) != SLICER_OK)
+        return bad("--shape-noise: " + npix + ": " + slicer_last_error(nullptr));
     return 0;
 }
 
@@ -270,6 +311,19 @@ int LensingOutputs::create()
             slicer_smooth_create(h, p.npix, o.smooth_kind == "map" ? SLICER_SMOOTH_MAP : SLICER_SMOOTH_GAUSS, sigma,
                                  kSmoothTruncate, smh.emplace_back().out()) != SLICER_OK)
             return fail(h, "slicer_amd: --smooth");
+    }
+    if (o.shape_noise) {
+        if (slicer_noise_sigma_pix(o.noise_sigma_e, o.noise_ngal, p.fov, p.npix, &noise_sigma_pix) != SLICER_OK ||
+            slicer_noise_create(h, p.npix, o.noise_seed, nh.out()) != SLICER_OK)
+            return fail(h, "slicer_amd: --shape-noise");
+        for (size_t k = 0; k < o.smooth_arcmin.size(); k++) {
+            noise_gain.push_back(0.0);
+            if (slicer_smooth_noise_gain(o.smooth_kind == "map" ? SLICER_SMOOTH_MAP : SLICER_SMOOTH_GAUSS,
+                                         o.smooth_sigma_pix(k, p.npix, p.fov), kSmoothTruncate, &noise_gain.back()) != SLICER_OK)
+                return fail(h, "slicer_amd: --shape-noise");
+        }
+        for (double z : zs)  // (sources at one redshift share their stream, and with it their noise)
+            noise_stream.push_back((uint32_t)std::count_if(zs.begin(), zs.end(), [z](double other) { return other < z; }));
     }
     if (!o.raytrace)
         return 0;
@@ -385,8 +439,8 @@ bool LensingOutputs::save(const char *what, const string &token, size_t s, const
 }
 
 // Per source the kappa file, then its moments, then the histograms of its pyramid (which the moments of the same source
-// left behind), then the shear files, then the smoothed maps with their moments and histograms; after the sources the
-// tables.
+// left behind), then the shear files, then the smoothed maps with their moments and histograms, then the noisy maps with
+// theirs; after the sources the tables.
 int LensingOutputs::write()
 {
     if (slicer_kappa_finalize(kh) != SLICER_OK)
@@ -405,6 +459,8 @@ int LensingOutputs::write()
             return rc;
         if (const int rc = source_smooth(s, d_kappa))
             return rc;
+        if (const int rc = nh ? source_noise(s, d_kappa) : 0)
+            return rc;
     }
     if (const int rc = ph ? power_spectra() : 0)
         return rc;
@@ -414,17 +470,24 @@ int LensingOutputs::write()
         return 1;
     if (mh && !smh.empty() && write_table("moments of the smoothed maps", ".smooth_moments_", smooth_moments))
         return 1;
-    return pkh && !smh.empty()
-               ? write_table("histograms and peak counts of the smoothed maps", ".smooth_peaks_", smooth_peaks)
-               : 0;
+    if (pkh && !smh.empty() && write_table("histograms and peak counts of the smoothed maps", ".smooth_peaks_", smooth_peaks))
+        return 1;
+    if (mh && nh && write_table("moments of the noisy maps", ".noisy_moments_", noisy_moments))
+        return 1;
+    if (pkh && nh && write_table("histograms and peak counts of the noisy maps", ".noisy_peaks_", noisy_peaks))
+        return 1;
+    if (mh && nh && !smh.empty() &&
+        write_table("moments of the smoothed noisy maps", ".noisy_smooth_moments_", noisy_smooth_moments))
+        return 1;
+    return pkh && nh && !smh.empty() ? write_table("histograms and peak counts of the smoothed noisy maps",
+                                                   ".noisy_smooth_peaks_", noisy_smooth_peaks)
+                                     : 0;
 }
 
-// --smooth: per scale k the smoothed kappa map of source s, .<kind><k>_kappa_z, and its rows of the two tables
-int LensingOutputs::source_smooth(size_t s, const float *d_kappa)
+// the '#' lines of --smooth in the tables of the smoothed maps
+string LensingOutputs::smooth_head() const
 {
-    if (smh.empty())
-        return 0;
-    string head;  // of both tables
+    string head;
     add(head, "# smooth %s\n# scales_arcmin", o.smooth_kind.c_str());
     for (double a : o.smooth_arcmin)
         add(head, " %.17g", a);
@@ -435,6 +498,73 @@ int LensingOutputs::source_smooth(size_t s, const float *d_kappa)
     for (int32_t r : smooth_radius)
         add(head, " %d", (int)r);
     add(head, "\n");
+    return head;
+}
+
+// the '#' lines of --shape-noise in the tables of the noisy maps
+string LensingOutputs::noise_head() const
+{
+    string head;
+    add(head, "# sigma_e %.17g\n# ngal_arcmin2 %.17g\n# noise_sigma_pix %.17g\n# seed %llu\n# nreal %d\n", o.noise_sigma_e,
+        o.noise_ngal, noise_sigma_pix, (unsigned long long)o.noise_seed, o.noise_nreal);
+    return head;
+}
+
+// --shape-noise: per realisation r the noisy kappa map of source s, .noisy<r>_kappa_z, its rows of the two tables, and
+// with --smooth every scale of the noisy map, .noisy<r>_<kind><k>_kappa_z, with the rows of those
+int LensingOutputs::source_noise(size_t s, const float *d_kappa)
+{
+    const char *who = "slicer_amd: --shape-noise";
+    const string head = noise_head();
+    string smoothed_head = smh.empty() ? "" : smooth_head() + head + "# noise_sigma";
+    for (double g : noise_gain)
+        add(smoothed_head, " %.17g", noise_sigma_pix * g);
+    smoothed_head += "\n";
+    for (int r = 0; r < o.noise_nreal; r++) {
+        float *d_noisy = nullptr;
+        if (slicer_noise_run(nh, d_kappa, noise_sigma_pix, noise_stream[s], (uint32_t)r) != SLICER_OK ||
+            slicer_noise_read(nh, map.data()) != SLICER_OK || slicer_noise_device_map(nh, &d_noisy) != SLICER_OK)
+            return fail(h, who);
+        const vector<FitsKey> keys = {{"SIGMAE", false, 0, o.noise_sigma_e, " "},
+                                      {"NGAL", false, 0, o.noise_ngal, " "},
+                                      {"SIGMAPIX", false, 0, noise_sigma_pix, " "},
+                                      {"SEED", true, (long)o.noise_seed, 0.0, " "},
+                                      {"REALIS", true, r, 0.0, " "}};
+        const string real = std::to_string(r);
+        if (!save("noisy convergence", ".noisy" + real + "_kappa_z", s, keys))
+            return fail(h, who);
+        if (const int rc = mh ? source_moments(s, d_noisy, noisy_moments, head, "real ", real + " ") : 0)
+            return rc;
+        if (const int rc = pkh ? source_peaks(s, d_noisy, noisy_peaks, head, "real ", real + " ") : 0)
+            return rc;
+        for (size_t k = 0; k < smh.size(); k++) {
+            float *d_smooth = nullptr;
+            if (slicer_smooth_run(smh[k], d_noisy) != SLICER_OK || slicer_smooth_read(smh[k], map.data()) != SLICER_OK ||
+                slicer_smooth_device_map(smh[k], &d_smooth) != SLICER_OK)
+                return fail(h, who);
+            vector<FitsKey> more = keys;
+            more.push_back({"SCALE", false, 0, o.smooth_arcmin[k], " "});
+            more.push_back({"RADIUS", true, smooth_radius[k], 0.0, " "});
+            more.push_back({"NOISESIG", false, 0, noise_sigma_pix * noise_gain[k], " "});
+            const string lead = real + " " + std::to_string(k) + " ";
+            if (!save("smoothed noisy convergence", ".noisy" + real + "_" + o.smooth_kind + std::to_string(k) + "_kappa_z", s,
+                      more))
+                return fail(h, who);
+            if (const int rc = mh ? source_moments(s, d_smooth, noisy_smooth_moments, smoothed_head, "real scale ", lead) : 0)
+                return rc;
+            if (const int rc = pkh ? source_peaks(s, d_smooth, noisy_smooth_peaks, smoothed_head, "real scale ", lead) : 0)
+                return rc;
+        }
+    }
+    return 0;
+}
+
+// --smooth: per scale k the smoothed kappa map of source s, .<kind><k>_kappa_z, and its rows of the two tables
+int LensingOutputs::source_smooth(size_t s, const float *d_kappa)
+{
+    if (smh.empty())
+        return 0;
+    const string head = smooth_head();  // of both tables
     for (size_t k = 0; k < smh.size(); k++) {
         float *d_smooth = nullptr;
         if (slicer_smooth_run(smh[k], d_kappa) != SLICER_OK || slicer_smooth_read(smh[k], map.data()) != SLICER_OK ||
@@ -443,20 +573,21 @@ int LensingOutputs::source_smooth(size_t s, const float *d_kappa)
         const vector<FitsKey> keys = {{"SCALE", false, 0, o.smooth_arcmin[k], " "}, {"RADIUS", true, smooth_radius[k], 0.0, " "}};
         if (!save("smoothed convergence", "." + o.smooth_kind + std::to_string(k) + "_kappa_z", s, keys))
             return fail(h, "slicer_amd: --smooth");
-        if (const int rc = mh ? source_moments(s, d_smooth, smooth_moments, head, (int)k) : 0)
+        const string lead = std::to_string(k) + " ";
+        if (const int rc = mh ? source_moments(s, d_smooth, smooth_moments, head, "scale ", lead) : 0)
             return rc;
-        if (const int rc = pkh ? source_peaks(s, d_smooth, smooth_peaks, head, (int)k) : 0)
+        if (const int rc = pkh ? source_peaks(s, d_smooth, smooth_peaks, head, "scale ", lead) : 0)
             return rc;
     }
     return 0;
 }
 
 // The moments table: '#' lines (npix, angle, levels, column names), then per (source, level) z level npix mean S2 ... S8
-// (%.17g): the raw sums about the level's own mean.  The table of the smoothed maps: `head` before the column names, and
-// the scale's index in front of every row.
-int LensingOutputs::source_moments(size_t s, const float *d_map, string &text, const string &head, int scale)
+// (%.17g): the raw sums about the level's own mean.  The tables of the smoothed and the noisy maps: `head` before the
+// column names, `lead_names` in front of them and `lead` in front of every row.
+int LensingOutputs::source_moments(size_t s, const float *d_map, string &text, const string &head, const string &lead_names,
+                                   const string &lead)
 {
-    const string lead = scale < 0 ? "" : std::to_string(scale) + " ";
     const int nlev = o.moments_levels + 1;
     vector<int32_t> npix(nlev);
     vector<double> mean(nlev), sums(nlev * SLICER_MOMENTS_ORDERS);
@@ -465,7 +596,7 @@ int LensingOutputs::source_moments(size_t s, const float *d_map, string &text, c
         return fail(h, "slicer_amd: --moments");
     if (text.empty()) {
         add(text, "# npix %d\n# angle_deg %.17g\n# levels %d\n", p.npix, p.fov, o.moments_levels);
-        text += head + (scale < 0 ? "# z level npix mean" : "# scale z level npix mean");
+        text += head + "# " + lead_names + "z level npix mean";
         for (int k = 2; k < 2 + SLICER_MOMENTS_ORDERS; k++)
             add(text, " S%d", k);
         add(text, "\n");
@@ -483,9 +614,9 @@ int LensingOutputs::source_moments(size_t s, const float *d_map, string &text, c
 // The histogram table: '#' lines (npix, angle, levels, the edges, column names), then per (source, level) one row per
 // bin: -1 (below the first edge), 0 ... B-1, B (above the last), B+1 (NaN pixels).  The levels are those of the pyramid
 // that the moments of this source left behind (level 0 alone without --moments).
-int LensingOutputs::source_peaks(size_t s, float *d_map, string &text, const string &head, int scale)
+int LensingOutputs::source_peaks(size_t s, float *d_map, string &text, const string &head, const string &lead_names,
+                                 const string &lead)
 {
-    const string lead = scale < 0 ? "" : std::to_string(scale) + " ";
     const vector<double> &e = o.peaks_edges;
     const int B = (int)e.size() - 1, levels = mh ? o.moments_levels : 0;
     vector<int64_t> c(3 * B + 7);  // pdf, peaks, minima [B]; below, above [3]; nan
@@ -494,7 +625,7 @@ int LensingOutputs::source_peaks(size_t s, float *d_map, string &text, const str
         add(text, "# npix %d\n# angle_deg %.17g\n# levels %d\n# edges", p.npix, p.fov, levels);
         for (double v : e)
             add(text, " %.17g", v);
-        text += "\n" + head + (scale < 0 ? "# " : "# scale ") + "z level npix bin lo hi n_pixels n_peaks n_minima\n";
+        text += "\n" + head + "# " + lead_names + "z level npix bin lo hi n_pixels n_peaks n_minima\n";
     }
     for (int l = 0; l <= levels; l++) {
         float *d_level = d_map;

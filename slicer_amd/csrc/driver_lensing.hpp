@@ -1,6 +1,6 @@
 // driver_lensing.hpp -- the lensing outputs of the SLICER_amd driver (slicer_main.cpp): their options, their host
-// planning and the device-0 work behind --kappa, --shear, --deflection, --raytrace, --power, --moments, --peaks and
-// --smooth (driver_lensing.cpp describes the options), with the small helpers the rest of the driver shares with them.
+// planning and the device-0 work behind --kappa, --shear, --deflection, --raytrace, --power, --moments, --peaks,
+// --smooth and --shape-noise (driver_lensing.cpp describes the options), with the small helpers the rest of the driver shares with them.
 #pragma once
 #include <deque>
 #include <string>
@@ -25,6 +25,10 @@ struct LensingOptions {
     std::vector<double> peaks_edges;  // empty: no --peaks
     std::string smooth_kind;             // "" (no --smooth), "gauss" or "map"
     std::vector<double> smooth_arcmin;   // its scales
+    bool shape_noise = false;            // --shape-noise sigma_e,ngal[,seed[,nreal]]
+    double noise_sigma_e = 0.0, noise_ngal = 0.0;  // per component; per arcmin^2
+    uint64_t noise_seed = 0;
+    int noise_nreal = 1;
 
     bool gradient() const { return shear_derivative == "gradient"; }
     int n_power_edges(int npix) const { return power_edges.empty() ? npix : (int)power_edges.size(); }
@@ -97,6 +101,12 @@ struct LensingOutputs {
     Owned<slicer_peaks_handle, slicer_peaks_destroy> pkh{};
     std::deque<Owned<slicer_smooth_handle, slicer_smooth_destroy>> smh{};  // --smooth: one per scale
     std::vector<int32_t> smooth_radius{};
+    // --shape-noise: one handle for all sources, the noise of a pixel, the gain of every --smooth scale on it, and the
+    // stream of every source: its rank in ascending redshift, so that the order of the --kappa list changes no file
+    Owned<slicer_noise_handle, slicer_noise_destroy> nh{};
+    double noise_sigma_pix = 0.0;
+    std::vector<double> noise_gain{};
+    std::vector<uint32_t> noise_stream{};
     // --raytrace: a one-source kappa handle that makes a plane's lens map, the rays, their six output buffers, and the
     // sources in ascending redshift with the position of the next one to observe
     Owned<slicer_kappa_handle, slicer_kappa_destroy> lkh{};
@@ -108,6 +118,8 @@ struct LensingOutputs {
     std::vector<float> map{};    // the host copy of the map that save() writes
     std::string moments{}, peaks{};  // their tables, which write() gathers source by source
     std::string smooth_moments{}, smooth_peaks{};  // the same of the smoothed maps, scale by scale
+    std::string noisy_moments{}, noisy_peaks{};    // the same of the noisy maps, realisation by realisation
+    std::string noisy_smooth_moments{}, noisy_smooth_peaks{};  // ... and of the smoothed noisy maps
 
     int create();
     // The planes i0 .. i1-1 of one pass go into the kappa maps as ONE batch whether they were deposited now (their
@@ -122,10 +134,16 @@ private:
     int observe_sources(int done);
     bool save(const char *what, const std::string &token, size_t s, const std::vector<FitsKey> &more = {});
     // The rows of source s for the map at d_map onto the end of `text`, led by its '#' lines while it is empty.
-    // Smoothed maps: `head` goes between the '#' lines and the column names, `scale` (>= 0) in front of every row.
-    int source_moments(size_t s, const float *d_map, std::string &text, const std::string &head = "", int scale = -1);
-    int source_peaks(size_t s, float *d_map, std::string &text, const std::string &head = "", int scale = -1);
+    // Smoothed and noisy maps: `head` goes between the '#' lines and the column names, `lead_names` ("scale ", "real ",
+    // "real scale ") in front of the column names and `lead` (their values, each followed by a blank) in front of every row.
+    int source_moments(size_t s, const float *d_map, std::string &text, const std::string &head = "",
+                       const std::string &lead_names = "", const std::string &lead = "");
+    int source_peaks(size_t s, float *d_map, std::string &text, const std::string &head = "",
+                     const std::string &lead_names = "", const std::string &lead = "");
+    std::string smooth_head() const;
+    std::string noise_head() const;
     int source_smooth(size_t s, const float *d_kappa);
+    int source_noise(size_t s, const float *d_kappa);
     int source_shear(size_t s, const float *d_kappa);
     int power_spectra();
     int write_table(const char *what, const char *token, const std::string &text) const;

@@ -2,7 +2,8 @@
 potential maps from them (row N6), the binned auto and cross power spectra of such maps (row N7), the deflection
 maps and finite-difference derivatives of the potential (row N8), and the central moments of such maps over a pyramid
 of 2x2 halvings (row N9), and the one-point PDF histogram and peak / minimum counts of such maps (row N10), and
-multi-plane ray tracing through the lens planes (row N11), and Gaussian and aperture-mass smoothing of such maps (row N12).
+multi-plane ray tracing through the lens planes (row N11), and Gaussian and aperture-mass smoothing of such maps (row N12),
+and shape noise for such maps from a counter-based generator (row N13).
 
 plane_weights wraps the host weights of include/slicer_amd.h (slicer_lensing_weights); Kappa is the device accumulator
 (slicer_kappa_*) bound to a Slicer handle: it reads the finalized plane maps where they are, in HBM.  Shear (slicer_shear_*)
@@ -12,7 +13,8 @@ map); Power (slicer_power_*) bins the spectra of several of them into C_l; Momen
 level by level and sums the powers 2 ... 8 of every level's pixels about a centre; Peaks (slicer_peaks_*) counts a
 map's pixels, peaks and minima by height over a list of edges; Rays (slicer_rays_*) shoots one ray per pixel through
 the planes' deflection, convergence and shear maps (plane_strengths scales a mass plane to its lens map); Smooth
-(slicer_smooth_*) filters a map with a truncated Gaussian or with the aperture-mass filter built from it.
+(slicer_smooth_*) filters a map with a truncated Gaussian or with the aperture-mass filter built from it; Noise
+(slicer_noise_*) adds Gaussian noise that is a pure function of (seed, stream, realisation, pixel) to a map.
 """
 import ctypes as C
 import math
@@ -533,6 +535,95 @@ class Smooth(_SubHandle):
         n = self.last_npix or 1
         out = np.empty((n, n), np.float32)
         self._s._chk(_L.slicer_smooth_read(self._sh, out.ctypes.data))
+        return out
+
+
+def noise_words(seed, stream, realisation, block):
+    """The four Philox4x32-10 words (uint32 [4]) of block `block` of (seed, stream, realisation), as slicer_noise_words
+    makes them; host only, no device needed."""
+    w = np.empty(4, np.uint32)
+    _host_chk(_L.slicer_noise_words(int(seed), int(stream), int(realisation), int(block), w.ctypes.data))
+    return w
+
+
+def noise_sigma_pix(sigma_e, ngal_arcmin2, angle_deg, npix):
+    """sigma_e / sqrt(n_gal A_pix), A_pix = (60 angle_deg / npix)^2 arcmin^2: the shape noise of a pixel for an
+    ellipticity dispersion sigma_e PER COMPONENT and n_gal galaxies per arcmin^2; host only, no device needed."""
+    out = C.c_double()
+    _host_chk(_L.slicer_noise_sigma_pix(float(sigma_e), float(ngal_arcmin2), float(angle_deg), int(npix), C.byref(out)))
+    return out.value
+
+
+def smooth_noise_gain(kind, sigma_pix, truncate=4.0):
+    """The rms of Smooth's output for white noise of unit variance, at a pixel at least the radius away from every edge
+    (slicer_smooth_noise_gain): sigma_smoothed = sigma_pix_noise * gain; host only, no device needed."""
+    if kind not in _SMOOTH_KINDS:
+        raise ValueError('kind: "gauss" or "map"')
+    out = C.c_double()
+    _host_chk(_L.slicer_smooth_noise_gain(_SMOOTH_KINDS[kind], float(sigma_pix), float(truncate), C.byref(out)))
+    return out.value
+
+
+class Noise(_SubHandle):
+    """Shape noise for maps of up to npix^2 pixels on the device of `slicer`, on its stream:
+    out = x + sigma z, z standard normals that are a pure function of (seed, stream, realisation, flat pixel index)."""
+    _handle, _destroy = "_nh", "slicer_noise_destroy"
+
+    def __init__(self, slicer: Slicer, npix, seed=0):
+        self._s = slicer
+        self.npix, self.seed = int(npix), int(seed)
+        self.last_shape = None  # of the last run
+        nh = C.c_void_p()
+        slicer._chk(_L.slicer_noise_create(slicer._h, self.npix, self.seed, C.byref(nh)))
+        self._nh = nh
+
+    def run(self, d_map=None, sigma=1.0, stream=0, realisation=0, npix=None):
+        """d_map: device address of an f32 map of npix^2 pixels (None: the handle's npix; otherwise at most that), or
+        None for the noise alone; it may be device_map() itself (a second layer)."""
+        d = None if d_map is None else int(d_map)
+        if npix is None:
+            self._s._chk(_L.slicer_noise_run(self._nh, d, float(sigma), int(stream), int(realisation)))
+        else:
+            self._s._chk(_L.slicer_noise_run_npix(self._nh, d, int(npix), float(sigma), int(stream), int(realisation)))
+        n = self.npix if npix is None else int(npix)
+        self.last_shape = (n, n)
+
+    def run_at(self, d_map, first_pixel, count, sigma=1.0, stream=0, realisation=0):
+        """The pixels first_pixel ... first_pixel + count - 1 of the flat index (first_pixel a multiple of 4); d_map
+        (or None) and the output both start at that pixel."""
+        d = None if d_map is None else int(d_map)
+        self._s._chk(_L.slicer_noise_run_at(self._nh, d, int(first_pixel), int(count), float(sigma), int(stream),
+                                            int(realisation)))
+        self.last_shape = (int(count),)
+
+    def run_kappa(self, kappa: Kappa, s, sigma=1.0, stream=0, realisation=0):
+        """The map of source s of a Kappa accumulator, where it is."""
+        self.run(kappa.device_map(s), sigma, stream, realisation, kappa.npix)
+
+    def run_level(self, moments: Moments, level, sigma=1.0, stream=0, realisation=0):
+        """Level `level` >= 1 of the last run of a Moments pyramid, where it is (level 0 is the caller's own map)."""
+        self.run(moments.device_map(level), sigma, stream, realisation, moments.npix >> int(level))
+
+    def words(self, first_block, n_blocks, stream=0, realisation=0):
+        """The words of blocks first_block ... first_block + n_blocks - 1 as the device makes them, uint32 [n_blocks, 4]."""
+        n_blocks = int(n_blocks)
+        d = self._s.malloc(16 * max(n_blocks, 1))
+        try:
+            self._s._chk(_L.slicer_noise_words_device(self._nh, int(first_block), n_blocks, int(stream), int(realisation), d))
+            return self._s.to_host(d, (n_blocks, 4), np.uint32)
+        finally:
+            self._s.free(d)
+
+    def device_map(self):
+        """Device address of the last run's output: f32, the pixels of that run."""
+        p = C.c_void_p()
+        self._s._chk(_L.slicer_noise_device_map(self._nh, C.byref(p)))
+        return p.value
+
+    def read(self):
+        """The last run's output: f32 [n, n] after run, [count] after run_at; waits for the stream."""
+        out = np.empty(self.last_shape or (1,), np.float32)
+        self._s._chk(_L.slicer_noise_read(self._nh, out.ctypes.data))
         return out
 
 
