@@ -533,6 +533,51 @@ int slicer_peaks_read(slicer_peaks_handle ph, int64_t *pdf, int64_t *peaks, int6
                       int64_t *above, int64_t *n_nan);
 int slicer_peaks_destroy(slicer_peaks_handle ph);
 
+/* ---- Minkowski functionals of a map's excursion sets, as exact counts ----
+ * The input is any device f32 map of npix^2 pixels (row-major), 1 <= npix <= 131072, which is only read.  The thresholds
+ * t_0 < t_1 < ... < t_{T-1} are f64, finite and strictly ascending, 1 <= T <= SLICER_MINKOWSKI_MAX_THRESHOLDS (the B + 1
+ * edges of slicer_peaks_edges with B <= 1024 serve as thresholds).
+ * Rank: k(x) = the number of t_j <= x, every pixel x widened exactly to f64 and compared in f64 against the f64 thresholds
+ * (the thresholds are never rounded to f32); k(NaN) = 0, k(-inf) = 0, k(+inf) = T.  Pixel x is in the excursion set Q_j
+ * (x >= t_j) iff k(x) > j.  A NaN is in no set; the NaN pixels are counted in n_nan.
+ * Pixel complex: the map is npix^2 closed unit squares (faces), 2 npix (npix + 1) unit edges and (npix + 1)^2 vertices.
+ * The field of view does not wrap; positions outside the map are in no set (rank 0).  An edge or a vertex belongs to the
+ * closure of Q_j iff at least one of its adjacent faces does: an edge has 2 adjacent faces, an edge on the map's border 1,
+ * a vertex 4, 2 or 1.  Per threshold j = 0 ... T-1:
+ *   faces[j]     the pixels with k > j
+ *   edges[j]     the edges, border edges included, with max k over their adjacent faces > j
+ *   vertices[j]  the vertices with max k over their adjacent faces > j
+ *   boundary[j]  the interior edges with exactly one of their two faces in Q_j (max k > j and not min k > j): the
+ *                perimeter of Q_j inside the field, in pixel sides
+ *   border[j]    the border edges whose one face is in Q_j: the part of the outline that lies on the map's rim (a corner
+ *                pixel counts twice); kept apart from boundary so that the caller chooses the convention
+ * The Euler characteristic chi[j] = vertices[j] - edges[j] + faces[j] is the number of 8-connected components of Q_j minus
+ * its holes (the 4-connected components of the complement that do not reach outside the map); it is not stored here.
+ * All counts are int64 and exact; the same input gives the same numbers on every run; there is no floating-point
+ * accumulation anywhere.
+ *   slicer_minkowski_create    on the device and stream of h (create it after any slicer_set_stream, destroy it before
+ *                              h).  The numbers are checked before the handle, so that they can be checked without a
+ *                              device: npix < 1, fewer than 1 or more than 1025 thresholds, a threshold that is not
+ *                              finite, thresholds not strictly ascending: SLICER_ERR_ARG; npix > 131072:
+ *                              SLICER_ERR_UNSUPPORTED.  Device memory: the thresholds, 8 (5 T + 1) + 8 (5 (T + 1) + 1)
+ *                              bytes of results and at most max(64, 8 per compute unit) rows of 4 (5 (T + 1) + 1) bytes
+ *                              (SLICER_ERR_NOMEM)
+ *   slicer_minkowski_run       any device f32 map of the handle's npix^2 pixels (e.g. slicer_kappa_device_map);
+ *                              enqueued, no synchronisation.  A NULL map: SLICER_ERR_ARG
+ *   slicer_minkowski_run_npix  the same of a smaller map of npix^2 pixels, 1 <= npix <= the handle's (others:
+ *                              SLICER_ERR_ARG), so that one handle serves every level of a moments pyramid
+ *   slicer_minkowski_read      faces, edges, vertices, boundary, border [T] each and the NaN count of the last run (any
+ *                              of them NULL); waits for the stream.  Before any run: SLICER_ERR_STATE */
+typedef struct slicer_minkowski *slicer_minkowski_handle;
+#define SLICER_MINKOWSKI_MAX_THRESHOLDS 1025
+int slicer_minkowski_create(slicer_handle h, int32_t npix, int32_t n_thresholds, const double *thresholds,
+                            slicer_minkowski_handle *out);
+int slicer_minkowski_run(slicer_minkowski_handle mh, const float *d_map);
+int slicer_minkowski_run_npix(slicer_minkowski_handle mh, const float *d_map, int32_t npix);
+int slicer_minkowski_read(slicer_minkowski_handle mh, int64_t *faces, int64_t *edges, int64_t *vertices, int64_t *boundary,
+                          int64_t *border, int64_t *n_nan);
+int slicer_minkowski_destroy(slicer_minkowski_handle mh);
+
 /* ---- Multi-plane ray tracing through the lens planes ----
  * One ray per pixel of an npix^2 grid (axis 0 slow = component 1, axis 1 contiguous = component 2, as for N6 and N8), on the
  * device and stream of h (create it after any slicer_set_stream, destroy it before h).  State per ray, 12 f64: position

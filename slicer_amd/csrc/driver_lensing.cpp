@@ -23,6 +23,12 @@
 //     map and the counts of its peaks and minima by height (strictly above / below all 8 neighbours; the map does not
 //     wrap) over `bins` (1 ... 1024) uniform bins from lo to hi; with --moments also of every level of its pyramid of
 //     block means.
+//   * --minkowski lo,hi,bins: <directory><simulation>.minkowski_<npix>_<suffix>.txt, the Minkowski functionals of the
+//     excursion sets kappa >= t of every kappa map as exact counts of the faces, edges and vertices of the pixel complex
+//     (area, outline length inside the field and on the rim, Euler characteristic) over the bins + 1 thresholds that are
+//     the edges of `bins` (1 ... 1024) uniform bins from lo to hi; with --moments also of every level of its pyramid of
+//     block means; with --smooth and / or --shape-noise also .smooth_minkowski_, .noisy_minkowski_ and
+//     .noisy_smooth_minkowski_, where --peaks writes its tables of those maps.
 //   * --smooth gauss|map:a1,a2,...: per source and per scale a_k (arcminutes; sigma = a_k npix / (60 ANGLE) pixels)
 //     the kappa map smoothed with a Gaussian truncated at 4 sigma (gauss) or turned into the aperture mass of the filter
 //     built from it (map), .<kind><k>_kappa_z..., with the kappa file's header and the keys SCALE (arcminutes) and RADIUS
@@ -94,6 +100,24 @@ __attribute__((format(printf, 2, 3))) static void add(string &text, const char *
     text += piece;
 }
 
+// The value lo,hi,bins of `option` into the bins + 1 uniform edges of slicer_peaks_edges: 0, or 2 after the message
+static int uniform_edges(const string &option, const char *value, const char *meaning, vector<double> &edges)
+{
+    const vector<string> tok = value ? split(value) : vector<string>{};
+    char *e0 = nullptr, *e1 = nullptr, *e2 = nullptr;
+    const double lo = tok.size() == 3 ? strtod(tok[0].c_str(), &e0) : 0.0;
+    const double hi = tok.size() == 3 ? strtod(tok[1].c_str(), &e1) : 0.0;
+    const long bins = tok.size() == 3 ? strtol(tok[2].c_str(), &e2, 10) : 0;
+    if (tok.size() != 3 || tok[0].empty() || tok[1].empty() || tok[2].empty() || *e0 != '\0' || *e1 != '\0' ||
+        *e2 != '\0' || bins < 1 || bins > SLICER_PEAKS_MAX_BINS)
+        return bad("bad " + option + " (lo,hi,bins: " + meaning + " and the number of bins, 1 ... " +
+                   std::to_string(SLICER_PEAKS_MAX_BINS) + ")");
+    edges.resize(bins + 1);
+    if (slicer_peaks_edges(lo, hi, (int32_t)bins, edges.data()) != SLICER_OK)
+        return bad("bad " + option + ": " + slicer_last_error(nullptr));
+    return 0;
+}
+
 int LensingOptions::parse(int argc, char **argv, int &i)
 {
     const string a = argv[i];
@@ -124,18 +148,12 @@ int LensingOptions::parse(int argc, char **argv, int &i)
         moments_levels = (int)v;
         moments_levels_given = true;
     } else if (a == "--peaks") {
-        const vector<string> tok = has_value ? split(argv[++i]) : vector<string>{};
-        char *e0 = nullptr, *e1 = nullptr, *e2 = nullptr;
-        const double lo = tok.size() == 3 ? strtod(tok[0].c_str(), &e0) : 0.0;
-        const double hi = tok.size() == 3 ? strtod(tok[1].c_str(), &e1) : 0.0;
-        const long bins = tok.size() == 3 ? strtol(tok[2].c_str(), &e2, 10) : 0;
-        if (tok.size() != 3 || tok[0].empty() || tok[1].empty() || tok[2].empty() || *e0 != '\0' || *e1 != '\0' ||
-            *e2 != '\0' || bins < 1 || bins > SLICER_PEAKS_MAX_BINS)
-            return bad("bad --peaks (lo,hi,bins: the first and the last edge and the number of bins, 1 ... " +
-                       std::to_string(SLICER_PEAKS_MAX_BINS) + ")");
-        peaks_edges.resize(bins + 1);
-        if (slicer_peaks_edges(lo, hi, (int32_t)bins, peaks_edges.data()) != SLICER_OK)
-            return bad(string("bad --peaks: ") + slicer_last_error(nullptr));
+        if (const int rc = uniform_edges(a, has_value ? argv[++i] : nullptr, "the first and the last edge", peaks_edges))
+            return rc;
+    } else if (a == "--minkowski") {
+        if (const int rc = uniform_edges(a, has_value ? argv[++i] : nullptr, "the first and the last threshold",
+                                         minkowski_thresholds))
+            return rc;
     } else if (a == "--smooth") {
         const string v = has_value ? argv[++i] : "";
         const size_t colon = v.find(':');
@@ -193,6 +211,8 @@ int LensingOptions::check() const
         {moments && no_kappa, "--moments needs --kappa (the moments are those of the kappa maps)"},
         {moments_levels_given && !moments, "--moments-levels needs --moments"},
         {!peaks_edges.empty() && no_kappa, "--peaks needs --kappa (the histograms and peak counts are those of the kappa maps)"},
+        {!minkowski_thresholds.empty() && no_kappa,
+         "--minkowski needs --kappa (the Minkowski functionals are those of the kappa maps)"},
         {!smooth_kind.empty() && no_kappa, "--smooth needs --kappa (the smoothed maps are those of the kappa maps)"},
         {shape_noise && no_kappa, "--shape-noise needs --kappa (the noise is added to the kappa maps)"},
     };
@@ -304,6 +324,10 @@ int LensingOutputs::create()
     if (!o.peaks_edges.empty() &&
         slicer_peaks_create(h, p.npix, (int)o.peaks_edges.size(), o.peaks_edges.data(), pkh.out()) != SLICER_OK)
         return fail(h, "slicer_amd: --peaks");
+    if (!o.minkowski_thresholds.empty() &&
+        slicer_minkowski_create(h, p.npix, (int)o.minkowski_thresholds.size(), o.minkowski_thresholds.data(), mkh.out()) !=
+            SLICER_OK)
+        return fail(h, "slicer_amd: --minkowski");
     for (size_t k = 0; k < o.smooth_arcmin.size(); k++) {
         const double sigma = o.smooth_sigma_pix(k, p.npix, p.fov);
         smooth_radius.push_back(0);
@@ -438,9 +462,9 @@ bool LensingOutputs::save(const char *what, const string &token, size_t s, const
     return false;
 }
 
-// Per source the kappa file, then its moments, then the histograms of its pyramid (which the moments of the same source
-// left behind), then the shear files, then the smoothed maps with their moments and histograms, then the noisy maps with
-// theirs; after the sources the tables.
+// Per source the kappa file, then its moments, then the histograms and the Minkowski functionals of its pyramid (which
+// the moments of the same source left behind), then the shear files, then the smoothed maps with their moments,
+// histograms and functionals, then the noisy maps with theirs; after the sources the tables.
 int LensingOutputs::write()
 {
     if (slicer_kappa_finalize(kh) != SLICER_OK)
@@ -454,6 +478,8 @@ int LensingOutputs::write()
         if (const int rc = mh ? source_moments(s, d_kappa, moments) : 0)
             return rc;
         if (const int rc = pkh ? source_peaks(s, d_kappa, peaks) : 0)
+            return rc;
+        if (const int rc = mkh ? source_minkowski(s, d_kappa, minkowski) : 0)
             return rc;
         if (const int rc = o.shear ? source_shear(s, d_kappa) : 0)
             return rc;
@@ -479,8 +505,17 @@ int LensingOutputs::write()
     if (mh && nh && !smh.empty() &&
         write_table("moments of the smoothed noisy maps", ".noisy_smooth_moments_", noisy_smooth_moments))
         return 1;
-    return pkh && nh && !smh.empty() ? write_table("histograms and peak counts of the smoothed noisy maps",
-                                                   ".noisy_smooth_peaks_", noisy_smooth_peaks)
+    if (pkh && nh && !smh.empty() &&
+        write_table("histograms and peak counts of the smoothed noisy maps", ".noisy_smooth_peaks_", noisy_smooth_peaks))
+        return 1;
+    if (mkh && write_table("Minkowski functionals", ".minkowski_", minkowski))
+        return 1;
+    if (mkh && !smh.empty() && write_table("Minkowski functionals of the smoothed maps", ".smooth_minkowski_", smooth_minkowski))
+        return 1;
+    if (mkh && nh && write_table("Minkowski functionals of the noisy maps", ".noisy_minkowski_", noisy_minkowski))
+        return 1;
+    return mkh && nh && !smh.empty() ? write_table("Minkowski functionals of the smoothed noisy maps",
+                                                   ".noisy_smooth_minkowski_", noisy_smooth_minkowski)
                                      : 0;
 }
 
@@ -537,6 +572,8 @@ int LensingOutputs::source_noise(size_t s, const float *d_kappa)
             return rc;
         if (const int rc = pkh ? source_peaks(s, d_noisy, noisy_peaks, head, "real ", real + " ") : 0)
             return rc;
+        if (const int rc = mkh ? source_minkowski(s, d_noisy, noisy_minkowski, head, "real ", real + " ") : 0)
+            return rc;
         for (size_t k = 0; k < smh.size(); k++) {
             float *d_smooth = nullptr;
             if (slicer_smooth_run(smh[k], d_noisy) != SLICER_OK || slicer_smooth_read(smh[k], map.data()) != SLICER_OK ||
@@ -553,6 +590,8 @@ int LensingOutputs::source_noise(size_t s, const float *d_kappa)
             if (const int rc = mh ? source_moments(s, d_smooth, noisy_smooth_moments, smoothed_head, "real scale ", lead) : 0)
                 return rc;
             if (const int rc = pkh ? source_peaks(s, d_smooth, noisy_smooth_peaks, smoothed_head, "real scale ", lead) : 0)
+                return rc;
+            if (const int rc = mkh ? source_minkowski(s, d_smooth, noisy_smooth_minkowski, smoothed_head, "real scale ", lead) : 0)
                 return rc;
         }
     }
@@ -577,6 +616,8 @@ int LensingOutputs::source_smooth(size_t s, const float *d_kappa)
         if (const int rc = mh ? source_moments(s, d_smooth, smooth_moments, head, "scale ", lead) : 0)
             return rc;
         if (const int rc = pkh ? source_peaks(s, d_smooth, smooth_peaks, head, "scale ", lead) : 0)
+            return rc;
+        if (const int rc = mkh ? source_minkowski(s, d_smooth, smooth_minkowski, head, "scale ", lead) : 0)
             return rc;
     }
     return 0;
@@ -644,6 +685,40 @@ int LensingOutputs::source_peaks(size_t s, float *d_map, string &text, const str
             row(b, e[b], e[b + 1], c[b], c[B + b], c[2 * B + b]);
         row(B, e[B], INFINITY, above[0], above[1], above[2]);
         row(B + 1, NAN, NAN, c[3 * B + 6], 0, 0);
+    }
+    return 0;
+}
+
+// The Minkowski table: '#' lines (npix, angle, levels, the thresholds, column names), then per (source, level) one row
+// per threshold j: the exact counts of slicer_minkowski_read and euler = n_vertices - n_edges + n_faces; n_nan is the
+// level's, repeated in every row.  The levels are those of source_peaks.
+int LensingOutputs::source_minkowski(size_t s, float *d_map, string &text, const string &head, const string &lead_names,
+                                     const string &lead)
+{
+    const vector<double> &t = o.minkowski_thresholds;
+    const int T = (int)t.size(), levels = mh ? o.moments_levels : 0;
+    vector<int64_t> c(5 * T);  // faces, edges, vertices, boundary, border [T]
+    int64_t n_nan = 0;
+    if (text.empty()) {
+        add(text, "# npix %d\n# angle_deg %.17g\n# levels %d\n# thresholds", p.npix, p.fov, levels);
+        for (double v : t)
+            add(text, " %.17g", v);
+        text += "\n" + head + "# " + lead_names +
+                "z level npix j threshold n_faces n_edges n_vertices n_boundary n_border euler n_nan\n";
+    }
+    for (int l = 0; l <= levels; l++) {
+        float *d_level = d_map;
+        if (l > 0 && slicer_moments_device_map(mh, l, &d_level) != SLICER_OK)
+            return fail(h, "slicer_amd: --minkowski");
+        if (slicer_minkowski_run_npix(mkh, d_level, p.npix >> l) != SLICER_OK ||
+            slicer_minkowski_read(mkh, &c[0], &c[T], &c[2 * T], &c[3 * T], &c[4 * T], &n_nan) != SLICER_OK)
+            return fail(h, "slicer_amd: --minkowski");
+        for (int j = 0; j < T; j++) {
+            text += lead;
+            add(text, "%.17g %d %d %d %.17g %lld %lld %lld %lld %lld %lld %lld\n", plan.zs[s], l, p.npix >> l, j, t[j],
+                (long long)c[j], (long long)c[T + j], (long long)c[2 * T + j], (long long)c[3 * T + j],
+                (long long)c[4 * T + j], (long long)(c[2 * T + j] - c[T + j] + c[j]), (long long)n_nan);
+        }
     }
     return 0;
 }

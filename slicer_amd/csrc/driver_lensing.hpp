@@ -1,6 +1,6 @@
 // driver_lensing.hpp -- the lensing outputs of the SLICER_amd driver (slicer_main.cpp): their options, their host
 // planning and the device-0 work behind --kappa, --shear, --deflection, --raytrace, --power, --moments, --peaks,
-// --smooth and --shape-noise (driver_lensing.cpp describes the options), with the small helpers the rest of the driver shares with them.
+// --minkowski, --smooth and --shape-noise (driver_lensing.cpp describes the options), with the small helpers the rest of the driver shares with them.
 #pragma once
 #include <deque>
 #include <string>
@@ -23,6 +23,7 @@ struct LensingOptions {
     bool moments = false, moments_levels_given = false;
     int moments_levels = 0;
     std::vector<double> peaks_edges;  // empty: no --peaks
+    std::vector<double> minkowski_thresholds;  // empty: no --minkowski
     std::string smooth_kind;             // "" (no --smooth), "gauss" or "map"
     std::vector<double> smooth_arcmin;   // its scales
     bool shape_noise = false;            // --shape-noise sigma_e,ngal[,seed[,nreal]]
@@ -99,6 +100,7 @@ struct LensingOutputs {
     Owned<slicer_power_handle, slicer_power_destroy> ph{};
     Owned<slicer_moments_handle, slicer_moments_destroy> mh{};
     Owned<slicer_peaks_handle, slicer_peaks_destroy> pkh{};
+    Owned<slicer_minkowski_handle, slicer_minkowski_destroy> mkh{};
     std::deque<Owned<slicer_smooth_handle, slicer_smooth_destroy>> smh{};  // --smooth: one per scale
     std::vector<int32_t> smooth_radius{};
     // --shape-noise: one handle for all sources, the noise of a pixel, the gain of every --smooth scale on it, and the
@@ -120,6 +122,7 @@ struct LensingOutputs {
     std::string smooth_moments{}, smooth_peaks{};  // the same of the smoothed maps, scale by scale
     std::string noisy_moments{}, noisy_peaks{};    // the same of the noisy maps, realisation by realisation
     std::string noisy_smooth_moments{}, noisy_smooth_peaks{};  // ... and of the smoothed noisy maps
+    std::string minkowski{}, smooth_minkowski{}, noisy_minkowski{}, noisy_smooth_minkowski{};  // --minkowski: the same four
 
     int create();
     // The planes i0 .. i1-1 of one pass go into the kappa maps as ONE batch whether they were deposited now (their
@@ -140,6 +143,8 @@ private:
                        const std::string &lead_names = "", const std::string &lead = "");
     int source_peaks(size_t s, float *d_map, std::string &text, const std::string &head = "",
                      const std::string &lead_names = "", const std::string &lead = "");
+    int source_minkowski(size_t s, float *d_map, std::string &text, const std::string &head = "",
+                         const std::string &lead_names = "", const std::string &lead = "");
     std::string smooth_head() const;
     std::string noise_head() const;
     int source_smooth(size_t s, const float *d_kappa);

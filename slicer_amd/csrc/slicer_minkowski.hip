@@ -1,0 +1,491 @@
+// slicer_minkowski.hip -- on-device Minkowski functionals of a map's excursion sets as exact counts.
+//
+// Of an n x n f32 map x (row-major, only read) and f64 thresholds t_0 < ... < t_{T-1}:
+//   k(x)        the number of t_j <= (double)x, compared in f64 against the f64 thresholds; k(NaN) = k(-inf) = 0,
+//               k(+inf) = T.  Pixel x is in the excursion set Q_j iff k(x) > j; positions outside the map have k = 0.
+//   The map is a complex of n^2 closed unit squares (faces), 2 n (n + 1) unit edges and (n + 1)^2 vertices that does
+//   not wrap; an edge or a vertex is in the closure of Q_j iff one of its adjacent faces is.  Per threshold j:
+//   faces[j]    pixels with k > j                       vertices[j]  vertices with max k over their faces > j
+//   edges[j]    edges with max k over their faces > j   border[j]    edges on the map's rim whose one face has k > j
+//   boundary[j] interior edges with exactly one of their two faces in Q_j = #{max k > j} - #{min k > j}
+//   n_nan       NaN pixels (in no set).
+// Every count is an integer: nothing here is a floating-point sum, so the results are exact and the same on every run.
+//
+// k_minkowski works on the grid of (n + 1)^2 cells.  Cell (i, j), 0 <= i, j <= n, owns face (i, j), the vertex at its
+// top-left corner, its top edge (between faces (i-1, j) and (i, j)) and its left edge (between faces (i, j-1) and
+// (i, j)): every face, edge and vertex has exactly one owner, and an owned edge is on the rim iff i is 0 or n (top
+// edge) or j is 0 or n (left edge).  What does not exist (a face or a left edge of row n, a top edge of column n,
+// anything past them) has only faces of rank 0 and is never counted, so existence needs no test.
+// A workgroup of 256 threads takes tiles of kT0 x kT1 = 16 x 64 cells (the tile of slicer_peaks.hip) and every thread
+// four adjacent cells of one row.  A tile needs the RANKS of 17 x 65 pixels: its own faces, one row above and one
+// column to the left.  Every pixel of the window is searched once, while it is staged, and the window holds the ranks
+// as u16 (k <= 1025), not the floats: 17 rows of pitch 72 with the tile's first column at window column 4, so that a
+// thread's four ranks of a row are one 8-byte LDS access and the left neighbour one u16.  Thread t stages the four
+// pixels of quad t % 16 of window row t / 16 (rows r0 - 1 ... r0 + 14) and, for t < 81, one more pixel: the tile's
+// last row (t < 64) or the column to the left (64 <= t < 81).  The five are searched side by side in ONE pass of the
+// branch-free binary search of slicer_peaks.hip (ceil(log2 T) + 1 LDS reads of the f64 thresholds, steps that depend on
+// T alone), so the 81 extra pixels cost a fifth more reads and no second pass.  Loads: a float4 per quad when 4 | n and
+// the map is on the 16-byte grid (k_minkowski<true>), scalar loads otherwise (<false>); the window, and so the counts,
+// are the same.  NaN pixels are counted where they are staged as one of the tile's own faces.
+// Counters: five u32 LDS histograms of T + 1 rank bins -- face k, vertex max k, interior-edge max k, interior-edge
+// min k, rim-edge k -- and the NaN counter, incremented with LDS integer atomics; rank 0 is in no set and is skipped.
+// Lanes that hit one counter at once are served one after the other, and on a smooth map or with few thresholds most
+// lanes of a wave do.  Two measures, neither changes a count: (1) the counters are kept in 2^c copies, c the largest
+// with 2^c <= 32 and 2^c * 20 (T + 1) B <= 16 KB (32 copies at T = 9, 8 at 65, 1 above 408), copy `lane mod 2^c` of
+// counter m at word m * 2^c + copy, so the copies of one counter lie in adjacent banks; the flush adds them.  (2) A
+// thread whose ten ranks are equal (its four cells lie inside a plateau of rank r; rank 0 outside the map makes that
+// impossible on the rim) adds 4 faces, 4 vertices and 8 interior edges (max and min) of rank r with four atomics
+// instead of twenty-four.
+// u32 is enough: the interior-edge histograms take at most 2 * 1024 increments a tile, a workgroup takes at most
+// ceil(tiles / G) tiles, tiles <= 8193 * 2049 and G >= min(tiles, 64) (a static_assert).
+// The grid is fixed: G = min(tiles, max(kMinGroups, w * CUs)) workgroups, w = min(8, what a CU's LDS holds at once),
+// workgroup b takes tiles b, b + G, ...  Flush: workgroup b stores its counters as row b of partial[G][5 (T + 1) + 1];
+// k_minkowski_finish sums the rows of every column into int64, k_minkowski_suffix (one workgroup) forms
+// out[j] = sum over k > j of hist[k] and stores faces, edges = edge max + rim, vertices, boundary = edge max - edge
+// min, border = rim, and the NaN count.  Every row and every result is stored by every launch: nothing is zeroed
+// between runs, nothing carried over, no global atomics.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <new>
+#include <vector>
+
+#include "slicer_host.hpp"
+
+namespace {
+
+constexpr int kT0 = 16, kT1 = 64;  // tile: rows x columns of cells
+constexpr int kPer = 4;            // adjacent cells of a thread
+constexpr int kThreads = kT0 * kT1 / kPer;
+constexpr int kRows = kT0 + 1;           // window rows: one above the tile
+constexpr int kLeft = 4;                 // window column of the tile's first pixel
+constexpr int kPitch = kLeft + kT1 + 4;  // 72 u16: every window row starts on the 16-byte grid
+constexpr int kQuads = kT1 / kPer;       // quads of a tile row = threads of a tile row
+constexpr int kExtra = kT1 + kRows;      // the tile's last row and the column to its left: one pixel a thread
+constexpr int kMaxNpix = 131072;
+constexpr int kMaxT = SLICER_MINKOWSKI_MAX_THRESHOLDS;
+constexpr int kHists = 5;  // face, vertex, interior-edge max, interior-edge min, rim edge
+enum { H_FACE = 0, H_VERTEX, H_EDGE_MAX, H_EDGE_MIN, H_RIM };
+constexpr int kPerCu = 8, kMinGroups = 64;  // workgroups per CU at most; fewer where their LDS does not fit
+constexpr size_t kLdsPerCu = 160 * 1024;    // gfx950
+constexpr size_t kCopyBytes = 16 * 1024;     // LDS for the copies of the counters (one copy may be larger)
+constexpr int kFinCols = 16, kFinRows = 16;  // k_minkowski_finish: columns of a workgroup x threads of a column
+
+static_assert(kThreads == 256 && kFinCols * kFinRows == kThreads, "one thread per four cells of a tile");
+static_assert(kExtra <= kThreads && kQuads * (kRows - 1) == kThreads, "a quad and at most one more pixel a thread");
+static_assert((((int64_t)kMaxNpix + 1 + kT0 - 1) / kT0) * (((int64_t)kMaxNpix + 1 + kT1 - 1) / kT1) / kMinGroups + 1 <
+                  ((int64_t)1 << 32) / (2 * kT0 * kT1),
+              "a workgroup's u32 counters hold the 2 * 1024 increments a tile of every tile it can meet");
+
+struct MinkArgs {
+    const float *x;
+    const double *thr;  // [T]
+    unsigned *partial;  // [gridDim.x][5 (T + 1) + 1]
+    int n, T;
+    int tiles_x, ntiles;
+    int lg_copies;  // log2 of the copies of every counter in LDS
+};
+
+// log2 of the copies of the 5 (T + 1) counters that kCopyBytes hold, 32 at most
+int lg_copies_of(int T)
+{
+    int lg = 0;
+    while (lg < 5 && ((size_t)kHists * (T + 1) * sizeof(unsigned) << (lg + 1)) <= kCopyBytes)
+        lg++;
+    return lg;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(kThreads) void k_minkowski(MinkArgs a)
+{
+    __shared__ __attribute__((aligned(16))) unsigned short win[kRows * kPitch];
+    extern __shared__ double dyn[];
+    const int n = a.n, T = a.T, nb = T + 1, nC = kHists * nb + 1, tid = threadIdx.x;
+    const int lg = a.lg_copies, nan_at = (kHists * nb) << lg;  // counter (h, k), copy c: cnt[((h nb + k) << lg) + c]
+    const unsigned copy = tid & ((1 << lg) - 1);
+    double *thr = dyn;
+    unsigned *cnt = reinterpret_cast<unsigned *>(dyn + T);
+    for (int k = tid; k < T; k += kThreads)
+        thr[k] = a.thr[k];
+    for (int k = tid; k <= nan_at; k += kThreads)
+        cnt[k] = 0u;
+    // w more elements of rank k in histogram h; rank 0 is in no set
+    const auto add = [&](int h, unsigned k, unsigned w) {
+        if (k)
+            atomicAdd(&cnt[(((unsigned)(h * nb) + k) << lg) + copy], w);
+    };
+    const int lr = tid / kQuads, lc = tid % kQuads * kPer;
+    for (int t = blockIdx.x; t < a.ntiles; t += gridDim.x) {
+        const int r0 = t / a.tiles_x * kT0, c0 = t % a.tiles_x * kT1;
+        __syncthreads();  // the previous tile's window has been read (first tile: thresholds and counters are in place)
+        // the five pixels of this thread: v[0..3] the quad of window row lr (map row r0 - 1 + lr), v[4] the extra one.
+        // A position outside the map stays -inf: rank 0, like the NaNs, which are counted here.
+        float v[kPer + 1];
+#pragma unroll
+        for (int q = 0; q <= kPer; q++)
+            v[q] = -INFINITY;
+        {
+            const int r = r0 - 1 + lr, c = c0 + lc;
+            if (r >= 0 && r < n) {
+                if (VEC) {  // 4 | n and c % 4 == 0: a float4 lies in the map whole or not at all
+                    if (c < n) {
+                        const float4 m = *reinterpret_cast<const float4 *>(a.x + (size_t)r * n + c);
+                        v[0] = m.x, v[1] = m.y, v[2] = m.z, v[3] = m.w;
+                    }
+                } else {
+#pragma unroll
+                    for (int q = 0; q < kPer; q++)
+                        if (c + q < n)
+                            v[q] = a.x[(size_t)r * n + c + q];
+                }
+            }
+        }
+        int er = -1, ec = -1;  // the extra pixel's map position
+        if (tid < kT1)
+            er = r0 + kT0 - 1, ec = c0 + tid;
+        else if (tid < kExtra)
+            er = r0 - 1 + (tid - kT1), ec = c0 - 1;
+        if (er >= 0 && er < n && ec >= 0 && ec < n)
+            v[kPer] = a.x[(size_t)er * n + ec];
+        unsigned n_nan = 0;  // among the tile's own faces: every row of the quads but the first, and the last row
+#pragma unroll
+        for (int q = 0; q < kPer; q++)
+            n_nan += lr >= 1 && v[q] != v[q] ? 1u : 0u;
+        n_nan += tid < kT1 && v[kPer] != v[kPer] ? 1u : 0u;
+        if (n_nan)
+            atomicAdd(&cnt[nan_at], n_nan);
+        // pos[q]: how many of t_0 ... t_{T-1} are <= pixel q.  Invariant of the search: every threshold before `pos`
+        // is <= x and the answer lies in pos ... pos + len.  The steps depend on T alone, so the wave never diverges,
+        // and the five pixels' reads of a step are independent of one another.  A NaN fails every comparison: rank 0.
+        double xd[kPer + 1];
+        int pos[kPer + 1];
+#pragma unroll
+        for (int q = 0; q <= kPer; q++) {
+            xd[q] = (double)v[q];
+            pos[q] = 0;
+        }
+        for (int len = T; len > 1;) {
+            const int half = len / 2;
+#pragma unroll
+            for (int q = 0; q <= kPer; q++)
+                pos[q] = thr[pos[q] + half - 1] <= xd[q] ? pos[q] + half : pos[q];
+            len -= half;
+        }
+#pragma unroll
+        for (int q = 0; q <= kPer; q++)
+            pos[q] += thr[pos[q]] <= xd[q] ? 1 : 0;
+        *reinterpret_cast<uint2 *>(win + lr * kPitch + kLeft + lc) =
+            make_uint2((unsigned)pos[0] | (unsigned)pos[1] << 16, (unsigned)pos[2] | (unsigned)pos[3] << 16);
+        if (tid < kT1)
+            win[(kRows - 1) * kPitch + kLeft + tid] = (unsigned short)pos[kPer];
+        else if (tid < kExtra)
+            win[(tid - kT1) * kPitch + kLeft - 1] = (unsigned short)pos[kPer];
+        __syncthreads();
+        const int i = r0 + lr, j0 = c0 + lc;
+        if (i > n || j0 > n)
+            continue;  // (only faces of rank 0 around these cells)
+        // up[q], at[q]: the ranks of faces (i-1, j0-1+q) and (i, j0-1+q), q = 0 ... 4
+        unsigned up[kPer + 1], at[kPer + 1];
+        {
+            const unsigned short *w = win + lr * kPitch + kLeft + lc;
+            const uint2 u = *reinterpret_cast<const uint2 *>(w), d = *reinterpret_cast<const uint2 *>(w + kPitch);
+            up[0] = w[-1], at[0] = w[kPitch - 1];
+            up[1] = u.x & 0xffffu, up[2] = u.x >> 16, up[3] = u.y & 0xffffu, up[4] = u.y >> 16;
+            at[1] = d.x & 0xffffu, at[2] = d.x >> 16, at[3] = d.y & 0xffffu, at[4] = d.y >> 16;
+        }
+        // Ten equal ranks: none of the ten faces is outside the map (rank 0 counts nothing), so the four cells' faces,
+        // vertices and eight edges are all inside, all of that rank: four increments instead of twenty-four
+        bool flat = true;
+#pragma unroll
+        for (int q = 0; q <= kPer; q++)
+            flat = flat && up[q] == at[1] && at[q] == at[1];
+        if (flat) {
+            add(H_FACE, at[1], kPer);
+            add(H_VERTEX, at[1], kPer);
+            add(H_EDGE_MAX, at[1], 2 * kPer);
+            add(H_EDGE_MIN, at[1], 2 * kPer);
+            continue;
+        }
+        const bool rim_row = i == 0 || i == n;
+#pragma unroll
+        for (int q = 0; q < kPer; q++) {
+            const int j = j0 + q;
+            const unsigned f = at[q + 1], left = at[q], above = up[q + 1];
+            add(H_FACE, f, 1);
+            add(H_VERTEX, max(max(up[q], above), max(left, f)), 1);
+            if (rim_row) {  // the top edge: one of its two faces is outside
+                add(H_RIM, max(above, f), 1);
+            } else {
+                add(H_EDGE_MAX, max(above, f), 1);
+                add(H_EDGE_MIN, min(above, f), 1);
+            }
+            if (j == 0 || j == n) {  // the left edge
+                add(H_RIM, max(left, f), 1);
+            } else {
+                add(H_EDGE_MAX, max(left, f), 1);
+                add(H_EDGE_MIN, min(left, f), 1);
+            }
+        }
+    }
+    __syncthreads();
+    unsigned *out = a.partial + (size_t)blockIdx.x * nC;
+    for (int k = tid; k < nC - 1; k += kThreads) {
+        unsigned sum = 0;
+        for (int c = 0; c < 1 << lg; c++)
+            sum += cnt[(k << lg) + c];
+        out[k] = sum;
+    }
+    if (tid == 0)
+        out[nC - 1] = cnt[nan_at];
+}
+
+// Workgroup v sums columns 16 v ... 16 v + 15 of partial[G][nC] into hist[nC]: sixteen threads a column, thread rg of
+// them the rows rg, rg + 16, ...; integer sums, so the order does not matter.
+__global__ __launch_bounds__(kThreads) void k_minkowski_finish(const unsigned *partial, int G, int nC, int64_t *hist)
+{
+    __shared__ int64_t red[kFinRows][kFinCols];
+    const int cl = threadIdx.x % kFinCols, rg = threadIdx.x / kFinCols, col = (int)blockIdx.x * kFinCols + cl;
+    int64_t acc = 0;
+    if (col < nC) {
+#pragma unroll 8
+        for (int g = rg; g < G; g += kFinRows)
+            acc += (int64_t)partial[(size_t)g * nC + col];
+    }
+    red[rg][cl] = acc;
+    __syncthreads();
+    if (rg != 0 || col >= nC)
+        return;
+    for (int k = 1; k < kFinRows; k++)
+        acc += red[k][cl];
+    hist[col] = acc;
+}
+
+// One workgroup: suf[h][k] = sum over m >= k of histogram h.  Thread u sums the bins u per ... (u + 1) per - 1 of every
+// histogram, the 256 chunk sums are scanned from the back in eight doubling steps, and every thread walks its bins down
+// from the sum of the chunks after its own.  Then res = faces [T], edges [T], vertices [T], boundary [T], border [T],
+// n_nan with out[j] = suf[j + 1].
+__global__ __launch_bounds__(kThreads) void k_minkowski_suffix(const int64_t *hist, int T, int64_t *res)
+{
+    __shared__ int64_t suf[kHists][kMaxT + 1];
+    __shared__ int64_t chunk[kHists][kThreads];
+    const int nb = T + 1, tid = threadIdx.x, per = (nb + kThreads - 1) / kThreads;
+    const int lo = min(tid * per, nb), hi = min(lo + per, nb);
+    int64_t own[kHists];
+    for (int h = 0; h < kHists; h++) {
+        own[h] = 0;
+        for (int k = lo; k < hi; k++)
+            own[h] += hist[(size_t)h * nb + k];
+        chunk[h][tid] = own[h];
+    }
+    __syncthreads();
+    for (int off = 1; off < kThreads; off <<= 1) {
+        int64_t more[kHists];
+        for (int h = 0; h < kHists; h++)
+            more[h] = tid + off < kThreads ? chunk[h][tid + off] : 0;
+        __syncthreads();
+        for (int h = 0; h < kHists; h++)
+            chunk[h][tid] += more[h];
+        __syncthreads();
+    }
+    for (int h = 0; h < kHists; h++) {
+        int64_t run = chunk[h][tid] - own[h];  // the chunks after this thread's
+        for (int k = hi - 1; k >= lo; k--) {
+            run += hist[(size_t)h * nb + k];
+            suf[h][k] = run;
+        }
+    }
+    __syncthreads();
+    for (int j = tid; j < T; j += kThreads) {
+        const int64_t edge_max = suf[H_EDGE_MAX][j + 1], rim = suf[H_RIM][j + 1];
+        res[j] = suf[H_FACE][j + 1];
+        res[T + j] = edge_max + rim;
+        res[2 * T + j] = suf[H_VERTEX][j + 1];
+        res[3 * T + j] = edge_max - suf[H_EDGE_MIN][j + 1];
+        res[4 * T + j] = rim;
+    }
+    if (tid == 0)
+        res[5 * T] = hist[kHists * nb];
+}
+
+size_t mink_columns(int T) { return (size_t)kHists * ((size_t)T + 1) + 1; }
+
+// the thresholds, the copies of the 5 (T + 1) counters and the NaN counter
+size_t mink_dyn_lds(int T)
+{
+    return (size_t)T * sizeof(double) + (((mink_columns(T) - 1) << lg_copies_of(T)) + 1) * sizeof(unsigned);
+}
+
+int64_t tiles_of(int n) { return (int64_t)((n + 1 + kT0 - 1) / kT0) * ((n + 1 + kT1 - 1) / kT1); }
+
+// 0, or the message of what is wrong with the thresholds
+const char *thresholds_fault(int32_t T, const double *thr)
+{
+    for (int k = 0; k < T; k++)
+        if (!std::isfinite(thr[k]))
+            return "thresholds must be finite";
+    for (int k = 1; k < T; k++)
+        if (!(thr[k - 1] < thr[k]))
+            return "thresholds must be strictly ascending";
+    return nullptr;
+}
+
+}  // namespace
+
+struct slicer_minkowski {
+    slicer_handle h = nullptr;
+    int device = 0;
+    int n = 0, T = 0;
+    int gmax = 0;  // rows of `partial`
+    std::vector<double> thr;
+    double *d_thr = nullptr;
+    unsigned *partial = nullptr;
+    int64_t *hist = nullptr;  // the column sums of `partial`
+    int64_t *res = nullptr;
+    bool ran = false;
+    DevAllocs mem;
+};
+
+extern "C" {
+
+int slicer_minkowski_create(slicer_handle h, int32_t npix, int32_t n_thresholds, const double *thresholds,
+                            slicer_minkowski_handle *out)
+{
+    // the numbers first: they need no handle, so a caller can have them checked before any device exists
+    if (out)
+        *out = nullptr;
+    if (npix < 1)
+        return fail(h, SLICER_ERR_ARG, "slicer_minkowski_create: npix must be positive");
+    if (npix > kMaxNpix)
+        return fail(h, SLICER_ERR_UNSUPPORTED, "slicer_minkowski_create: npix = %d above %d", npix, kMaxNpix);
+    if (n_thresholds < 1)
+        return fail(h, SLICER_ERR_ARG, "slicer_minkowski_create: fewer than 1 threshold");
+    if (n_thresholds > kMaxT)
+        return fail(h, SLICER_ERR_ARG, "slicer_minkowski_create: %d thresholds, at most %d", n_thresholds, kMaxT);
+    if (!thresholds)
+        return fail(h, SLICER_ERR_ARG, "slicer_minkowski_create: null argument");
+    if (const char *what = thresholds_fault(n_thresholds, thresholds))
+        return fail(h, SLICER_ERR_ARG, "slicer_minkowski_create: %s", what);
+    if (!h || !out)
+        return fail(h, SLICER_ERR_ARG, "slicer_minkowski_create: null argument");
+    const char *who = "slicer_minkowski_create";
+    hipStream_t st = nullptr;
+    int dev = 0;
+    if (int rc = sub_open(h, who, &st, &dev))
+        return rc;
+    slicer_minkowski_handle mh = new (std::nothrow) slicer_minkowski;
+    if (!mh)
+        return fail(h, SLICER_ERR_NOMEM, "out of host memory");
+    mh->h = h;
+    mh->device = dev;
+    mh->n = npix;
+    mh->T = n_thresholds;
+    // as many workgroups as are resident at once: by LDS (the window, the thresholds, the counters), kPerCu at most
+    const size_t lds = kRows * kPitch * sizeof(unsigned short) + mink_dyn_lds(mh->T);
+    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(kPerCu, kLdsPerCu / lds));
+    mh->gmax = (int)std::min<int64_t>(tiles_of(npix), std::max(kMinGroups, per_cu * h->num_cus));
+    mh->thr.assign(thresholds, thresholds + n_thresholds);
+    const size_t nC = mink_columns(mh->T);
+    int rc = SLICER_OK;
+    rc = mh->mem.alloc(rc, h, who, (void **)&mh->d_thr, (size_t)n_thresholds * sizeof(double));
+    rc = mh->mem.alloc(rc, h, who, (void **)&mh->partial, (size_t)mh->gmax * nC * sizeof(unsigned));
+    rc = mh->mem.alloc(rc, h, who, (void **)&mh->hist, nC * sizeof(int64_t));
+    rc = mh->mem.alloc(rc, h, who, (void **)&mh->res, (5 * (size_t)mh->T + 1) * sizeof(int64_t));
+    if (rc == SLICER_OK) {
+        // (mh->thr outlives the copy)
+        hipError_t e = hipMemcpyAsync(mh->d_thr, mh->thr.data(), (size_t)n_thresholds * sizeof(double), hipMemcpyHostToDevice, st);
+        if (e != hipSuccess)
+            rc = fail(h, SLICER_ERR_HIP, "%s: copying the thresholds: %s", who, hipGetErrorString(e));
+    }
+    if (rc != SLICER_OK) {
+        delete mh;
+        return rc;
+    }
+    *out = mh;
+    return SLICER_OK;
+}
+
+int slicer_minkowski_run_npix(slicer_minkowski_handle mh, const float *d_map, int32_t npix)
+{
+    if (!mh || !d_map)
+        return fail(mh ? mh->h : nullptr, SLICER_ERR_ARG, "slicer_minkowski_run_npix: null argument");
+    if (npix < 1 || npix > mh->n)
+        return fail(mh->h, SLICER_ERR_ARG, "slicer_minkowski_run_npix: npix = %d outside 1..%d", npix, mh->n);
+    hipStream_t st;
+    if (int rc = sub_stream(mh->h, mh->device, &st))
+        return rc;
+    mh->ran = false;
+    const int nC = (int)mink_columns(mh->T);
+    MinkArgs a{};
+    a.x = d_map;
+    a.thr = mh->d_thr;
+    a.partial = mh->partial;
+    a.n = npix;
+    a.T = mh->T;
+    a.tiles_x = (npix + 1 + kT1 - 1) / kT1;
+    a.ntiles = (int)tiles_of(npix);
+    a.lg_copies = lg_copies_of(mh->T);
+    const int G = std::min(a.ntiles, mh->gmax);
+    const size_t lds = mink_dyn_lds(mh->T);
+    {
+        ProfScope ps(mh->h, KN_MINKOWSKI);
+        if (npix % 4 == 0 && (uintptr_t)d_map % 16 == 0)
+            hipLaunchKernelGGL(k_minkowski<true>, dim3((unsigned)G), dim3(kThreads), lds, st, a);
+        else
+            hipLaunchKernelGGL(k_minkowski<false>, dim3((unsigned)G), dim3(kThreads), lds, st, a);
+        HIPCHK(mh->h, hipGetLastError());
+    }
+    {
+        ProfScope ps(mh->h, KN_MINKOWSKI_FINISH);
+        hipLaunchKernelGGL(k_minkowski_finish, dim3((unsigned)((nC + kFinCols - 1) / kFinCols)), dim3(kThreads), 0, st,
+                           mh->partial, G, nC, mh->hist);
+        HIPCHK(mh->h, hipGetLastError());
+        hipLaunchKernelGGL(k_minkowski_suffix, dim3(1), dim3(kThreads), 0, st, mh->hist, mh->T, mh->res);
+        HIPCHK(mh->h, hipGetLastError());
+    }
+    mh->ran = true;
+    return SLICER_OK;
+}
+
+int slicer_minkowski_run(slicer_minkowski_handle mh, const float *d_map)
+{
+    if (!mh || !d_map)
+        return fail(mh ? mh->h : nullptr, SLICER_ERR_ARG, "slicer_minkowski_run: null argument");
+    return slicer_minkowski_run_npix(mh, d_map, mh->n);
+}
+
+int slicer_minkowski_read(slicer_minkowski_handle mh, int64_t *faces, int64_t *edges, int64_t *vertices, int64_t *boundary,
+                          int64_t *border, int64_t *n_nan)
+{
+    if (!mh)
+        return fail(nullptr, SLICER_ERR_ARG, "slicer_minkowski_read: null handle");
+    if (!mh->ran)
+        return fail(mh->h, SLICER_ERR_STATE, "slicer_minkowski_read before any slicer_minkowski_run");
+    hipStream_t st;
+    if (int rc = sub_stream(mh->h, mh->device, &st))
+        return rc;
+    const size_t T = (size_t)mh->T;
+    std::vector<int64_t> r(5 * T + 1);
+    HIPCHK(mh->h, hipMemcpyAsync(r.data(), mh->res, r.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(mh->h, hipStreamSynchronize(st));
+    int64_t *const outs[5] = {faces, edges, vertices, boundary, border};
+    for (size_t k = 0; k < 5; k++)
+        if (outs[k])
+            std::copy_n(&r[k * T], T, outs[k]);
+    if (n_nan)
+        *n_nan = r[5 * T];
+    return SLICER_OK;
+}
+
+int slicer_minkowski_destroy(slicer_minkowski_handle mh)
+{
+    if (!mh)
+        return SLICER_ERR_ARG;
+    (void)hipSetDevice(mh->device);
+    (void)hipStreamSynchronize(mh->h->stream);
+    delete mh;
+    return SLICER_OK;
+}
+
+}  // extern "C"

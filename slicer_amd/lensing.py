@@ -3,7 +3,8 @@ potential maps from them (row N6), the binned auto and cross power spectra of su
 maps and finite-difference derivatives of the potential (row N8), and the central moments of such maps over a pyramid
 of 2x2 halvings (row N9), and the one-point PDF histogram and peak / minimum counts of such maps (row N10), and
 multi-plane ray tracing through the lens planes (row N11), and Gaussian and aperture-mass smoothing of such maps (row N12),
-and shape noise for such maps from a counter-based generator (row N13).
+and shape noise for such maps from a counter-based generator (row N13), and the Minkowski functionals of such maps'
+excursion sets as exact counts (row N14).
 
 plane_weights wraps the host weights of include/slicer_amd.h (slicer_lensing_weights); Kappa is the device accumulator
 (slicer_kappa_*) bound to a Slicer handle: it reads the finalized plane maps where they are, in HBM.  Shear (slicer_shear_*)
@@ -14,7 +15,8 @@ level by level and sums the powers 2 ... 8 of every level's pixels about a centr
 map's pixels, peaks and minima by height over a list of edges; Rays (slicer_rays_*) shoots one ray per pixel through
 the planes' deflection, convergence and shear maps (plane_strengths scales a mass plane to its lens map); Smooth
 (slicer_smooth_*) filters a map with a truncated Gaussian or with the aperture-mass filter built from it; Noise
-(slicer_noise_*) adds Gaussian noise that is a pure function of (seed, stream, realisation, pixel) to a map.
+(slicer_noise_*) adds Gaussian noise that is a pure function of (seed, stream, realisation, pixel) to a map;
+Minkowski (slicer_minkowski_*) counts the faces, edges and vertices of the pixel complex that lie in the sets x >= t_j.
 """
 import ctypes as C
 import math
@@ -471,6 +473,76 @@ class Peaks(_SubHandle):
                                           below.ctypes.data, above.ctypes.data, nan.ctypes.data))
         return {"edges": self.edges.copy(), "pdf": pdf, "peaks": peaks, "minima": minima, "below": below, "above": above,
                 "nan": int(nan[0])}
+
+
+MINKOWSKI_MAX_THRESHOLDS = 1025
+
+
+class Minkowski(_SubHandle):
+    """The Minkowski functionals of the excursion sets x >= t_j of an npix^2 map over the f64 `thresholds`, as exact
+    int64 counts of the faces, edges and vertices of the pixel complex, on the device of `slicer`, on its stream
+    (DESIGN.md S8 row N14).  peaks_edges(lo, hi, bins) gives bins + 1 uniform thresholds."""
+    _handle, _destroy = "_mh", "slicer_minkowski_destroy"
+
+    def __init__(self, slicer: Slicer, npix, thresholds):
+        self._s = slicer
+        self.npix = int(npix)
+        self.thresholds = np.array(thresholds, np.float64).ravel()
+        self.n_thresholds = self.thresholds.size
+        mh = C.c_void_p()
+        slicer._chk(_L.slicer_minkowski_create(slicer._h, self.npix, self.n_thresholds, _dptr(self.thresholds),
+                                               C.byref(mh)))
+        self._mh = mh
+        self.last_npix = None  # of the last run
+
+    def run(self, d_map, npix=None):
+        """d_map: device address of an f32 map of npix^2 pixels (None: the handle's npix; otherwise at most that)."""
+        d = None if d_map is None else int(d_map)
+        if npix is None:
+            self._s._chk(_L.slicer_minkowski_run(self._mh, d))
+        else:
+            self._s._chk(_L.slicer_minkowski_run_npix(self._mh, d, int(npix)))
+        self.last_npix = self.npix if npix is None else int(npix)
+
+    def run_kappa(self, kappa: Kappa, s):
+        """The map of source s of a Kappa accumulator, where it is."""
+        self.run(kappa.device_map(s), kappa.npix)
+
+    def run_level(self, moments: Moments, level):
+        """Level `level` >= 1 of the last run of a Moments pyramid, where it is (level 0 is the caller's own map)."""
+        self.run(moments.device_map(level), moments.npix >> int(level))
+
+    def read(self):
+        """dict: thresholds [T], faces, edges, vertices, boundary, border and euler = vertices - edges + faces (int64
+        [T], one value per threshold), nan, and npix: the map size of the last run."""
+        T = self.n_thresholds
+        faces, edges, vertices, boundary, border = (np.empty(T, np.int64) for _ in range(5))
+        nan = np.empty(1, np.int64)
+        self._s._chk(_L.slicer_minkowski_read(self._mh, faces.ctypes.data, edges.ctypes.data, vertices.ctypes.data,
+                                              boundary.ctypes.data, border.ctypes.data, nan.ctypes.data))
+        return {"thresholds": self.thresholds.copy(), "faces": faces, "edges": edges, "vertices": vertices,
+                "boundary": boundary, "border": border, "euler": vertices - edges + faces, "nan": int(nan[0]),
+                "npix": self.last_npix}
+
+
+def minkowski_functionals(read, angle_deg):
+    """The counts of a Minkowski.read() of a map of angle_deg degrees a side as densities; host only.  With npix =
+    read["npix"], theta = angle_deg * pi / 180 and the pixel side d = theta / npix, each one f64 expression:
+      v0 = faces / npix^2                              the area fraction
+      v1 = boundary * d / (4 * theta^2)                a quarter of the outline's length inside the field per area
+      v1_with_border = (boundary + border) * d / (4 * theta^2)   the same with the part on the map's rim
+      v2 = euler / theta^2                             the Euler characteristic per area
+    v1 is the Manhattan length of a pixelised outline: for an isotropic smooth field it overestimates the length of the
+    smooth contour by about 4 / pi.  That is reported as it is, not corrected."""
+    npix = int(read["npix"])
+    theta = float(angle_deg) * math.pi / 180.0
+    d = theta / npix
+    f64 = lambda k: np.asarray(read[k], np.int64).astype(np.float64)
+    return {"thresholds": np.array(read["thresholds"], np.float64),
+            "v0": f64("faces") / (float(npix) * float(npix)),
+            "v1": f64("boundary") * d / (4.0 * theta * theta),
+            "v1_with_border": (f64("boundary") + f64("border")) * d / (4.0 * theta * theta),
+            "v2": f64("euler") / (theta * theta)}
 
 
 SMOOTH_GAUSS, SMOOTH_MAP = 0, 1
