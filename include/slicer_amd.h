@@ -578,6 +578,64 @@ int slicer_minkowski_read(slicer_minkowski_handle mh, int64_t *faces, int64_t *e
                           int64_t *border, int64_t *n_nan);
 int slicer_minkowski_destroy(slicer_minkowski_handle mh);
 
+/* ---- Binned bispectra of a kappa map ----
+ * In the notation of the power spectra above (row N7): theta = angle_deg * pi / 180, khat = rfft2(kappa) in f64,
+ * l_f = 2 pi / theta, edges r_0 < ... < r_B in units of l_f (edges = NULL: 0, 1, ..., npix-1 with n_edges = npix), and a
+ * mode is in bin b by the rule of slicer_power_bins: r_b * r_b <= m2 < r_{b+1} * r_{b+1} on the integer m2, the squares
+ * rounded to f64, the last bin closed on the right.  One exception: the mode m2 = 0 is in no bin (the mean never enters a
+ * bispectrum).  Per bin b, both kept in f64 and never rounded to f32 (the normalisation below cancels heavily for thin
+ * triangles):
+ *   F_b = irfft2(khat * 1[mode in b]),   I_b = irfft2(1[mode in b]),   s = (npix, npix)
+ * and per triple i <= j <= k of bins
+ *   S_ijk = sum over the pixels of F_i F_j F_k,   T_ijk = npix^4 * sum over the pixels of I_i I_j I_k,
+ *   B_ijk = theta^4 / npix^6 * (npix^4 S_ijk) / T_ijk          (the convention of C = theta^2 / npix^4 |khat|^2).
+ * In exact arithmetic T_ijk is an integer: the number of ordered triples (l1 in i, l2 in j, l3 in k) of modes of the full
+ * npix x npix plane with l1 + l2 + l3 = 0 modulo npix on both axes, and npix^4 S_ijk is the sum of
+ * khat(l1) khat(l2) khat(l3) over those same triangles.  Triangles that close only modulo npix are counted by S and by T
+ * alike; edges at or below npix / 3 avoid them.  A triple whose T reads below 0.5 has no closed triangle: its B is NaN.
+ * A triple list is n_triples rows (i, j, k) of int32 with 0 <= i <= j <= k < B (otherwise SLICER_ERR_ARG); it may repeat
+ * a triple.  triples = NULL: all B (B + 1) (B + 2) / 6 triples in lexicographic order (n_triples must be that number).
+ *   slicer_bispectrum_triangles  the exact T of every triple of the list, host only (no device; messages through
+ *                                slicer_last_error(NULL)): an enumeration of the modes of bins i and j with a table
+ *                                lookup of -l1 - l2.  Bad edges are refused as by slicer_power_bins, npix outside
+ *                                1..16384 and a bad triple with SLICER_ERR_ARG; more than 2^31 mode pairs (the sum of
+ *                                N_i N_j over the triples, N the full-plane modes of a bin): SLICER_ERR_UNSUPPORTED
+ *   slicer_bispectrum_create     on the device and stream of h (create it after any slicer_set_stream, destroy it before
+ *                                h); reads the shear_split option.  Refused before any allocation: an npix that
+ *                                slicer_shear_supported rejects, more than 32 bins or more than 2^20 triples
+ *                                (SLICER_ERR_UNSUPPORTED); bad edges, a bad triple, an angle that is not positive and
+ *                                finite (SLICER_ERR_ARG).  T is computed here, once, on the device, from the I_b in the
+ *                                buffer that the runs then use for the F_b; it waits for the stream.  Device memory
+ *                                (SLICER_ERR_NOMEM): B maps of 8 npix^2 bytes, one spectrum of 16 npix (npix/2+1) bytes,
+ *                                the transform's buffers, and 8 n_triples bytes per chunk of pixels (at most 1024 chunks,
+ *                                of at least 4096 pixels)
+ *   slicer_bispectrum_run        a device f32 map (e.g. slicer_kappa_device_map); enqueued, no synchronisation
+ *   slicer_bispectrum_read       b, triangles (the T as the device summed them, not rounded) and sums (the raw S),
+ *                                [n_triples] each, any of them NULL; waits for the stream.  triangles can be read right
+ *                                after create; b and sums before any run: SLICER_ERR_STATE
+ *   slicer_bispectrum_spectrum   khat of the last run, [npix][npix/2+1] (re, im) f64 pairs, bitwise equal to
+ *                                slicer_shear_spectrum under the same shear_split; waits for the stream
+ *   slicer_bispectrum_read_map   F_bin of the last run, [npix][npix] f64; waits for the stream
+ * No atomics: the same input gives bitwise the same output, run after run; the S of a triple does not depend on which
+ * other triples are in the list; an input pointer off the 16-byte grid gives the same bits; shear_split 0 and 1 give the
+ * same bits of b, triangles, sums and the maps.  (shear_split reorders the transform's butterflies and with them the last
+ * bits of slicer_shear_spectrum, so every result here comes from the unsplit plan; with shear_split = 1 the map is
+ * transformed once more with the split plan, and that is the spectrum slicer_bispectrum_spectrum reports: it differs
+ * from the one behind the results by the transform's rounding, and costs a second plan's buffers.)  Products
+ * associate as (F_i F_j) F_k; the sums are blocked (64 products, then the blocks of a chunk, a butterfly over 64 lanes,
+ * then the chunks in index order in 64 runs and a second butterfly). */
+typedef struct slicer_bispectrum_s *slicer_bispectrum_handle;
+#define SLICER_BISPECTRUM_MAX_BINS 32
+int slicer_bispectrum_triangles(int32_t npix, int32_t n_edges, const double *edges, int32_t n_triples,
+                                const int32_t *triples /* [n_triples][3] or NULL */, int64_t *out);
+int slicer_bispectrum_create(slicer_handle h, int32_t npix, double angle_deg, int32_t n_edges, const double *edges,
+                             int32_t n_triples, const int32_t *triples, slicer_bispectrum_handle *out);
+int slicer_bispectrum_run(slicer_bispectrum_handle bh, const float *d_map);
+int slicer_bispectrum_read(slicer_bispectrum_handle bh, double *b, double *triangles, double *sums);
+int slicer_bispectrum_spectrum(slicer_bispectrum_handle bh, double *host);
+int slicer_bispectrum_read_map(slicer_bispectrum_handle bh, int32_t bin, double *host);
+int slicer_bispectrum_destroy(slicer_bispectrum_handle bh);
+
 /* ---- Multi-plane ray tracing through the lens planes ----
  * One ray per pixel of an npix^2 grid (axis 0 slow = component 1, axis 1 contiguous = component 2, as for N6 and N8), on the
  * device and stream of h (create it after any slicer_set_stream, destroy it before h).  State per ray, 12 f64: position

@@ -14,6 +14,7 @@ from .lensing import (FD_ALPHA1, FD_ALPHA2, FD_COUNT, FD_GAMMA, FD_GAMMA1, FD_GA
 from .lensing import HALVE_MEAN, HALVE_SUM, MOMENTS_ORDERS, Moments, combine_moments, moments_depth  # noqa: F401
 from .lensing import PEAKS_MAX_BINS, Peaks, peaks_edges  # noqa: F401
 from .lensing import MINKOWSKI_MAX_THRESHOLDS, Minkowski, minkowski_functionals  # noqa: F401
+from .lensing import BISPECTRUM_MAX_BINS, Bispectrum, bispectrum_triangles, bispectrum_triples  # noqa: F401
 from .lensing import SMOOTH_GAUSS, SMOOTH_MAP, SMOOTH_MAX_RADIUS, Smooth, smooth_weights  # noqa: F401
 from .lensing import Noise, noise_sigma_pix, noise_words, smooth_noise_gain  # noqa: F401
 from .lensing import (RAYS_COUNT, RAYS_DEFLECTION1, RAYS_DEFLECTION2, RAYS_GAMMA1, RAYS_GAMMA2, RAYS_KAPPA,  # noqa: F401

@@ -29,6 +29,10 @@
 //     the edges of `bins` (1 ... 1024) uniform bins from lo to hi; with --moments also of every level of its pyramid of
 //     block means; with --smooth and / or --shape-noise also .smooth_minkowski_, .noisy_minkowski_ and
 //     .noisy_smooth_minkowski_, where --peaks writes its tables of those maps.
+//   * --bispectrum all|equilateral with --bispectrum-edges r0,r1,... (required; 2 ... 33 edges in the units of
+//     --power-edges): <directory><simulation>.bl_<npix>_<suffix>.txt, the binned bispectrum B_ijk of every kappa map over
+//     all triples i <= j <= k of the bins or over the equilateral ones, with the number of closed triangles of every
+//     triple; nan marks a triple without one.  The smoothed and the noisy maps have none.
 //   * --smooth gauss|map:a1,a2,...: per source and per scale a_k (arcminutes; sigma = a_k npix / (60 ANGLE) pixels)
 //     the kappa map smoothed with a Gaussian truncated at 4 sigma (gauss) or turned into the aperture mass of the filter
 //     built from it (map), .<kind><k>_kappa_z..., with the kappa file's header and the keys SCALE (arcminutes) and RADIUS
@@ -137,6 +141,18 @@ int LensingOptions::parse(int argc, char **argv, int &i)
                 return bad("bad --power-edges (a comma-separated list of radii in units of l_f)");
             power_edges.push_back(r);
         }
+    } else if (a == "--bispectrum" && has_value) bispectrum = argv[++i];
+    else if (a == "--bispectrum-edges" && has_value) {
+        for (const string &tok : split(argv[++i])) {
+            char *end = nullptr;
+            const double r = strtod(tok.c_str(), &end);
+            if (tok.empty() || *end != '\0')
+                return bad("bad --bispectrum-edges (a comma-separated list of radii in units of l_f)");
+            bispectrum_edges.push_back(r);
+        }
+        if (bispectrum_edges.size() > SLICER_BISPECTRUM_MAX_BINS + 1)
+            return bad("bad --bispectrum-edges (" + std::to_string(bispectrum_edges.size()) + " edges, at most " +
+                       std::to_string(SLICER_BISPECTRUM_MAX_BINS + 1) + ")");
     } else if (a == "--moments") moments = true;
     else if (a == "--moments-levels") {
         if (!has_value)
@@ -199,6 +215,7 @@ int LensingOptions::parse(int argc, char **argv, int &i)
 int LensingOptions::check() const
 {
     const bool no_kappa = kappa.empty(), derivative = !shear_derivative.empty(), pw = !power.empty();
+    const bool bs = !bispectrum.empty();
     const std::pair<bool, const char *> rules[] = {
         {shear && no_kappa, "--shear needs --kappa (the shear maps are computed from the kappa maps)"},
         {raytrace && no_kappa, "--raytrace needs --kappa (the rays are observed at the source redshifts of the kappa maps)"},
@@ -208,6 +225,10 @@ int LensingOptions::check() const
         {pw && power != "auto" && power != "cross", "bad --power (auto or cross)"},
         {pw && no_kappa, "--power needs --kappa (the power spectra are those of the kappa maps)"},
         {!power_edges.empty() && !pw, "--power-edges needs --power"},
+        {bs && bispectrum != "all" && bispectrum != "equilateral", "bad --bispectrum (all or equilateral)"},
+        {bs && no_kappa, "--bispectrum needs --kappa (the bispectra are those of the kappa maps)"},
+        {!bispectrum_edges.empty() && !bs, "--bispectrum-edges needs --bispectrum"},
+        {bs && bispectrum_edges.empty(), "--bispectrum needs --bispectrum-edges (the bin edges in units of l_f)"},
         {moments && no_kappa, "--moments needs --kappa (the moments are those of the kappa maps)"},
         {moments_levels_given && !moments, "--moments-levels needs --moments"},
         {!peaks_edges.empty() && no_kappa, "--peaks needs --kappa (the histograms and peak counts are those of the kappa maps)"},
@@ -240,6 +261,14 @@ int LensingOptions::check_npix(const InputParams &p) const
         vector<double> mr(cnt.size());
         if (slicer_power_bins(p.npix, ne, power_edges_or_null(), cnt.data(), mr.data()) != SLICER_OK)
             return bad(string("--power-edges: ") + slicer_last_error(nullptr));
+    }
+    if (!bispectrum.empty() && !slicer_shear_supported(p.npix))
+        return bad("--bispectrum: " + npix + fft_sizes);
+    if (!bispectrum.empty()) {  // the edges
+        vector<int64_t> cnt(std::max<size_t>(bispectrum_edges.size(), 2) - 1);
+        vector<double> mr(cnt.size());
+        if (slicer_power_bins(p.npix, (int)bispectrum_edges.size(), bispectrum_edges.data(), cnt.data(), mr.data()) != SLICER_OK)
+            return bad(string("--bispectrum-edges: ") + slicer_last_error(nullptr));
     }
     if (moments) {  // the pyramid's depth
         int most = 0;
@@ -328,6 +357,17 @@ int LensingOutputs::create()
         slicer_minkowski_create(h, p.npix, (int)o.minkowski_thresholds.size(), o.minkowski_thresholds.data(), mkh.out()) !=
             SLICER_OK)
         return fail(h, "slicer_amd: --minkowski");
+    if (!o.bispectrum.empty()) {
+        const int B = (int)o.bispectrum_edges.size() - 1;
+        for (int i = 0; i < B; i++)
+            for (int j = i; j < B; j++)
+                for (int k = j; k < B; k++)
+                    if (o.bispectrum == "all" || (i == j && j == k))
+                        bispectrum_triples.insert(bispectrum_triples.end(), {i, j, k});
+        if (slicer_bispectrum_create(h, p.npix, p.fov, B + 1, o.bispectrum_edges.data(), (int)bispectrum_triples.size() / 3,
+                                     bispectrum_triples.data(), bsh.out()) != SLICER_OK)
+            return fail(h, "slicer_amd: --bispectrum");
+    }
     for (size_t k = 0; k < o.smooth_arcmin.size(); k++) {
         const double sigma = o.smooth_sigma_pix(k, p.npix, p.fov);
         smooth_radius.push_back(0);
@@ -489,6 +529,8 @@ int LensingOutputs::write()
             return rc;
     }
     if (const int rc = ph ? power_spectra() : 0)
+        return rc;
+    if (const int rc = bsh ? bispectra() : 0)
         return rc;
     if (mh && write_table("moments", ".moments_", moments))
         return 1;
@@ -778,6 +820,47 @@ int LensingOutputs::power_spectra()
         add(cl, "\n");
     }
     return write_table("power spectra", ".cl_", cl);
+}
+
+// The bispectra table: '#' lines (npix, angle, source redshifts, the bin edges in multipoles, column names), then per
+// triple i j k, the mean multipole of each of its bins, the number of closed triangles (the device's sum, rounded) and B
+// of every source (%.17g; nan for a triple without a closed triangle).  One handle, one source after the other.
+int LensingOutputs::bispectra()
+{
+    const char *who = "slicer_amd: --bispectrum";
+    const int S = (int)plan.zs.size(), B = (int)o.bispectrum_edges.size() - 1;
+    const size_t n = bispectrum_triples.size() / 3;
+    vector<double> b(S * n), triangles(n), mean(B);
+    vector<int64_t> counts(B);
+    if (slicer_power_bins(p.npix, B + 1, o.bispectrum_edges.data(), counts.data(), mean.data()) != SLICER_OK)
+        return fail(nullptr, who);
+    for (int s = 0; s < S; s++) {
+        float *d_kappa = nullptr;
+        if (slicer_kappa_device_map(kh, s, &d_kappa) != SLICER_OK || slicer_bispectrum_run(bsh, d_kappa) != SLICER_OK ||
+            slicer_bispectrum_read(bsh, &b[s * n], triangles.data(), nullptr) != SLICER_OK)
+            return fail(h, who);
+    }
+    const double ell_f = 2.0 * M_PI / (p.fov * M_PI / 180.0);
+    string bl;
+    add(bl, "# npix %d\n# angle_deg %.17g\n# zs", p.npix, p.fov);
+    for (double z : plan.zs)
+        add(bl, " %.17g", z);
+    add(bl, "\n# ell_edges");
+    for (double r : o.bispectrum_edges)
+        add(bl, " %.17g", r * ell_f);
+    add(bl, "\n# i j k ell_mean_i ell_mean_j ell_mean_k n_triangles");
+    for (int s = 0; s < S; s++)
+        add(bl, " B_%d", s);
+    add(bl, "\n");
+    for (size_t t = 0; t < n; t++) {
+        const int32_t *r = &bispectrum_triples[3 * t];
+        add(bl, "%d %d %d %.17g %.17g %.17g %lld", (int)r[0], (int)r[1], (int)r[2], ell_f * mean[r[0]], ell_f * mean[r[1]],
+            ell_f * mean[r[2]], (long long)llrint(triangles[t]));
+        for (int s = 0; s < S; s++)
+            add(bl, " %.17g", b[s * n + t]);
+        add(bl, "\n");
+    }
+    return write_table("bispectra", ".bl_", bl);
 }
 
 // "Saving the <what> on:" <directory><simulation><token><npix>_<suffix>.txt, then the file; 0, or 1 after the message

@@ -1,6 +1,6 @@
 // driver_lensing.hpp -- the lensing outputs of the SLICER_amd driver (slicer_main.cpp): their options, their host
 // planning and the device-0 work behind --kappa, --shear, --deflection, --raytrace, --power, --moments, --peaks,
-// --minkowski, --smooth and --shape-noise (driver_lensing.cpp describes the options), with the small helpers the rest of the driver shares with them.
+// --minkowski, --bispectrum, --smooth and --shape-noise (driver_lensing.cpp describes the options), with the small helpers the rest of the driver shares with them.
 #pragma once
 #include <deque>
 #include <string>
@@ -24,6 +24,8 @@ struct LensingOptions {
     int moments_levels = 0;
     std::vector<double> peaks_edges;  // empty: no --peaks
     std::vector<double> minkowski_thresholds;  // empty: no --minkowski
+    std::string bispectrum;                 // "" (no --bispectrum), "all" or "equilateral"
+    std::vector<double> bispectrum_edges;   // --bispectrum-edges, required with it: at most 33
     std::string smooth_kind;             // "" (no --smooth), "gauss" or "map"
     std::vector<double> smooth_arcmin;   // its scales
     bool shape_noise = false;            // --shape-noise sigma_e,ngal[,seed[,nreal]]
@@ -101,6 +103,8 @@ struct LensingOutputs {
     Owned<slicer_moments_handle, slicer_moments_destroy> mh{};
     Owned<slicer_peaks_handle, slicer_peaks_destroy> pkh{};
     Owned<slicer_minkowski_handle, slicer_minkowski_destroy> mkh{};
+    Owned<slicer_bispectrum_handle, slicer_bispectrum_destroy> bsh{};  // --bispectrum: one handle, source after source
+    std::vector<int32_t> bispectrum_triples{};                         // its list, rows (i, j, k)
     std::deque<Owned<slicer_smooth_handle, slicer_smooth_destroy>> smh{};  // --smooth: one per scale
     std::vector<int32_t> smooth_radius{};
     // --shape-noise: one handle for all sources, the noise of a pixel, the gain of every --smooth scale on it, and the
@@ -151,6 +155,7 @@ private:
     int source_noise(size_t s, const float *d_kappa);
     int source_shear(size_t s, const float *d_kappa);
     int power_spectra();
+    int bispectra();
     int write_table(const char *what, const char *token, const std::string &text) const;
 };
 

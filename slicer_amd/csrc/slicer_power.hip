@@ -196,7 +196,9 @@ __global__ void k_power_finish(const double *partial, const int *slice_off, cons
     cl[(size_t)(pair0 + q) * B + b] = nmodes[b] > 0.0 ? sum / nmodes[b] * norm : (double)NAN;
 }
 
-// The edges, or 0 .. npix-1 for NULL (then n_edges must be npix); "" if they are usable, else why not.
+}  // namespace
+
+// The edges, or 0 .. npix-1 for NULL (then n_edges must be npix); "" if they are usable, else why not (slicer_fft.hpp).
 const char *check_edges(int npix, int n_edges, const double *edges, std::vector<double> &out)
 {
     if (n_edges < 2)
@@ -218,6 +220,8 @@ const char *check_edges(int npix, int n_edges, const double *edges, std::vector<
     }
     return "";
 }
+
+namespace {
 
 // N_b and the sum of sqrt(m2) over every mode of the half plane (host; long double sums)
 void bin_modes(int n, const std::vector<double> &edges, std::vector<int64_t> &counts, std::vector<double> &mean)

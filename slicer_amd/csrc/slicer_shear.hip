@@ -20,7 +20,9 @@
 // alpha1 = i K0 phihat and alpha2 = i K1 phihat, then the same column and row chains with the plain f32 store.
 // Twiddles: one f64 table W_n^j = exp(-2 pi i j / n), j < n, from long-double sincos on the host.  No atomics and
 // no work handed between workgroups: the results are bitwise repeatable.  The plan and the forward chains are shared
-// with the power-spectrum handle (slicer_power.hip) through slicer_fft.hpp.
+// with the power-spectrum handle (slicer_power.hip) through slicer_fft.hpp.  The bispectrum handle (slicer_bispectrum.hip,
+// row N15) also runs the inverse chains, through slicer_fft_inverse_band: a band load instead of the filter and an f64
+// store instead of the f32 one, both compiled into a second instantiation of k_fft_pass only.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -41,8 +43,10 @@ constexpr int kColCap = kLdsPoints / 8;          // column passes: at least 8 ad
 constexpr int kMaxLines = 64;
 constexpr int kMaxStages = 16;
 
-enum Load { L_COMPLEX = 0, L_REAL_EVEN, L_REAL_PAIR, L_SPLIT_EVEN, L_SPLIT_PAIR, L_FILTER, L_C2R_EVEN, L_C2R_PAIR };
-enum Store { S_COMPLEX = 0, S_REAL_EVEN, S_REAL_PAIR, S_GAMMA_EVEN, S_GAMMA_PAIR };
+enum Load { L_COMPLEX = 0, L_REAL_EVEN, L_REAL_PAIR, L_SPLIT_EVEN, L_SPLIT_PAIR, L_FILTER, L_C2R_EVEN, L_C2R_PAIR, L_BAND };
+enum Store { S_COMPLEX = 0, S_REAL_EVEN, S_REAL_PAIR, S_GAMMA_EVEN, S_GAMMA_PAIR, S_REAL64_EVEN, S_REAL64_PAIR };
+// L_BAND and S_REAL64_* (slicer_fft_inverse_band) exist only in the BAND instantiation of k_fft_pass: the kernel behind
+// the shear, deflection and power outputs is compiled without them and keeps its registers.
 
 struct PassArgs {
     const void *in;
@@ -58,7 +62,9 @@ struct PassArgs {
     int filt;                          // L_FILTER: SLICER_SHEAR_PHI / _GAMMA1 / _GAMMA2 / _ALPHA1 / _ALPHA2
     double phi_c;                      // L_FILTER phi: -2 / (2 pi / theta)^2
     double alpha_c;                    // L_FILTER alpha: -2 / (2 pi / theta)
-    double scale;                      // S_REAL_* / S_GAMMA_*: 1 / n^2
+    double scale;                      // S_REAL_* / S_GAMMA_* / S_REAL64_*: 1 / n^2
+    double band_lo2, band_hi2;         // L_BAND: the mode is kept iff lo2 <= m2 < hi2 (<= with band_closed) and m2 != 0
+    int band_closed, band_ones;        // L_BAND: band_ones = the spectrum is not read, every kept mode is 1
     int nst;
     int rad[kMaxStages];
 };
@@ -78,9 +84,18 @@ __device__ inline double2 twid(const PassArgs &a, int x, int M)
     return a.inv ? conjg(w) : w;
 }
 
+template <bool BAND>
 __device__ double2 load_point(const PassArgs &a, int l, int e)
 {
     const int n = a.n, H = a.H;
+    if (BAND && a.load == L_BAND) {  // khat[e][l] (or 1) inside the band of the exact integer m2, 0 outside and at m2 = 0
+        const double f0 = (double)(e < (n + 1) / 2 ? e : e - n), f1 = (double)l;
+        const double m2 = f0 * f0 + f1 * f1;  // exact: integers below 2^28
+        const bool in = m2 != 0.0 && m2 >= a.band_lo2 && (a.band_closed ? m2 <= a.band_hi2 : m2 < a.band_hi2);
+        if (!in)
+            return make_double2(0.0, 0.0);
+        return a.band_ones ? make_double2(1.0, 0.0) : ((const double2 *)a.in)[(size_t)e * H + l];
+    }
     switch (a.load) {
     case L_REAL_EVEN: {  // row l: x[2e] + i x[2e+1]
         const float *k = (const float *)a.in + (size_t)l * n + 2 * e;
@@ -155,9 +170,23 @@ __device__ double2 load_point(const PassArgs &a, int l, int e)
     }
 }
 
+template <bool BAND>
 __device__ void store_point(const PassArgs &a, int l, int e, double2 v)
 {
     const int n = a.n;
+    if (BAND && a.store == S_REAL64_EVEN) {  // S_REAL_EVEN without the cast
+        double *o = (double *)a.out + (size_t)l * n + 2 * e;
+        o[0] = v.x * a.scale;
+        o[1] = v.y * a.scale;
+        return;
+    }
+    if (BAND && a.store == S_REAL64_PAIR) {  // S_REAL_PAIR without the cast
+        double *o = (double *)a.out + (size_t)(2 * l) * n + e;
+        o[0] = v.x * a.scale;
+        if (2 * l + 1 < n)
+            o[n] = v.y * a.scale;
+        return;
+    }
     switch (a.store) {
     case S_REAL_EVEN: {
         float *o = (float *)a.out + (size_t)l * n + 2 * e;
@@ -249,6 +278,7 @@ __device__ void lds_stage(const PassArgs &a, double2 *lds, int C, int R, int Ns)
     __syncthreads();
 }
 
+template <bool BAND>
 __global__ __launch_bounds__(kThreads) void k_fft_pass(PassArgs a)
 {
     extern __shared__ double2 lds[];
@@ -257,7 +287,7 @@ __global__ __launch_bounds__(kThreads) void k_fft_pass(PassArgs a)
         const int c = a.cfast ? t % C : t / R, r = a.cfast ? t / C : t % R, l = l0 + c;
         double2 v = make_double2(0.0, 0.0);
         if (l < a.nlines) {
-            v = load_point(a, l, j + r * stride);
+            v = load_point<BAND>(a, l, j + r * stride);
             if (k && r)
                 v = cmul(v, twid(a, r * k, a.Ns * R));
         }
@@ -280,7 +310,7 @@ __global__ __launch_bounds__(kThreads) void k_fft_pass(PassArgs a)
     for (int t = threadIdx.x; t < C * R; t += kThreads) {
         const int c = a.cfast ? t % C : t / R, q = a.cfast ? t / C : t % R, l = l0 + c;
         if (l < a.nlines)
-            store_point(a, l, base + q * a.Ns, lds[c * a.Rp + q]);
+            store_point<BAND>(a, l, base + q * a.Ns, lds[c * a.Rp + q]);
     }
 }
 
@@ -405,7 +435,10 @@ int run_chain(slicer_fft_s *f, hipStream_t st, const std::vector<Pass> &passes, 
         }
         const size_t lds = (size_t)ps.C * ps.Rp * sizeof(double2);
         const dim3 grid((unsigned)((a.nlines + ps.C - 1) / ps.C), (unsigned)(a.L / ps.R));
-        hipLaunchKernelGGL(k_fft_pass, grid, dim3(kThreads), lds, st, a);
+        if (a.load == L_BAND || a.store == S_REAL64_EVEN || a.store == S_REAL64_PAIR)
+            hipLaunchKernelGGL(k_fft_pass<true>, grid, dim3(kThreads), lds, st, a);
+        else
+            hipLaunchKernelGGL(k_fft_pass<false>, grid, dim3(kThreads), lds, st, a);
         HIPCHK(f->h, hipGetLastError());
         in = a.out;
     }
@@ -434,9 +467,10 @@ int slicer_fft_create(slicer_handle h, int npix, int split, hipStream_t st, int 
     const size_t passes = std::max(f->row_chain.size(), f->col_chain.size());
 
     int rc = SLICER_OK;
-    if (hipFuncSetAttribute((const void *)k_fft_pass, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)((kLdsPoints + kMaxLines) * sizeof(double2))) != hipSuccess)
-        rc = fail(h, SLICER_ERR_HIP, "%s: cannot raise the LDS limit of the FFT kernel", who);
+    for (const void *kernel : {(const void *)k_fft_pass<false>, (const void *)k_fft_pass<true>})
+        if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)((kLdsPoints + kMaxLines) * sizeof(double2))) != hipSuccess)
+            rc = fail(h, SLICER_ERR_HIP, "%s: cannot raise the LDS limit of the FFT kernel", who);
     const size_t cbytes = (size_t)n * f->H * sizeof(double2);
     rc = f->mem.alloc(rc, h, who, (void **)&f->tw, (size_t)n * sizeof(double2));
     rc = f->mem.alloc(rc, h, who, (void **)&f->A, cbytes);
@@ -475,6 +509,24 @@ int slicer_fft_forward(slicer_fft_s *f, hipStream_t st, const float *map, double
         return rc;
     e = End{f->A, khat, even ? L_SPLIT_EVEN : L_SPLIT_PAIR, S_COMPLEX, 0, 0, 1, f->H};
     return run_chain(f, st, f->col_chain, true, false, e, proto);
+}
+
+int slicer_fft_inverse_band(slicer_fft_s *f, hipStream_t st, const double2 *khat, double lo2, double hi2, int closed,
+                            double *out)
+{
+    const bool even = f->n % 2 == 0;
+    PassArgs p{};
+    p.band_lo2 = lo2;
+    p.band_hi2 = hi2;
+    p.band_closed = closed;
+    p.band_ones = khat == nullptr;
+    p.scale = 1.0 / ((double)f->n * (double)f->n);
+    // band + columns khat -> A; c2r rows A -> out, as the shear handle's inverses with the f64 store
+    End e{khat, f->A, L_BAND, S_COMPLEX, 0, 0, 1, f->H};
+    if (int rc = run_chain(f, st, f->col_chain, true, true, e, p))
+        return rc;
+    e = End{f->A, out, even ? L_C2R_EVEN : L_C2R_PAIR, even ? S_REAL64_EVEN : S_REAL64_PAIR, 0, 0, 0, 0};
+    return run_chain(f, st, f->row_chain, false, true, e, p);
 }
 
 void slicer_fft_destroy(slicer_fft_s *f) { delete f; }

@@ -4,7 +4,7 @@ maps and finite-difference derivatives of the potential (row N8), and the centra
 of 2x2 halvings (row N9), and the one-point PDF histogram and peak / minimum counts of such maps (row N10), and
 multi-plane ray tracing through the lens planes (row N11), and Gaussian and aperture-mass smoothing of such maps (row N12),
 and shape noise for such maps from a counter-based generator (row N13), and the Minkowski functionals of such maps'
-excursion sets as exact counts (row N14).
+excursion sets as exact counts (row N14), and the binned bispectra of such maps (row N15).
 
 plane_weights wraps the host weights of include/slicer_amd.h (slicer_lensing_weights); Kappa is the device accumulator
 (slicer_kappa_*) bound to a Slicer handle: it reads the finalized plane maps where they are, in HBM.  Shear (slicer_shear_*)
@@ -16,7 +16,8 @@ map's pixels, peaks and minima by height over a list of edges; Rays (slicer_rays
 the planes' deflection, convergence and shear maps (plane_strengths scales a mass plane to its lens map); Smooth
 (slicer_smooth_*) filters a map with a truncated Gaussian or with the aperture-mass filter built from it; Noise
 (slicer_noise_*) adds Gaussian noise that is a pure function of (seed, stream, realisation, pixel) to a map;
-Minkowski (slicer_minkowski_*) counts the faces, edges and vertices of the pixel complex that lie in the sets x >= t_j.
+Minkowski (slicer_minkowski_*) counts the faces, edges and vertices of the pixel complex that lie in the sets x >= t_j;
+Bispectrum (slicer_bispectrum_*) contracts the band-filtered f64 maps of a map over a list of bin triples.
 """
 import ctypes as C
 import math
@@ -543,6 +544,101 @@ def minkowski_functionals(read, angle_deg):
             "v1": f64("boundary") * d / (4.0 * theta * theta),
             "v1_with_border": (f64("boundary") + f64("border")) * d / (4.0 * theta * theta),
             "v2": f64("euler") / (theta * theta)}
+
+
+BISPECTRUM_MAX_BINS = 32
+
+
+def bispectrum_triples(n_bins, kind="all"):
+    """The triples i <= j <= k of n_bins bins, int32 [n, 3]: "all" B (B + 1) (B + 2) / 6 of them in lexicographic order,
+    or the "equilateral" ones (b, b, b)."""
+    B = int(n_bins)
+    if kind == "equilateral":
+        t = [(b, b, b) for b in range(B)]
+    elif kind == "all":
+        t = [(i, j, k) for i in range(B) for j in range(i, B) for k in range(j, B)]
+    else:
+        raise ValueError('kind: "all" or "equilateral"')
+    return np.array(t, np.int32).reshape(-1, 3)
+
+
+def _triples(n_bins, triples):
+    """int32 [n, 3] from "all", "equilateral", None (all) or an array of rows (i, j, k)."""
+    if triples is None or isinstance(triples, str):
+        return bispectrum_triples(n_bins, "all" if triples is None else triples)
+    t = np.ascontiguousarray(triples, np.int32)
+    if t.ndim != 2 or t.shape[1] != 3:
+        raise ValueError("triples: rows (i, j, k)")
+    return t
+
+
+def bispectrum_triangles(npix, edges=None, triples=None):
+    """Host only (no device): the exact number of closed triangles T_ijk (int64) of every triple (None: all of them) for
+    the edges (units of l_f; None: 0, 1, ..., npix - 1), by enumeration (slicer_bispectrum_triangles)."""
+    n_edges, e = _edges(npix, edges, None, 1.0)
+    t = _triples(max(n_edges - 1, 0), triples)
+    out = np.zeros(t.shape[0], np.int64)
+    _host_chk(_L.slicer_bispectrum_triangles(int(npix), n_edges, _dptr(e), t.shape[0], _dptr(t), out.ctypes.data))
+    return out
+
+
+class Bispectrum(_SubHandle):
+    """Binned bispectra B_ijk of an npix^2 map of side angle_deg degrees over a list of bin triples, on the device of
+    `slicer`, on its stream.  edges in units of l_f = 2 pi / theta, or ell_edges in multipoles,
+    at most 32 bins; triples "all", "equilateral" or rows (i, j, k) with i <= j <= k."""
+    _handle, _destroy = "_bh", "slicer_bispectrum_destroy"
+
+    def __init__(self, slicer: Slicer, npix, angle_deg, edges=None, ell_edges=None, triples="all"):
+        self._s = slicer
+        self.npix, self.angle_deg = int(npix), float(angle_deg)
+        ok = math.isfinite(self.angle_deg) and self.angle_deg > 0  # otherwise slicer_bispectrum_create refuses it
+        self.ell_f = ell_fundamental(self.angle_deg) if ok else math.nan
+        n_edges, e = _edges(self.npix, edges, ell_edges, self.angle_deg)
+        self.edges = np.arange(self.npix, dtype=np.float64) if e is None else e.copy()
+        self.n_bins = n_edges - 1
+        # (more than 32 bins: "all" would be a long list that the create call refuses anyway, so it gets one triple)
+        many = self.n_bins > BISPECTRUM_MAX_BINS and (triples is None or isinstance(triples, str))
+        self.triples = np.zeros((1, 3), np.int32) if many else _triples(self.n_bins, triples)
+        bh = C.c_void_p()
+        slicer._chk(_L.slicer_bispectrum_create(slicer._h, self.npix, self.angle_deg, n_edges, _dptr(e),
+                                                self.triples.shape[0], _dptr(self.triples), C.byref(bh)))
+        self._bh = bh
+
+    def run(self, d_map):
+        """d_map: device address of an f32 npix^2 map."""
+        self._s._chk(_L.slicer_bispectrum_run(self._bh, None if d_map is None else int(d_map)))
+
+    def run_kappa(self, kappa: Kappa, s):
+        """The map of source s of a Kappa accumulator, where it is."""
+        self.run(kappa.device_map(s))
+
+    def triangles(self):
+        """T_ijk as the device summed them at create (f64, not rounded); readable before any run."""
+        t = np.empty(self.triples.shape[0], np.float64)
+        self._s._chk(_L.slicer_bispectrum_read(self._bh, None, t.ctypes.data, None))
+        return t
+
+    def read(self):
+        """dict: b (B_ijk, NaN for a triple without a closed triangle), triangles (T_ijk), sums (the raw S_ijk), triples
+        [n, 3], and per bin ell_mean and counts (the half-plane modes, m2 = 0 included) from power_bins."""
+        n = self.triples.shape[0]
+        b, t, s = (np.empty(n, np.float64) for _ in range(3))
+        self._s._chk(_L.slicer_bispectrum_read(self._bh, b.ctypes.data, t.ctypes.data, s.ctypes.data))
+        bins = power_bins(self.npix, self.edges)
+        return {"b": b, "triangles": t, "sums": s, "triples": self.triples.copy(),
+                "ell_mean": bins["mean_radius"] * self.ell_f, "counts": bins["counts"]}
+
+    def spectrum(self):
+        """rfft2 of the last run's input, [npix, npix // 2 + 1] complex128."""
+        out = np.empty((self.npix, self.npix // 2 + 1), np.complex128)
+        self._s._chk(_L.slicer_bispectrum_spectrum(self._bh, out.ctypes.data))
+        return out
+
+    def read_map(self, bin):
+        """F_bin of the last run, f64 [npix, npix]."""
+        out = np.empty((self.npix, self.npix), np.float64)
+        self._s._chk(_L.slicer_bispectrum_read_map(self._bh, int(bin), out.ctypes.data))
+        return out
 
 
 SMOOTH_GAUSS, SMOOTH_MAP = 0, 1
