@@ -104,16 +104,35 @@ __attribute__((format(printf, 2, 3))) static void add(string &text, const char *
     text += piece;
 }
 
+// the whole of `token` as a double: false for an empty token and for one with anything after the number
+static bool whole_double(const string &token, double *v)
+{
+    char *end = nullptr;
+    *v = strtod(token.c_str(), &end);
+    return !token.empty() && *end == '\0';
+}
+
+// a comma-separated list of doubles onto the end of `out`: false at the first piece that is not one
+static bool parse_doubles(const char *value, vector<double> &out)
+{
+    for (const string &tok : split(value)) {
+        double v;
+        if (!whole_double(tok, &v))
+            return false;
+        out.push_back(v);
+    }
+    return true;
+}
+
 // The value lo,hi,bins of `option` into the bins + 1 uniform edges of slicer_peaks_edges: 0, or 2 after the message
 static int uniform_edges(const string &option, const char *value, const char *meaning, vector<double> &edges)
 {
     const vector<string> tok = value ? split(value) : vector<string>{};
-    char *e0 = nullptr, *e1 = nullptr, *e2 = nullptr;
-    const double lo = tok.size() == 3 ? strtod(tok[0].c_str(), &e0) : 0.0;
-    const double hi = tok.size() == 3 ? strtod(tok[1].c_str(), &e1) : 0.0;
-    const long bins = tok.size() == 3 ? strtol(tok[2].c_str(), &e2, 10) : 0;
-    if (tok.size() != 3 || tok[0].empty() || tok[1].empty() || tok[2].empty() || *e0 != '\0' || *e1 != '\0' ||
-        *e2 != '\0' || bins < 1 || bins > SLICER_PEAKS_MAX_BINS)
+    double lo = 0.0, hi = 0.0;
+    char *end = nullptr;
+    const bool three = tok.size() == 3 && whole_double(tok[0], &lo) && whole_double(tok[1], &hi) && !tok[2].empty();
+    const long bins = three ? strtol(tok[2].c_str(), &end, 10) : 0;
+    if (!three || *end != '\0' || bins < 1 || bins > SLICER_PEAKS_MAX_BINS)
         return bad("bad " + option + " (lo,hi,bins: " + meaning + " and the number of bins, 1 ... " +
                    std::to_string(SLICER_PEAKS_MAX_BINS) + ")");
     edges.resize(bins + 1);
@@ -134,22 +153,12 @@ int LensingOptions::parse(int argc, char **argv, int &i)
     else if (a == "--shear-derivative" && has_value) shear_derivative = argv[++i];
     else if (a == "--power" && has_value) power = argv[++i];
     else if (a == "--power-edges" && has_value) {
-        for (const string &tok : split(argv[++i])) {
-            char *end = nullptr;
-            const double r = strtod(tok.c_str(), &end);
-            if (tok.empty() || *end != '\0')
-                return bad("bad --power-edges (a comma-separated list of radii in units of l_f)");
-            power_edges.push_back(r);
-        }
+        if (!parse_doubles(argv[++i], power_edges))
+            return bad("bad --power-edges (a comma-separated list of radii in units of l_f)");
     } else if (a == "--bispectrum" && has_value) bispectrum = argv[++i];
     else if (a == "--bispectrum-edges" && has_value) {
-        for (const string &tok : split(argv[++i])) {
-            char *end = nullptr;
-            const double r = strtod(tok.c_str(), &end);
-            if (tok.empty() || *end != '\0')
-                return bad("bad --bispectrum-edges (a comma-separated list of radii in units of l_f)");
-            bispectrum_edges.push_back(r);
-        }
+        if (!parse_doubles(argv[++i], bispectrum_edges))
+            return bad("bad --bispectrum-edges (a comma-separated list of radii in units of l_f)");
         if (bispectrum_edges.size() > SLICER_BISPECTRUM_MAX_BINS + 1)
             return bad("bad --bispectrum-edges (" + std::to_string(bispectrum_edges.size()) + " edges, at most " +
                        std::to_string(SLICER_BISPECTRUM_MAX_BINS + 1) + ")");
@@ -176,9 +185,8 @@ int LensingOptions::parse(int argc, char **argv, int &i)
         smooth_kind = v.substr(0, colon);
         smooth_arcmin.clear();
         for (const string &tok : colon == string::npos ? vector<string>{} : split(v.substr(colon + 1))) {
-            char *end = nullptr;
-            smooth_arcmin.push_back(strtod(tok.c_str(), &end));
-            if (tok.empty() || *end != '\0' || !std::isfinite(smooth_arcmin.back()) || !(smooth_arcmin.back() > 0))
+            smooth_arcmin.push_back(0.0);
+            if (!whole_double(tok, &smooth_arcmin.back()) || !std::isfinite(smooth_arcmin.back()) || !(smooth_arcmin.back() > 0))
                 smooth_arcmin.clear();
             if (smooth_arcmin.empty())
                 break;
@@ -194,14 +202,13 @@ int LensingOptions::parse(int argc, char **argv, int &i)
         for (const string &t : tok)
             if (t.empty() || t[0] == '-' || t[0] == '+' || isspace((unsigned char)t[0]))
                 return bad(usage);
-        char *e0 = nullptr, *e1 = nullptr, *e2 = nullptr, *e3 = nullptr;
-        noise_sigma_e = strtod(tok[0].c_str(), &e0);
-        noise_ngal = strtod(tok[1].c_str(), &e1);
+        char *e2 = nullptr, *e3 = nullptr;
+        const bool sigma_whole = whole_double(tok[0], &noise_sigma_e), ngal_whole = whole_double(tok[1], &noise_ngal);
         errno = 0;
         const unsigned long long seed = tok.size() > 2 ? strtoull(tok[2].c_str(), &e2, 10) : 0;
         const bool seed_ok = tok.size() <= 2 || (*e2 == '\0' && errno == 0 && seed <= (unsigned long long)INT64_MAX);
         const long nreal = tok.size() > 3 ? strtol(tok[3].c_str(), &e3, 10) : 1;
-        if (*e0 != '\0' || *e1 != '\0' || !seed_ok || (tok.size() > 3 && *e3 != '\0') || nreal < 1 || nreal > 1024 ||
+        if (!sigma_whole || !ngal_whole || !seed_ok || (tok.size() > 3 && *e3 != '\0') || nreal < 1 || nreal > 1024 ||
             !std::isfinite(noise_sigma_e) || !(noise_sigma_e > 0) || !std::isfinite(noise_ngal) || !(noise_ngal > 0))
             return bad(usage);
         noise_seed = seed;
@@ -297,9 +304,8 @@ int plan_lensing(const LensingOptions &o, const InputParams &p, const Header &si
         return 0;
     const bool all = o.kappa == "all";  // otherwise z1,z2,...
     for (const string &tok : all ? vector<string>{} : split(o.kappa)) {
-        char *end = nullptr;
-        plan.zs.push_back(strtod(tok.c_str(), &end));
-        if (tok.empty() || *end != '\0' || !(plan.zs.back() >= 0))
+        plan.zs.push_back(0.0);
+        if (!whole_double(tok, &plan.zs.back()) || !(plan.zs.back() >= 0))
             return bad("bad --kappa (all, or a comma-separated list of source redshifts)");
     }
     const int P = lens.nplanes, S = all ? P : (int)plan.zs.size();
@@ -515,11 +521,7 @@ int LensingOutputs::write()
         float *d_kappa = nullptr;
         if (slicer_kappa_device_map(kh, (int)s, &d_kappa) != SLICER_OK)
             return fail(h, "slicer_amd: --kappa");
-        if (const int rc = mh ? source_moments(s, d_kappa, moments) : 0)
-            return rc;
-        if (const int rc = pkh ? source_peaks(s, d_kappa, peaks) : 0)
-            return rc;
-        if (const int rc = mkh ? source_minkowski(s, d_kappa, minkowski) : 0)
+        if (const int rc = map_statistics(s, d_kappa, KAPPA))
             return rc;
         if (const int rc = o.shear ? source_shear(s, d_kappa) : 0)
             return rc;
@@ -532,33 +534,24 @@ int LensingOutputs::write()
         return rc;
     if (const int rc = bsh ? bispectra() : 0)
         return rc;
-    if (mh && write_table("moments", ".moments_", moments))
-        return 1;
-    if (pkh && write_table("histograms and peak counts", ".peaks_", peaks))
-        return 1;
-    if (mh && !smh.empty() && write_table("moments of the smoothed maps", ".smooth_moments_", smooth_moments))
-        return 1;
-    if (pkh && !smh.empty() && write_table("histograms and peak counts of the smoothed maps", ".smooth_peaks_", smooth_peaks))
-        return 1;
-    if (mh && nh && write_table("moments of the noisy maps", ".noisy_moments_", noisy_moments))
-        return 1;
-    if (pkh && nh && write_table("histograms and peak counts of the noisy maps", ".noisy_peaks_", noisy_peaks))
-        return 1;
-    if (mh && nh && !smh.empty() &&
-        write_table("moments of the smoothed noisy maps", ".noisy_smooth_moments_", noisy_smooth_moments))
-        return 1;
-    if (pkh && nh && !smh.empty() &&
-        write_table("histograms and peak counts of the smoothed noisy maps", ".noisy_smooth_peaks_", noisy_smooth_peaks))
-        return 1;
-    if (mkh && write_table("Minkowski functionals", ".minkowski_", minkowski))
-        return 1;
-    if (mkh && !smh.empty() && write_table("Minkowski functionals of the smoothed maps", ".smooth_minkowski_", smooth_minkowski))
-        return 1;
-    if (mkh && nh && write_table("Minkowski functionals of the noisy maps", ".noisy_minkowski_", noisy_minkowski))
-        return 1;
-    return mkh && nh && !smh.empty() ? write_table("Minkowski functionals of the smoothed noisy maps",
-                                                   ".noisy_smooth_minkowski_", noisy_smooth_minkowski)
-                                     : 0;
+    // what stdout calls a statistic and its file token; the same of a kind of map, and whether the run has that kind
+    static const char *const statistic[N_STATISTICS][2] = {
+        {"moments", "moments_"}, {"histograms and peak counts", "peaks_"}, {"Minkowski functionals", "minkowski_"}};
+    static const char *const kind[N_KINDS][2] = {{"", "."},
+                                                 {" of the smoothed maps", ".smooth_"},
+                                                 {" of the noisy maps", ".noisy_"},
+                                                 {" of the smoothed noisy maps", ".noisy_smooth_"}};
+    const bool has_statistic[N_STATISTICS] = {mh != nullptr, pkh != nullptr, mkh != nullptr};
+    const bool has_kind[N_KINDS] = {true, !smh.empty(), nh != nullptr, nh != nullptr && !smh.empty()};
+    // the moments and the histograms kind by kind, then the Minkowski tables: the order these files have always had
+    for (const bool last : {false, true})
+        for (int k = 0; k < N_KINDS; k++)
+            for (int t = 0; t < N_STATISTICS; t++)
+                if ((t == MINKOWSKI) == last && has_statistic[t] && has_kind[k] &&
+                    write_table((string(statistic[t][0]) + kind[k][0]).c_str(), (string(kind[k][1]) + statistic[t][1]).c_str(),
+                                tables[t][k]))
+                    return 1;
+    return 0;
 }
 
 // the '#' lines of --smooth in the tables of the smoothed maps
@@ -610,11 +603,7 @@ int LensingOutputs::source_noise(size_t s, const float *d_kappa)
         const string real = std::to_string(r);
         if (!save("noisy convergence", ".noisy" + real + "_kappa_z", s, keys))
             return fail(h, who);
-        if (const int rc = mh ? source_moments(s, d_noisy, noisy_moments, head, "real ", real + " ") : 0)
-            return rc;
-        if (const int rc = pkh ? source_peaks(s, d_noisy, noisy_peaks, head, "real ", real + " ") : 0)
-            return rc;
-        if (const int rc = mkh ? source_minkowski(s, d_noisy, noisy_minkowski, head, "real ", real + " ") : 0)
+        if (const int rc = map_statistics(s, d_noisy, NOISY, head, "real ", real + " "))
             return rc;
         for (size_t k = 0; k < smh.size(); k++) {
             float *d_smooth = nullptr;
@@ -629,11 +618,7 @@ int LensingOutputs::source_noise(size_t s, const float *d_kappa)
             if (!save("smoothed noisy convergence", ".noisy" + real + "_" + o.smooth_kind + std::to_string(k) + "_kappa_z", s,
                       more))
                 return fail(h, who);
-            if (const int rc = mh ? source_moments(s, d_smooth, noisy_smooth_moments, smoothed_head, "real scale ", lead) : 0)
-                return rc;
-            if (const int rc = pkh ? source_peaks(s, d_smooth, noisy_smooth_peaks, smoothed_head, "real scale ", lead) : 0)
-                return rc;
-            if (const int rc = mkh ? source_minkowski(s, d_smooth, noisy_smooth_minkowski, smoothed_head, "real scale ", lead) : 0)
+            if (const int rc = map_statistics(s, d_smooth, NOISY_SMOOTH, smoothed_head, "real scale ", lead))
                 return rc;
         }
     }
@@ -655,11 +640,41 @@ int LensingOutputs::source_smooth(size_t s, const float *d_kappa)
         if (!save("smoothed convergence", "." + o.smooth_kind + std::to_string(k) + "_kappa_z", s, keys))
             return fail(h, "slicer_amd: --smooth");
         const string lead = std::to_string(k) + " ";
-        if (const int rc = mh ? source_moments(s, d_smooth, smooth_moments, head, "scale ", lead) : 0)
+        if (const int rc = map_statistics(s, d_smooth, SMOOTH, head, "scale ", lead))
             return rc;
-        if (const int rc = pkh ? source_peaks(s, d_smooth, smooth_peaks, head, "scale ", lead) : 0)
-            return rc;
-        if (const int rc = mkh ? source_minkowski(s, d_smooth, smooth_minkowski, head, "scale ", lead) : 0)
+    }
+    return 0;
+}
+
+int LensingOutputs::map_statistics(size_t s, float *d_map, MapKind kind, const string &head, const string &lead_names,
+                                   const string &lead)
+{
+    if (const int rc = mh ? source_moments(s, d_map, tables[MOMENTS][kind], head, lead_names, lead) : 0)
+        return rc;
+    if (const int rc = pkh ? source_peaks(s, d_map, tables[PEAKS][kind], head, lead_names, lead) : 0)
+        return rc;
+    return mkh ? source_minkowski(s, d_map, tables[MINKOWSKI][kind], head, lead_names, lead) : 0;
+}
+
+void LensingOutputs::counts_head(string &text, const char *name, const vector<double> &values, const string &head,
+                                 const string &columns) const
+{
+    if (!text.empty())
+        return;
+    add(text, "# npix %d\n# angle_deg %.17g\n# levels %d\n# %s", p.npix, p.fov, mh ? o.moments_levels : 0, name);
+    for (double v : values)
+        add(text, " %.17g", v);
+    text += "\n" + head + "# " + columns;
+}
+
+template <class Rows>
+int LensingOutputs::pyramid_levels(const char *who, float *d_map, Rows rows)
+{
+    for (int l = 0; l <= (mh ? o.moments_levels : 0); l++) {
+        float *d_level = d_map;
+        if (l > 0 && slicer_moments_device_map(mh, l, &d_level) != SLICER_OK)
+            return fail(h, who);
+        if (const int rc = rows(l, d_level))
             return rc;
     }
     return 0;
@@ -701,19 +716,11 @@ int LensingOutputs::source_peaks(size_t s, float *d_map, string &text, const str
                                  const string &lead)
 {
     const vector<double> &e = o.peaks_edges;
-    const int B = (int)e.size() - 1, levels = mh ? o.moments_levels : 0;
+    const int B = (int)e.size() - 1;
     vector<int64_t> c(3 * B + 7);  // pdf, peaks, minima [B]; below, above [3]; nan
     const int64_t *below = &c[3 * B], *above = below + 3;
-    if (text.empty()) {
-        add(text, "# npix %d\n# angle_deg %.17g\n# levels %d\n# edges", p.npix, p.fov, levels);
-        for (double v : e)
-            add(text, " %.17g", v);
-        text += "\n" + head + "# " + lead_names + "z level npix bin lo hi n_pixels n_peaks n_minima\n";
-    }
-    for (int l = 0; l <= levels; l++) {
-        float *d_level = d_map;
-        if (l > 0 && slicer_moments_device_map(mh, l, &d_level) != SLICER_OK)
-            return fail(h, "slicer_amd: --peaks");
+    counts_head(text, "edges", e, head, lead_names + "z level npix bin lo hi n_pixels n_peaks n_minima\n");
+    return pyramid_levels("slicer_amd: --peaks", d_map, [&](int l, float *d_level) {
         if (slicer_peaks_run_npix(pkh, d_level, p.npix >> l) != SLICER_OK ||
             slicer_peaks_read(pkh, &c[0], &c[B], &c[2 * B], &c[3 * B], &c[3 * B + 3], &c[3 * B + 6]) != SLICER_OK)
             return fail(h, "slicer_amd: --peaks");
@@ -727,8 +734,8 @@ int LensingOutputs::source_peaks(size_t s, float *d_map, string &text, const str
             row(b, e[b], e[b + 1], c[b], c[B + b], c[2 * B + b]);
         row(B, e[B], INFINITY, above[0], above[1], above[2]);
         row(B + 1, NAN, NAN, c[3 * B + 6], 0, 0);
-    }
-    return 0;
+        return 0;
+    });
 }
 
 // The Minkowski table: '#' lines (npix, angle, levels, the thresholds, column names), then per (source, level) one row
@@ -738,20 +745,12 @@ int LensingOutputs::source_minkowski(size_t s, float *d_map, string &text, const
                                      const string &lead)
 {
     const vector<double> &t = o.minkowski_thresholds;
-    const int T = (int)t.size(), levels = mh ? o.moments_levels : 0;
+    const int T = (int)t.size();
     vector<int64_t> c(5 * T);  // faces, edges, vertices, boundary, border [T]
     int64_t n_nan = 0;
-    if (text.empty()) {
-        add(text, "# npix %d\n# angle_deg %.17g\n# levels %d\n# thresholds", p.npix, p.fov, levels);
-        for (double v : t)
-            add(text, " %.17g", v);
-        text += "\n" + head + "# " + lead_names +
-                "z level npix j threshold n_faces n_edges n_vertices n_boundary n_border euler n_nan\n";
-    }
-    for (int l = 0; l <= levels; l++) {
-        float *d_level = d_map;
-        if (l > 0 && slicer_moments_device_map(mh, l, &d_level) != SLICER_OK)
-            return fail(h, "slicer_amd: --minkowski");
+    counts_head(text, "thresholds", t, head,
+                lead_names + "z level npix j threshold n_faces n_edges n_vertices n_boundary n_border euler n_nan\n");
+    return pyramid_levels("slicer_amd: --minkowski", d_map, [&](int l, float *d_level) {
         if (slicer_minkowski_run_npix(mkh, d_level, p.npix >> l) != SLICER_OK ||
             slicer_minkowski_read(mkh, &c[0], &c[T], &c[2 * T], &c[3 * T], &c[4 * T], &n_nan) != SLICER_OK)
             return fail(h, "slicer_amd: --minkowski");
@@ -761,8 +760,8 @@ int LensingOutputs::source_minkowski(size_t s, float *d_map, string &text, const
                 (long long)c[j], (long long)c[T + j], (long long)c[2 * T + j], (long long)c[3 * T + j],
                 (long long)c[4 * T + j], (long long)(c[2 * T + j] - c[T + j] + c[j]), (long long)n_nan);
         }
-    }
-    return 0;
+        return 0;
+    });
 }
 
 // smr.smr(kappa file): next to the kappa file, the same name with the .kappa_z token replaced, the same header

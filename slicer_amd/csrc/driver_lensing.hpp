@@ -122,11 +122,12 @@ struct LensingOutputs {
     size_t rt_next = 0;
     DeviceMaps upload{h};        // planes read back from their files
     std::vector<float> map{};    // the host copy of the map that save() writes
-    std::string moments{}, peaks{};  // their tables, which write() gathers source by source
-    std::string smooth_moments{}, smooth_peaks{};  // the same of the smoothed maps, scale by scale
-    std::string noisy_moments{}, noisy_peaks{};    // the same of the noisy maps, realisation by realisation
-    std::string noisy_smooth_moments{}, noisy_smooth_peaks{};  // ... and of the smoothed noisy maps
-    std::string minkowski{}, smooth_minkowski{}, noisy_minkowski{}, noisy_smooth_minkowski{};  // --minkowski: the same four
+    // The tables of --moments, --peaks and --minkowski, which write() gathers source by source: one per statistic and
+    // kind of map -- the kappa maps, the smoothed ones scale by scale, the noisy ones realisation by realisation, and
+    // the smoothed noisy ones
+    enum Statistic { MOMENTS, PEAKS, MINKOWSKI, N_STATISTICS };
+    enum MapKind { KAPPA, SMOOTH, NOISY, NOISY_SMOOTH, N_KINDS };
+    std::string tables[N_STATISTICS][N_KINDS]{};
 
     int create();
     // The planes i0 .. i1-1 of one pass go into the kappa maps as ONE batch whether they were deposited now (their
@@ -143,12 +144,22 @@ private:
     // The rows of source s for the map at d_map onto the end of `text`, led by its '#' lines while it is empty.
     // Smoothed and noisy maps: `head` goes between the '#' lines and the column names, `lead_names` ("scale ", "real ",
     // "real scale ") in front of the column names and `lead` (their values, each followed by a blank) in front of every row.
-    int source_moments(size_t s, const float *d_map, std::string &text, const std::string &head = "",
-                       const std::string &lead_names = "", const std::string &lead = "");
-    int source_peaks(size_t s, float *d_map, std::string &text, const std::string &head = "",
-                     const std::string &lead_names = "", const std::string &lead = "");
-    int source_minkowski(size_t s, float *d_map, std::string &text, const std::string &head = "",
-                         const std::string &lead_names = "", const std::string &lead = "");
+    int source_moments(size_t s, const float *d_map, std::string &text, const std::string &head,
+                       const std::string &lead_names, const std::string &lead);
+    int source_peaks(size_t s, float *d_map, std::string &text, const std::string &head, const std::string &lead_names,
+                     const std::string &lead);
+    int source_minkowski(size_t s, float *d_map, std::string &text, const std::string &head, const std::string &lead_names,
+                         const std::string &lead);
+    // ... of every statistic that is on, into its table of this kind of map: moments, then peaks, then Minkowski (the
+    // last two read the pyramid that the moments of the same map left behind)
+    int map_statistics(size_t s, float *d_map, MapKind kind, const std::string &head = "", const std::string &lead_names = "",
+                       const std::string &lead = "");
+    // The '#' lines of a --peaks / --minkowski table while `text` is empty: npix, angle, levels, `name` and the values,
+    // `head`, the column names.  The levels of the pyramid under d_map, 0 (the map itself) ... levels: rows(l, d_level).
+    void counts_head(std::string &text, const char *name, const std::vector<double> &values, const std::string &head,
+                     const std::string &columns) const;
+    template <class Rows>
+    int pyramid_levels(const char *who, float *d_map, Rows rows);
     std::string smooth_head() const;
     std::string noise_head() const;
     int source_smooth(size_t s, const float *d_kappa);

@@ -242,11 +242,9 @@ std::vector<Item> make_items(const std::vector<Triple> &u)
 
 }  // namespace
 
-struct slicer_bispectrum_s {
-    slicer_handle h = nullptr;
+struct slicer_bispectrum_s : SubHandle {
     slicer_fft_s *fft = nullptr;        // the unsplit plan: every result comes from it
     slicer_fft_s *fft_split = nullptr;  // shear_split = 1 only: the plan of spec_split
-    int device = 0;
     int n = 0, H = 0, B = 0, nslots = 0, nuniq = 0, nitems = 0, nchunks = 0, chunk = 0;
     double norm = 0.0;  // theta^4 / n^6
     std::vector<double> e2;  // edge squares, B + 1
@@ -258,7 +256,6 @@ struct slicer_bispectrum_s {
     int *uniq_of = nullptr;  // [nslots]: the unique triple of every list entry
     double *partial = nullptr, *sums = nullptr;
     bool ran = false;
-    DevAllocs mem;
     SLICER_FFT_INTERNAL ~slicer_bispectrum_s()
     {
         slicer_fft_destroy(fft);
@@ -401,15 +398,9 @@ int slicer_bispectrum_create(slicer_handle h, int32_t npix, double angle_deg, in
     if (!std::isfinite(angle_deg) || angle_deg <= 0.0)
         return fail(h, SLICER_ERR_ARG, "%s: the angle must be positive and finite", who);
     hipStream_t st = nullptr;
-    int dev = 0;
-    if (int rc = sub_open(h, who, &st, &dev))
+    slicer_bispectrum_handle bh = nullptr;
+    if (int rc = sub_new(h, who, &st, &bh))
         return rc;
-
-    slicer_bispectrum_handle bh = new (std::nothrow) slicer_bispectrum_s;
-    if (!bh)
-        return fail(h, SLICER_ERR_NOMEM, "out of host memory");
-    bh->h = h;
-    bh->device = dev;
     bh->n = n;
     bh->H = H;
     bh->B = B;
@@ -429,11 +420,11 @@ int slicer_bispectrum_create(slicer_handle h, int32_t npix, double angle_deg, in
     bh->chunk = (int)(((npix2 + want - 1) / want + 63) / 64 * 64);
     bh->nchunks = (int)((npix2 + bh->chunk - 1) / bh->chunk);
 
-    int rc = slicer_fft_create(h, n, 0, st, dev, who, &bh->fft);
+    int rc = slicer_fft_create(h, n, 0, st, bh->device, who, &bh->fft);
     rc = bh->mem.alloc(rc, h, who, (void **)&bh->spec, (size_t)n * H * sizeof(double2));
     if (h->opt.shear_split) {
         if (rc == SLICER_OK)
-            rc = slicer_fft_create(h, n, 1, st, dev, who, &bh->fft_split);
+            rc = slicer_fft_create(h, n, 1, st, bh->device, who, &bh->fft_split);
         rc = bh->mem.alloc(rc, h, who, (void **)&bh->spec_split, (size_t)n * H * sizeof(double2));
     }
     rc = bh->mem.alloc(rc, h, who, (void **)&bh->F, (size_t)B * npix2 * sizeof(double));
@@ -462,13 +453,9 @@ int slicer_bispectrum_create(slicer_handle h, int32_t npix, double angle_deg, in
         for (double &t : bh->T)
             t = n4 * t;
     }
-    if (rc != SLICER_OK) {
+    if (rc != SLICER_OK)
         (void)hipStreamSynchronize(st);
-        delete bh;
-        return rc;
-    }
-    *out = bh;
-    return SLICER_OK;
+    return sub_done(rc, bh, out);
 }
 
 int slicer_bispectrum_run(slicer_bispectrum_handle bh, const float *d_map)
@@ -526,13 +513,7 @@ int slicer_bispectrum_spectrum(slicer_bispectrum_handle bh, double *host)
         return fail(bh ? bh->h : nullptr, SLICER_ERR_ARG, "slicer_bispectrum_spectrum: null argument");
     if (!bh->ran)
         return fail(bh->h, SLICER_ERR_STATE, "slicer_bispectrum_spectrum before any slicer_bispectrum_run");
-    hipStream_t st;
-    if (int rc = sub_stream(bh->h, bh->device, &st))
-        return rc;
-    const double2 *spec = bh->spec_split ? bh->spec_split : bh->spec;
-    HIPCHK(bh->h, hipMemcpyAsync(host, spec, (size_t)bh->n * bh->H * sizeof(double2), hipMemcpyDeviceToHost, st));
-    HIPCHK(bh->h, hipStreamSynchronize(st));
-    return SLICER_OK;
+    return sub_read(*bh, host, bh->spec_split ? bh->spec_split : bh->spec, (size_t)bh->n * bh->H * sizeof(double2));
 }
 
 int slicer_bispectrum_read_map(slicer_bispectrum_handle bh, int32_t bin, double *host)
@@ -543,21 +524,8 @@ int slicer_bispectrum_read_map(slicer_bispectrum_handle bh, int32_t bin, double 
         return fail(bh->h, SLICER_ERR_ARG, "slicer_bispectrum_read_map: bin = %d outside 0..%d", bin, bh->B - 1);
     if (!bh->ran)
         return fail(bh->h, SLICER_ERR_STATE, "slicer_bispectrum_read_map before any slicer_bispectrum_run");
-    hipStream_t st;
-    if (int rc = sub_stream(bh->h, bh->device, &st))
-        return rc;
     const size_t npix2 = (size_t)bh->n * bh->n;
-    HIPCHK(bh->h, hipMemcpyAsync(host, bh->F + (size_t)bin * npix2, npix2 * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(bh->h, hipStreamSynchronize(st));
-    return SLICER_OK;
+    return sub_read(*bh, host, bh->F + (size_t)bin * npix2, npix2 * sizeof(double));
 }
 
-int slicer_bispectrum_destroy(slicer_bispectrum_handle bh)
-{
-    if (!bh)
-        return SLICER_ERR_ARG;
-    (void)hipSetDevice(bh->device);
-    (void)hipStreamSynchronize(bh->h->stream);
-    delete bh;
-    return SLICER_OK;
-}
+int slicer_bispectrum_destroy(slicer_bispectrum_handle bh) { return sub_destroy(bh); }

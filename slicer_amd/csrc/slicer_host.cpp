@@ -131,6 +131,25 @@ int sub_stream(slicer_handle h, int device, hipStream_t *st)
     return SLICER_OK;
 }
 
+int npix_in_range(slicer_handle h, const char *who, int npix, int max_npix)
+{
+    if (npix < 1)
+        return fail(h, SLICER_ERR_ARG, "%s: npix must be positive", who);
+    if (npix > max_npix)
+        return fail(h, SLICER_ERR_UNSUPPORTED, "%s: npix = %d above %d", who, npix, max_npix);
+    return SLICER_OK;
+}
+
+int sub_read(const SubHandle &s, void *host, const void *dev, size_t bytes)
+{
+    hipStream_t st;
+    if (int rc = sub_stream(s.h, s.device, &st))
+        return rc;
+    HIPCHK(s.h, hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st));
+    HIPCHK(s.h, hipStreamSynchronize(st));
+    return SLICER_OK;
+}
+
 int DevAllocs::alloc(int rc, slicer_handle h, const char *who, void **p, size_t bytes, const hipStream_t *zero_on)
 {
     if (rc != SLICER_OK)

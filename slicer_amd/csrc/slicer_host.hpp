@@ -1,7 +1,9 @@
 // slicer_host.hpp -- internal (not installed, not exported): the host layer under the C ABI of include/slicer_amd.h.
 // The handle, its error and profiling plumbing, what the sub-handles (kappa, shear, FFT plan, power, moments, peaks, rays, smooth, noise, minkowski, bispectrum)
 // share, and the functions that cross the files of the core pass:
-//   slicer_host.cpp    errors, grow-only buffers, profiling, the sub-handle helpers
+//   slicer_host.cpp    errors, grow-only buffers, profiling, the sub-handle helpers: SubHandle (the base of every
+//                      sub-handle struct) with sub_new / sub_done for its *_create, sub_stream for its launches, sub_read
+//                      for its read-backs and sub_destroy; npix_in_range and ranges_overlap for the argument checks
 //   slicer_capi.cpp    entry points of the core pass
 //   pass_plan.cpp      pass parameters, tile geometry, the exhaustive sweeps, slicer_debug_*
 //   binned_pass.cpp    map clearing, workspaces and pending lists of the binned pipeline, the per-chunk deposit
@@ -11,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <new>
 #include <string>
 #include <utility>
 #include <vector>
@@ -242,6 +245,57 @@ struct DevAllocs {
     void free_all();
     ~DevAllocs() { free_all(); }
 };
+// What every sub-handle struct starts with (they derive from it): the parent, its device, and the device memory.
+struct SubHandle {
+    slicer_handle h = nullptr;
+    int device = 0;
+    DevAllocs mem;
+};
+// The npix range of a *_create whose numbers are checked before its handle: "<who>: npix must be positive", or
+// "<who>: npix = <npix> above <max_npix>" (SLICER_ERR_UNSUPPORTED).
+int npix_in_range(slicer_handle h, const char *who, int npix, int max_npix);
+// A *_create after its argument checks: sub_open, then a T with h and device filled in (*x; null on failure).
+template <class T>
+int sub_new(slicer_handle h, const char *who, hipStream_t *st, T **x)
+{
+    *x = nullptr;
+    int device = 0;
+    if (int rc = sub_open(h, who, st, &device))
+        return rc;
+    if (!(*x = new (std::nothrow) T))
+        return fail(h, SLICER_ERR_NOMEM, "out of host memory");
+    (*x)->h = h;
+    (*x)->device = device;
+    return SLICER_OK;
+}
+// ... and its end: rc of the allocations and uploads; x goes to the caller, or is deleted.
+template <class T>
+int sub_done(int rc, T *x, T **out)
+{
+    if (rc != SLICER_OK) {
+        delete x;
+        return rc;
+    }
+    *out = x;
+    return SLICER_OK;
+}
+// `bytes` from `dev` to `host` on the parent's stream, and wait for them: what a *_read, *_read_map or *_spectrum ends in.
+int sub_read(const SubHandle &s, void *host, const void *dev, size_t bytes);
+// A *_destroy: waits for the parent's stream, then deletes.  Null: SLICER_ERR_ARG and no error text.
+template <class T>
+int sub_destroy(T *x)
+{
+    if (!x)
+        return SLICER_ERR_ARG;
+    (void)hipSetDevice(x->device);
+    (void)hipStreamSynchronize(x->h->stream);
+    delete x;
+    return SLICER_OK;
+}
+inline bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes)
+{
+    return (uintptr_t)a < (uintptr_t)b + b_bytes && (uintptr_t)b < (uintptr_t)a + a_bytes;
+}
 bool fft_size_supported(int n);  // 2 <= n <= 16384 with prime factors 2, 3, 5, 7 only: what slicer_fft_create plans
 
 // ---- pass_plan.cpp ----

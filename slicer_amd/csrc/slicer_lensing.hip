@@ -193,9 +193,7 @@ __global__ __launch_bounds__(kThreads) void k_kappa_finalize(FinalizeArgs a)
 
 }  // namespace
 
-struct slicer_kappa_s {
-    slicer_handle h = nullptr;
-    int device = 0;
+struct slicer_kappa_s : SubHandle {
     int npix = 0;
     uint64_t n = 0;
     int n_sources = 0;
@@ -208,7 +206,6 @@ struct slicer_kappa_s {
     int means_cap = 0;
     int n_added = 0;
     bool finalized = false;
-    DevAllocs mem;  // everything above
 };
 
 int slicer_kappa_create(slicer_handle h, int32_t npix, int32_t n_sources, slicer_kappa_handle *out)
@@ -218,17 +215,16 @@ int slicer_kappa_create(slicer_handle h, int32_t npix, int32_t n_sources, slicer
     *out = nullptr;
     if (npix <= 0 || n_sources <= 0)
         return fail(h, SLICER_ERR_ARG, "slicer_kappa_create: npix and n_sources must be positive");
-    slicer_kappa_handle kh = new (std::nothrow) slicer_kappa_s;
-    if (!kh)
-        return fail(h, SLICER_ERR_NOMEM, "out of host memory");
-    kh->h = h;
+    const char *who = "slicer_kappa_create";
+    hipStream_t st = nullptr;
+    slicer_kappa_handle kh = nullptr;
+    if (int rc = sub_new(h, who, &st, &kh))
+        return rc;
     kh->npix = npix;
     kh->n = (uint64_t)npix * (uint64_t)npix;
     kh->n_sources = n_sources;
     kh->nblocks = (unsigned)((kh->n + 4ull * kThreads - 1) / (4ull * kThreads));
-    hipStream_t st = nullptr;
-    const char *who = "slicer_kappa_create";
-    int rc = sub_open(h, who, &st, &kh->device);
+    int rc = SLICER_OK;
     kh->acc.assign(n_sources, nullptr);
     kh->kappa.assign(n_sources, nullptr);
     for (int s = 0; s < n_sources; s++) {
@@ -239,12 +235,7 @@ int slicer_kappa_create(slicer_handle h, int32_t npix, int32_t n_sources, slicer
     rc = kh->mem.alloc(rc, h, who, (void **)&kh->partials, (size_t)kMaxMaps * kh->nblocks * sizeof(double), &st);
     kh->means_cap = 1024;
     rc = kh->mem.alloc(rc, h, who, (void **)&kh->means, kh->means_cap * sizeof(double), &st);
-    if (rc != SLICER_OK) {
-        delete kh;
-        return rc;
-    }
-    *out = kh;
-    return SLICER_OK;
+    return sub_done(rc, kh, out);
 }
 
 int slicer_kappa_add(slicer_kappa_handle kh, int32_t n_maps, const float *const *d_maps, const double *coeff)
@@ -391,20 +382,7 @@ int slicer_kappa_read(slicer_kappa_handle kh, int32_t s, float *host)
         return rc;
     if (!host)
         return fail(kh->h, SLICER_ERR_ARG, "slicer_kappa_read: null host pointer");
-    hipStream_t st;
-    if (int rc = sub_stream(kh->h, kh->device, &st))
-        return rc;
-    HIPCHK(kh->h, hipMemcpyAsync(host, d, kh->n * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIPCHK(kh->h, hipStreamSynchronize(st));
-    return SLICER_OK;
+    return sub_read(*kh, host, d, kh->n * sizeof(float));
 }
 
-int slicer_kappa_destroy(slicer_kappa_handle kh)
-{
-    if (!kh)
-        return SLICER_ERR_ARG;
-    (void)hipSetDevice(kh->device);
-    (void)hipStreamSynchronize(kh->h->stream);
-    delete kh;
-    return SLICER_OK;
-}
+int slicer_kappa_destroy(slicer_kappa_handle kh) { return sub_destroy(kh); }

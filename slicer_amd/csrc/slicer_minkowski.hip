@@ -16,15 +16,17 @@
 // (i, j)): every face, edge and vertex has exactly one owner, and an owned edge is on the rim iff i is 0 or n (top
 // edge) or j is 0 or n (left edge).  What does not exist (a face or a left edge of row n, a top edge of column n,
 // anything past them) has only faces of rank 0 and is never counted, so existence needs no test.
-// A workgroup of 256 threads takes tiles of kT0 x kT1 = 16 x 64 cells (the tile of slicer_peaks.hip) and every thread
+// The tile, the search, the grid size and the column sums are those of slicer_rank_counts.hpp, shared with
+// slicer_peaks.hip.
+// A workgroup of 256 threads takes tiles of kT0 x kT1 = 16 x 64 cells and every thread
 // four adjacent cells of one row.  A tile needs the RANKS of 17 x 65 pixels: its own faces, one row above and one
 // column to the left.  Every pixel of the window is searched once, while it is staged, and the window holds the ranks
 // as u16 (k <= 1025), not the floats: 17 rows of pitch 72 with the tile's first column at window column 4, so that a
 // thread's four ranks of a row are one 8-byte LDS access and the left neighbour one u16.  Thread t stages the four
 // pixels of quad t % 16 of window row t / 16 (rows r0 - 1 ... r0 + 14) and, for t < 81, one more pixel: the tile's
-// last row (t < 64) or the column to the left (64 <= t < 81).  The five are searched side by side in ONE pass of the
-// branch-free binary search of slicer_peaks.hip (ceil(log2 T) + 1 LDS reads of the f64 thresholds, steps that depend on
-// T alone), so the 81 extra pixels cost a fifth more reads and no second pass.  Loads: a float4 per quad when 4 | n and
+// last row (t < 64) or the column to the left (64 <= t < 81).  The five are searched side by side in ONE pass of
+// rank_search (ceil(log2 T) + 1 LDS reads of the f64 thresholds), so the 81 extra pixels cost a fifth more reads and no
+// second pass.  Loads: a float4 per quad when 4 | n and
 // the map is on the 16-byte grid (k_minkowski<true>), scalar loads otherwise (<false>); the window, and so the counts,
 // are the same.  NaN pixels are counted where they are staged as one of the tile's own faces.
 // Counters: five u32 LDS histograms of T + 1 rank bins -- face k, vertex max k, interior-edge max k, interior-edge
@@ -40,40 +42,23 @@
 // ceil(tiles / G) tiles, tiles <= 8193 * 2049 and G >= min(tiles, 64) (a static_assert).
 // The grid is fixed: G = min(tiles, max(kMinGroups, w * CUs)) workgroups, w = min(8, what a CU's LDS holds at once),
 // workgroup b takes tiles b, b + G, ...  Flush: workgroup b stores its counters as row b of partial[G][5 (T + 1) + 1];
-// k_minkowski_finish sums the rows of every column into int64, k_minkowski_suffix (one workgroup) forms
+// k_column_sums sums the rows of every column into int64, k_minkowski_suffix (one workgroup) forms
 // out[j] = sum over k > j of hist[k] and stores faces, edges = edge max + rim, vertices, boundary = edge max - edge
 // min, border = rim, and the NaN count.  Every row and every result is stored by every launch: nothing is zeroed
 // between runs, nothing carried over, no global atomics.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <cmath>
-#include <cstdint>
-#include <new>
-#include <vector>
-
-#include "slicer_host.hpp"
+#include "slicer_rank_counts.hpp"
 
 namespace {
 
-constexpr int kT0 = 16, kT1 = 64;  // tile: rows x columns of cells
-constexpr int kPer = 4;            // adjacent cells of a thread
-constexpr int kThreads = kT0 * kT1 / kPer;
-constexpr int kRows = kT0 + 1;           // window rows: one above the tile
-constexpr int kLeft = 4;                 // window column of the tile's first pixel
-constexpr int kPitch = kLeft + kT1 + 4;  // 72 u16: every window row starts on the 16-byte grid
-constexpr int kQuads = kT1 / kPer;       // quads of a tile row = threads of a tile row
-constexpr int kExtra = kT1 + kRows;      // the tile's last row and the column to its left: one pixel a thread
-constexpr int kMaxNpix = 131072;
+constexpr int kRows = kT0 + 1;       // window rows: one above the tile
+constexpr int kExtra = kT1 + kRows;  // the tile's last row and the column to its left: one pixel a thread
 constexpr int kMaxT = SLICER_MINKOWSKI_MAX_THRESHOLDS;
 constexpr int kHists = 5;  // face, vertex, interior-edge max, interior-edge min, rim edge
 enum { H_FACE = 0, H_VERTEX, H_EDGE_MAX, H_EDGE_MIN, H_RIM };
-constexpr int kPerCu = 8, kMinGroups = 64;  // workgroups per CU at most; fewer where their LDS does not fit
-constexpr size_t kLdsPerCu = 160 * 1024;    // gfx950
-constexpr size_t kCopyBytes = 16 * 1024;     // LDS for the copies of the counters (one copy may be larger)
-constexpr int kFinCols = 16, kFinRows = 16;  // k_minkowski_finish: columns of a workgroup x threads of a column
+constexpr size_t kCopyBytes = 16 * 1024;  // LDS for the copies of the counters (one copy may be larger)
 
-static_assert(kThreads == 256 && kFinCols * kFinRows == kThreads, "one thread per four cells of a tile");
 static_assert(kExtra <= kThreads && kQuads * (kRows - 1) == kThreads, "a quad and at most one more pixel a thread");
 static_assert((((int64_t)kMaxNpix + 1 + kT0 - 1) / kT0) * (((int64_t)kMaxNpix + 1 + kT1 - 1) / kT1) / kMinGroups + 1 <
                   ((int64_t)1 << 32) / (2 * kT0 * kT1),
@@ -156,26 +141,13 @@ __global__ __launch_bounds__(kThreads) void k_minkowski(MinkArgs a)
         n_nan += tid < kT1 && v[kPer] != v[kPer] ? 1u : 0u;
         if (n_nan)
             atomicAdd(&cnt[nan_at], n_nan);
-        // pos[q]: how many of t_0 ... t_{T-1} are <= pixel q.  Invariant of the search: every threshold before `pos`
-        // is <= x and the answer lies in pos ... pos + len.  The steps depend on T alone, so the wave never diverges,
-        // and the five pixels' reads of a step are independent of one another.  A NaN fails every comparison: rank 0.
+        // pos[q]: how many of t_0 ... t_{T-1} are <= pixel q, the five side by side; a NaN has rank 0
         double xd[kPer + 1];
         int pos[kPer + 1];
 #pragma unroll
-        for (int q = 0; q <= kPer; q++) {
-            xd[q] = (double)v[q];
-            pos[q] = 0;
-        }
-        for (int len = T; len > 1;) {
-            const int half = len / 2;
-#pragma unroll
-            for (int q = 0; q <= kPer; q++)
-                pos[q] = thr[pos[q] + half - 1] <= xd[q] ? pos[q] + half : pos[q];
-            len -= half;
-        }
-#pragma unroll
         for (int q = 0; q <= kPer; q++)
-            pos[q] += thr[pos[q]] <= xd[q] ? 1 : 0;
+            xd[q] = (double)v[q];
+        rank_search(thr, T, xd, pos);
         *reinterpret_cast<uint2 *>(win + lr * kPitch + kLeft + lc) =
             make_uint2((unsigned)pos[0] | (unsigned)pos[1] << 16, (unsigned)pos[2] | (unsigned)pos[3] << 16);
         if (tid < kT1)
@@ -241,27 +213,6 @@ __global__ __launch_bounds__(kThreads) void k_minkowski(MinkArgs a)
         out[nC - 1] = cnt[nan_at];
 }
 
-// Workgroup v sums columns 16 v ... 16 v + 15 of partial[G][nC] into hist[nC]: sixteen threads a column, thread rg of
-// them the rows rg, rg + 16, ...; integer sums, so the order does not matter.
-__global__ __launch_bounds__(kThreads) void k_minkowski_finish(const unsigned *partial, int G, int nC, int64_t *hist)
-{
-    __shared__ int64_t red[kFinRows][kFinCols];
-    const int cl = threadIdx.x % kFinCols, rg = threadIdx.x / kFinCols, col = (int)blockIdx.x * kFinCols + cl;
-    int64_t acc = 0;
-    if (col < nC) {
-#pragma unroll 8
-        for (int g = rg; g < G; g += kFinRows)
-            acc += (int64_t)partial[(size_t)g * nC + col];
-    }
-    red[rg][cl] = acc;
-    __syncthreads();
-    if (rg != 0 || col >= nC)
-        return;
-    for (int k = 1; k < kFinRows; k++)
-        acc += red[k][cl];
-    hist[col] = acc;
-}
-
 // One workgroup: suf[h][k] = sum over m >= k of histogram h.  Thread u sums the bins u per ... (u + 1) per - 1 of every
 // histogram, the 256 chunk sums are scanned from the back in eight doubling steps, and every thread walks its bins down
 // from the sum of the chunks after its own.  Then res = faces [T], edges [T], vertices [T], boundary [T], border [T],
@@ -317,25 +268,9 @@ size_t mink_dyn_lds(int T)
     return (size_t)T * sizeof(double) + (((mink_columns(T) - 1) << lg_copies_of(T)) + 1) * sizeof(unsigned);
 }
 
-int64_t tiles_of(int n) { return (int64_t)((n + 1 + kT0 - 1) / kT0) * ((n + 1 + kT1 - 1) / kT1); }
-
-// 0, or the message of what is wrong with the thresholds
-const char *thresholds_fault(int32_t T, const double *thr)
-{
-    for (int k = 0; k < T; k++)
-        if (!std::isfinite(thr[k]))
-            return "thresholds must be finite";
-    for (int k = 1; k < T; k++)
-        if (!(thr[k - 1] < thr[k]))
-            return "thresholds must be strictly ascending";
-    return nullptr;
-}
-
 }  // namespace
 
-struct slicer_minkowski {
-    slicer_handle h = nullptr;
-    int device = 0;
+struct slicer_minkowski : SubHandle {
     int n = 0, T = 0;
     int gmax = 0;  // rows of `partial`
     std::vector<double> thr;
@@ -344,7 +279,6 @@ struct slicer_minkowski {
     int64_t *hist = nullptr;  // the column sums of `partial`
     int64_t *res = nullptr;
     bool ran = false;
-    DevAllocs mem;
 };
 
 extern "C" {
@@ -353,38 +287,29 @@ int slicer_minkowski_create(slicer_handle h, int32_t npix, int32_t n_thresholds,
                             slicer_minkowski_handle *out)
 {
     // the numbers first: they need no handle, so a caller can have them checked before any device exists
+    const char *who = "slicer_minkowski_create";
     if (out)
         *out = nullptr;
-    if (npix < 1)
-        return fail(h, SLICER_ERR_ARG, "slicer_minkowski_create: npix must be positive");
-    if (npix > kMaxNpix)
-        return fail(h, SLICER_ERR_UNSUPPORTED, "slicer_minkowski_create: npix = %d above %d", npix, kMaxNpix);
+    if (int rc = npix_in_range(h, who, npix, kMaxNpix))
+        return rc;
     if (n_thresholds < 1)
         return fail(h, SLICER_ERR_ARG, "slicer_minkowski_create: fewer than 1 threshold");
     if (n_thresholds > kMaxT)
         return fail(h, SLICER_ERR_ARG, "slicer_minkowski_create: %d thresholds, at most %d", n_thresholds, kMaxT);
     if (!thresholds)
         return fail(h, SLICER_ERR_ARG, "slicer_minkowski_create: null argument");
-    if (const char *what = thresholds_fault(n_thresholds, thresholds))
-        return fail(h, SLICER_ERR_ARG, "slicer_minkowski_create: %s", what);
+    if (const char *what = ascending_fault(n_thresholds, thresholds))
+        return fail(h, SLICER_ERR_ARG, "slicer_minkowski_create: thresholds must be %s", what);
     if (!h || !out)
         return fail(h, SLICER_ERR_ARG, "slicer_minkowski_create: null argument");
-    const char *who = "slicer_minkowski_create";
     hipStream_t st = nullptr;
-    int dev = 0;
-    if (int rc = sub_open(h, who, &st, &dev))
+    slicer_minkowski_handle mh = nullptr;
+    if (int rc = sub_new(h, who, &st, &mh))
         return rc;
-    slicer_minkowski_handle mh = new (std::nothrow) slicer_minkowski;
-    if (!mh)
-        return fail(h, SLICER_ERR_NOMEM, "out of host memory");
-    mh->h = h;
-    mh->device = dev;
     mh->n = npix;
     mh->T = n_thresholds;
-    // as many workgroups as are resident at once: by LDS (the window, the thresholds, the counters), kPerCu at most
-    const size_t lds = kRows * kPitch * sizeof(unsigned short) + mink_dyn_lds(mh->T);
-    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(kPerCu, kLdsPerCu / lds));
-    mh->gmax = (int)std::min<int64_t>(tiles_of(npix), std::max(kMinGroups, per_cu * h->num_cus));
+    // the LDS of a workgroup: the window, the thresholds, the counters; the tiles cover the n + 1 cells of a side
+    mh->gmax = resident_groups(kRows * kPitch * sizeof(unsigned short) + mink_dyn_lds(mh->T), tiles_of(npix + 1), h->num_cus);
     mh->thr.assign(thresholds, thresholds + n_thresholds);
     const size_t nC = mink_columns(mh->T);
     int rc = SLICER_OK;
@@ -398,12 +323,7 @@ int slicer_minkowski_create(slicer_handle h, int32_t npix, int32_t n_thresholds,
         if (e != hipSuccess)
             rc = fail(h, SLICER_ERR_HIP, "%s: copying the thresholds: %s", who, hipGetErrorString(e));
     }
-    if (rc != SLICER_OK) {
-        delete mh;
-        return rc;
-    }
-    *out = mh;
-    return SLICER_OK;
+    return sub_done(rc, mh, out);
 }
 
 int slicer_minkowski_run_npix(slicer_minkowski_handle mh, const float *d_map, int32_t npix)
@@ -423,14 +343,14 @@ int slicer_minkowski_run_npix(slicer_minkowski_handle mh, const float *d_map, in
     a.partial = mh->partial;
     a.n = npix;
     a.T = mh->T;
-    a.tiles_x = (npix + 1 + kT1 - 1) / kT1;
-    a.ntiles = (int)tiles_of(npix);
+    a.tiles_x = tiles_across(npix + 1);
+    a.ntiles = (int)tiles_of(npix + 1);
     a.lg_copies = lg_copies_of(mh->T);
     const int G = std::min(a.ntiles, mh->gmax);
     const size_t lds = mink_dyn_lds(mh->T);
     {
         ProfScope ps(mh->h, KN_MINKOWSKI);
-        if (npix % 4 == 0 && (uintptr_t)d_map % 16 == 0)
+        if (quads_aligned(d_map, npix))
             hipLaunchKernelGGL(k_minkowski<true>, dim3((unsigned)G), dim3(kThreads), lds, st, a);
         else
             hipLaunchKernelGGL(k_minkowski<false>, dim3((unsigned)G), dim3(kThreads), lds, st, a);
@@ -438,8 +358,7 @@ int slicer_minkowski_run_npix(slicer_minkowski_handle mh, const float *d_map, in
     }
     {
         ProfScope ps(mh->h, KN_MINKOWSKI_FINISH);
-        hipLaunchKernelGGL(k_minkowski_finish, dim3((unsigned)((nC + kFinCols - 1) / kFinCols)), dim3(kThreads), 0, st,
-                           mh->partial, G, nC, mh->hist);
+        launch_column_sums(st, mh->partial, G, nC, mh->hist);
         HIPCHK(mh->h, hipGetLastError());
         hipLaunchKernelGGL(k_minkowski_suffix, dim3(1), dim3(kThreads), 0, st, mh->hist, mh->T, mh->res);
         HIPCHK(mh->h, hipGetLastError());
@@ -462,30 +381,10 @@ int slicer_minkowski_read(slicer_minkowski_handle mh, int64_t *faces, int64_t *e
         return fail(nullptr, SLICER_ERR_ARG, "slicer_minkowski_read: null handle");
     if (!mh->ran)
         return fail(mh->h, SLICER_ERR_STATE, "slicer_minkowski_read before any slicer_minkowski_run");
-    hipStream_t st;
-    if (int rc = sub_stream(mh->h, mh->device, &st))
-        return rc;
     const size_t T = (size_t)mh->T;
-    std::vector<int64_t> r(5 * T + 1);
-    HIPCHK(mh->h, hipMemcpyAsync(r.data(), mh->res, r.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(mh->h, hipStreamSynchronize(st));
-    int64_t *const outs[5] = {faces, edges, vertices, boundary, border};
-    for (size_t k = 0; k < 5; k++)
-        if (outs[k])
-            std::copy_n(&r[k * T], T, outs[k]);
-    if (n_nan)
-        *n_nan = r[5 * T];
-    return SLICER_OK;
+    return read_slices(*mh, mh->res, {{faces, T}, {edges, T}, {vertices, T}, {boundary, T}, {border, T}, {n_nan, 1}});
 }
 
-int slicer_minkowski_destroy(slicer_minkowski_handle mh)
-{
-    if (!mh)
-        return SLICER_ERR_ARG;
-    (void)hipSetDevice(mh->device);
-    (void)hipStreamSynchronize(mh->h->stream);
-    delete mh;
-    return SLICER_OK;
-}
+int slicer_minkowski_destroy(slicer_minkowski_handle mh) { return sub_destroy(mh); }
 
 }  // extern "C"

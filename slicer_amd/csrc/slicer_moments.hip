@@ -303,16 +303,13 @@ int floor_log2(int n)
 
 }  // namespace
 
-struct slicer_moments {
-    slicer_handle h = nullptr;
-    int device = 0;
+struct slicer_moments : SubHandle {
     int n0 = 0, levels = 0, mode = 0;
     std::vector<LevelGeom> geom;  // levels + 1
     std::vector<float *> maps;    // [0] unused (the caller's), 1 ... levels
     double *partial = nullptr, *res = nullptr;
     size_t pstride = 0;
     bool ran = false;
-    DevAllocs mem;
 };
 
 extern "C" {
@@ -329,12 +326,11 @@ int slicer_moments_depth(int32_t npix)
 int slicer_moments_create(slicer_handle h, int32_t npix, int32_t levels, int32_t mode, slicer_moments_handle *out)
 {
     // the numbers first: they need no handle, so a caller can have them checked before any device exists
+    const char *who = "slicer_moments_create";
     if (out)
         *out = nullptr;
-    if (npix < 1)
-        return fail(h, SLICER_ERR_ARG, "slicer_moments_create: npix must be positive");
-    if (npix > kMaxNpix)
-        return fail(h, SLICER_ERR_UNSUPPORTED, "slicer_moments_create: npix = %d above %d", npix, kMaxNpix);
+    if (int rc = npix_in_range(h, who, npix, kMaxNpix))
+        return rc;
     if (levels < 0 || levels > floor_log2(npix))
         return fail(h, SLICER_ERR_ARG, "slicer_moments_create: levels = %d outside 0..%d for npix = %d", levels,
                     floor_log2(npix), npix);
@@ -343,16 +339,10 @@ int slicer_moments_create(slicer_handle h, int32_t npix, int32_t levels, int32_t
                     mode);
     if (!h || !out)
         return fail(h, SLICER_ERR_ARG, "slicer_moments_create: null argument");
-    const char *who = "slicer_moments_create";
     hipStream_t st = nullptr;
-    int dev = 0;
-    if (int rc = sub_open(h, who, &st, &dev))
+    slicer_moments_handle mh = nullptr;
+    if (int rc = sub_new(h, who, &st, &mh))
         return rc;
-    slicer_moments_handle mh = new (std::nothrow) slicer_moments;
-    if (!mh)
-        return fail(h, SLICER_ERR_NOMEM, "out of host memory");
-    mh->h = h;
-    mh->device = dev;
     mh->n0 = npix;
     mh->levels = levels;
     mh->mode = mode;
@@ -368,12 +358,7 @@ int slicer_moments_create(slicer_handle h, int32_t npix, int32_t levels, int32_t
     mh->pstride = (size_t)most;
     rc = mh->mem.alloc(rc, h, who, (void **)&mh->partial, kValues * mh->pstride * sizeof(double));
     rc = mh->mem.alloc(rc, h, who, (void **)&mh->res, (size_t)(levels + 1) * kRes * sizeof(double));
-    if (rc != SLICER_OK) {
-        delete mh;
-        return rc;
-    }
-    *out = mh;
-    return SLICER_OK;
+    return sub_done(rc, mh, out);
 }
 
 int slicer_moments_run(slicer_moments_handle mh, const float *d_map, const double *centres)
@@ -455,12 +440,9 @@ int slicer_moments_read(slicer_moments_handle mh, int32_t *npix_level, double *m
         return fail(nullptr, SLICER_ERR_ARG, "slicer_moments_read: null handle");
     if (!mh->ran)
         return fail(mh->h, SLICER_ERR_STATE, "slicer_moments_read before any slicer_moments_run");
-    hipStream_t st;
-    if (int rc = sub_stream(mh->h, mh->device, &st))
-        return rc;
     std::vector<double> r((size_t)(mh->levels + 1) * kRes);
-    HIPCHK(mh->h, hipMemcpyAsync(r.data(), mh->res, r.size() * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(mh->h, hipStreamSynchronize(st));
+    if (int rc = sub_read(*mh, r.data(), mh->res, r.size() * sizeof(double)))
+        return rc;
     for (int l = 0; l <= mh->levels; l++) {
         if (npix_level)
             npix_level[l] = mh->geom[l].n;
@@ -494,23 +476,10 @@ int slicer_moments_read_map(slicer_moments_handle mh, int32_t level, float *host
     float *d = nullptr;
     if (int rc = slicer_moments_device_map(mh, level, &d))
         return rc;
-    hipStream_t st;
-    if (int rc = sub_stream(mh->h, mh->device, &st))
-        return rc;
     const size_t n = (size_t)mh->geom[level].n;
-    HIPCHK(mh->h, hipMemcpyAsync(host, d, n * n * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIPCHK(mh->h, hipStreamSynchronize(st));
-    return SLICER_OK;
+    return sub_read(*mh, host, d, n * n * sizeof(float));
 }
 
-int slicer_moments_destroy(slicer_moments_handle mh)
-{
-    if (!mh)
-        return SLICER_ERR_ARG;
-    (void)hipSetDevice(mh->device);
-    (void)hipStreamSynchronize(mh->h->stream);
-    delete mh;
-    return SLICER_OK;
-}
+int slicer_moments_destroy(slicer_moments_handle mh) { return sub_destroy(mh); }
 
 }  // extern "C"

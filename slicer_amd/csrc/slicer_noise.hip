@@ -18,7 +18,6 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
-#include <new>
 
 #include "slicer_host.hpp"
 #include "slicer_philox.hpp"
@@ -116,14 +115,11 @@ int sigma_ok(slicer_handle h, const char *who, double sigma)
 
 }  // namespace
 
-struct slicer_noise {
-    slicer_handle h = nullptr;
-    int device = 0;
+struct slicer_noise : SubHandle {
     int n = 0;
     uint64_t seed = 0;
     float *out = nullptr;
     uint64_t ran = 0;  // pixels of the last run, 0 before any
-    DevAllocs mem;
 };
 
 extern "C" {
@@ -134,30 +130,18 @@ int slicer_noise_create(slicer_handle h, int32_t npix, uint64_t seed, slicer_noi
     const char *who = "slicer_noise_create";
     if (out)
         *out = nullptr;
-    if (npix < 1)
-        return fail(h, SLICER_ERR_ARG, "%s: npix must be positive", who);
-    if (npix > kMaxNpix)
-        return fail(h, SLICER_ERR_UNSUPPORTED, "%s: npix = %d above %d", who, npix, kMaxNpix);
+    if (int rc = npix_in_range(h, who, npix, kMaxNpix))
+        return rc;
     if (!h || !out)
         return fail(h, SLICER_ERR_ARG, "%s: null argument", who);
     hipStream_t st = nullptr;
-    int dev = 0;
-    if (int rc = sub_open(h, who, &st, &dev))
+    slicer_noise_handle nh = nullptr;
+    if (int rc = sub_new(h, who, &st, &nh))
         return rc;
-    slicer_noise_handle nh = new (std::nothrow) slicer_noise;
-    if (!nh)
-        return fail(h, SLICER_ERR_NOMEM, "out of host memory");
-    nh->h = h;
-    nh->device = dev;
     nh->n = npix;
     nh->seed = seed;
     const int rc = nh->mem.alloc(SLICER_OK, h, who, (void **)&nh->out, (size_t)npix * (size_t)npix * sizeof(float));
-    if (rc != SLICER_OK) {
-        delete nh;
-        return rc;
-    }
-    *out = nh;
-    return SLICER_OK;
+    return sub_done(rc, nh, out);
 }
 
 int slicer_noise_run_at(slicer_noise_handle nh, const float *d_map, uint64_t first_pixel, uint64_t count, double sigma,
@@ -175,12 +159,9 @@ int slicer_noise_run_at(slicer_noise_handle nh, const float *d_map, uint64_t fir
     if (count < 1 || count > np2)
         return fail(h, SLICER_ERR_ARG, "%s: count = %llu outside 1..%llu", who, (unsigned long long)count,
                     (unsigned long long)np2);
-    if (d_map && d_map != nh->out) {  // the output itself is a second layer; any other overlap is refused
-        const uintptr_t in0 = (uintptr_t)d_map, in1 = in0 + count * sizeof(float);
-        const uintptr_t out0 = (uintptr_t)nh->out, out1 = out0 + np2 * sizeof(float);
-        if (in0 < out1 && out0 < in1)
-            return fail(h, SLICER_ERR_ARG, "%s: the input overlaps the handle's own output at another offset", who);
-    }
+    // the output itself is a second layer; any other overlap is refused
+    if (d_map && d_map != nh->out && ranges_overlap(d_map, count * sizeof(float), nh->out, np2 * sizeof(float)))
+        return fail(h, SLICER_ERR_ARG, "%s: the input overlaps the handle's own output at another offset", who);
     hipStream_t st;
     if (int rc = sub_stream(h, nh->device, &st))
         return rc;
@@ -269,22 +250,9 @@ int slicer_noise_read(slicer_noise_handle nh, float *out)
         return fail(nh ? nh->h : nullptr, SLICER_ERR_ARG, "slicer_noise_read: null argument");
     if (!nh->ran)
         return fail(nh->h, SLICER_ERR_STATE, "slicer_noise_read before any slicer_noise_run");
-    hipStream_t st;
-    if (int rc = sub_stream(nh->h, nh->device, &st))
-        return rc;
-    HIPCHK(nh->h, hipMemcpyAsync(out, nh->out, nh->ran * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIPCHK(nh->h, hipStreamSynchronize(st));
-    return SLICER_OK;
+    return sub_read(*nh, out, nh->out, nh->ran * sizeof(float));
 }
 
-int slicer_noise_destroy(slicer_noise_handle nh)
-{
-    if (!nh)
-        return SLICER_ERR_ARG;
-    (void)hipSetDevice(nh->device);
-    (void)hipStreamSynchronize(nh->h->stream);
-    delete nh;
-    return SLICER_OK;
-}
+int slicer_noise_destroy(slicer_noise_handle nh) { return sub_destroy(nh); }
 
 }  // extern "C"

@@ -8,7 +8,9 @@
 //              A comparison with a NaN is false, so a NaN and its neighbours are neither; ties give neither.
 // Every count is an integer: nothing here is a floating-point sum, so the results are exact and the same on every run.
 //
-// k_peaks: a workgroup of 256 threads takes tiles of kT0 x kT1 = 16 x 64 pixels (the tile of slicer_fd.hip), stages a
+// The tile, the search, the grid size and the column sums are those of slicer_rank_counts.hpp, shared with
+// slicer_minkowski.hip.
+// k_peaks: a workgroup of 256 threads takes tiles of kT0 x kT1 = 16 x 64 pixels, stages a
 // tile with a halo of one pixel in LDS as f32 and every thread takes four adjacent pixels of one row.  The window is
 // 18 rows of pitch 72 with the tile's first column at window column 4 (not 18 x 66): the sixteen float4s of a window row
 // then sit on LDS's 16-byte grid, so staging stores and a thread's three row reads are 128-bit accesses; the halo
@@ -16,43 +18,25 @@
 // (k_peaks<true>), scalar loads otherwise (k_peaks<false>); the window, and so the counts, are the same.
 // The grid is fixed: G = min(tiles, max(kMinGroups, w * CUs)) workgroups, w = min(8, what a CU's LDS holds at once),
 // workgroup b takes tiles b, b + G, ..., so a workgroup zeroes and flushes its counters once a launch.  The edges sit
-// in LDS as f64 (at most 8200 B); the bin is the number of e_0 ... e_{B-1} that are <= x, minus one, by a branch-free
-// binary search of ceil(log2 B) + 1 LDS reads -- the rule itself, no guess to correct; e_B only decides `above`, which
-// closes the last bin.  A thread searches its four pixels side by side, so the reads of one step do not wait for one
-// another.  The counters are three u32 histograms of B bins and the 7 outside counts in LDS
+// in LDS as f64 (at most 8200 B); the bin is the number of e_0 ... e_{B-1} that are <= x, minus one, by rank_search
+// over a thread's four pixels side by side; e_B only decides `above`, which closes the last bin.
+// The counters are three u32 histograms of B bins and the 7 outside counts in LDS
 // (at most 12316 B), incremented with LDS integer atomics; peaks and minima reuse the pixel's bin.
 // u32 is enough: a workgroup counts at most ceil(tiles / G) * 1024 pixels, and tiles <= (131072 / 16) * (131072 / 64)
 // = 2^24 with G >= min(tiles, 64) gives at most 2^18 * 2^10 = 2^28 < 2^32.
-// Flush: workgroup b stores its counters as row b of partial[G][3 B + 7]; k_peaks_finish sums the rows of every column
+// Flush: workgroup b stores its counters as row b of partial[G][3 B + 7]; k_column_sums sums the rows of every column
 // into int64.  Every row and every result is stored by every launch: nothing is zeroed between runs, nothing carried
 // over, no global atomics.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <cmath>
-#include <cstdint>
-#include <new>
-#include <vector>
-
-#include "slicer_host.hpp"
+#include "slicer_rank_counts.hpp"
 
 namespace {
 
-constexpr int kT0 = 16, kT1 = 64;  // tile: rows x columns
-constexpr int kPer = 4;            // adjacent pixels of a thread
-constexpr int kThreads = kT0 * kT1 / kPer;
-constexpr int kRows = kT0 + 2;
-constexpr int kLeft = 4;                  // window column of the tile's first pixel
-constexpr int kPitch = kLeft + kT1 + 4;   // 72 floats: every window row starts on the 16-byte grid
-constexpr int kQuads = kT1 / kPer;        // float4s of a tile row = threads of a tile row
-constexpr int kMaxNpix = 131072;
+constexpr int kRows = kT0 + 2;  // window rows: the tile and its halo
 constexpr int kMaxBins = SLICER_PEAKS_MAX_BINS;
-constexpr int kOutside = 7;               // below[3], above[3], nan
-constexpr int kPerCu = 8, kMinGroups = 64;     // workgroups per CU at most; fewer where their LDS does not fit
-constexpr size_t kLdsPerCu = 160 * 1024;       // gfx950
-constexpr int kFinCols = 16, kFinRows = 16;  // k_peaks_finish: columns of a workgroup x threads of a column
+constexpr int kOutside = 7;  // below[3], above[3], nan
 
-static_assert(kThreads == 256 && kFinCols * kFinRows == kThreads, "one thread per four pixels of a tile");
 static_assert(((int64_t)kMaxNpix / kT0) * (kMaxNpix / kT1) / kMinGroups * (kT0 * kT1) < (int64_t)1 << 32,
               "a workgroup's u32 counters hold every pixel it can meet");
 
@@ -118,27 +102,14 @@ __global__ __launch_bounds__(kThreads) void k_peaks(PeakArgs a)
             nb[d][1] = m.x, nb[d][2] = m.y, nb[d][3] = m.z, nb[d][4] = m.w;
             nb[d][5] = row[kPer];
         }
-        // pos[q]: how many of e_0 ... e_{B-1} are <= pixel q.  Invariant of the search: every edge before `pos` is
-        // <= x and the answer lies in pos ... pos + len.  The steps depend on B alone, so the wave never diverges, and
-        // the four pixels' reads of a step are independent of one another.  (Pixels past the map's edge are zeros of
-        // the window: searched, never counted.)
+        // pos[q]: how many of e_0 ... e_{B-1} are <= pixel q.  (Pixels past the map's edge are zeros of the window:
+        // searched, never counted.)
         double xd[kPer];
         int pos[kPer];
 #pragma unroll
-        for (int q = 0; q < kPer; q++) {
-            xd[q] = (double)nb[1][q + 1];
-            pos[q] = 0;
-        }
-        for (int len = B; len > 1;) {
-            const int half = len / 2;
-#pragma unroll
-            for (int q = 0; q < kPer; q++)
-                pos[q] = edge[pos[q] + half - 1] <= xd[q] ? pos[q] + half : pos[q];
-            len -= half;
-        }
-#pragma unroll
         for (int q = 0; q < kPer; q++)
-            pos[q] += edge[pos[q]] <= xd[q] ? 1 : 0;
+            xd[q] = (double)nb[1][q + 1];
+        rank_search(edge, B, xd, pos);
         const bool row_inside = i >= 1 && i <= n - 2;
 #pragma unroll
         for (int q = 0; q < kPer; q++) {
@@ -178,48 +149,11 @@ __global__ __launch_bounds__(kThreads) void k_peaks(PeakArgs a)
         out[k] = cnt[k];
 }
 
-// Workgroup v sums columns 16 v ... 16 v + 15 of partial[G][nC]: sixteen threads a column, thread rg of them the rows
-// rg, rg + 16, ...; integer sums, so the order does not matter.
-__global__ __launch_bounds__(kThreads) void k_peaks_finish(const unsigned *partial, int G, int nC, int64_t *res)
-{
-    __shared__ int64_t red[kFinRows][kFinCols];
-    const int cl = threadIdx.x % kFinCols, rg = threadIdx.x / kFinCols, col = (int)blockIdx.x * kFinCols + cl;
-    int64_t acc = 0;
-    if (col < nC) {
-#pragma unroll 8
-        for (int g = rg; g < G; g += kFinRows)
-            acc += (int64_t)partial[(size_t)g * nC + col];
-    }
-    red[rg][cl] = acc;
-    __syncthreads();
-    if (rg != 0 || col >= nC)
-        return;
-    for (int k = 1; k < kFinRows; k++)
-        acc += red[k][cl];
-    res[col] = acc;
-}
-
 size_t peaks_dyn_lds(int B) { return (size_t)(B + 1) * sizeof(double) + (3 * (size_t)B + kOutside) * sizeof(unsigned); }
-
-int64_t tiles_of(int n) { return (int64_t)((n + kT0 - 1) / kT0) * ((n + kT1 - 1) / kT1); }
-
-// 0, or the message of what is wrong with the edges
-const char *edges_fault(int32_t n_edges, const double *edges)
-{
-    for (int k = 0; k < n_edges; k++)
-        if (!std::isfinite(edges[k]))
-            return "edges must be finite";
-    for (int k = 1; k < n_edges; k++)
-        if (!(edges[k - 1] < edges[k]))
-            return "edges must be strictly ascending";
-    return nullptr;
-}
 
 }  // namespace
 
-struct slicer_peaks {
-    slicer_handle h = nullptr;
-    int device = 0;
+struct slicer_peaks : SubHandle {
     int n = 0, B = 0;
     int gmax = 0;  // rows of `partial`
     std::vector<double> edges;
@@ -227,7 +161,6 @@ struct slicer_peaks {
     unsigned *partial = nullptr;
     int64_t *res = nullptr;
     bool ran = false;
-    DevAllocs mem;
 };
 
 extern "C" {
@@ -245,7 +178,7 @@ int slicer_peaks_edges(double lo, double hi, int32_t bins, double *edges)
     for (int b = 1; b < bins; b++)
         edges[b] = lo + (double)b * width;  // (-ffp-contract=off: the product and the sum are rounded apart)
     edges[bins] = hi;
-    if (edges_fault(bins + 1, edges))
+    if (ascending_fault(bins + 1, edges))
         return fail(nullptr, SLICER_ERR_ARG,
                     "slicer_peaks_edges: the edges of lo = %.17g, hi = %.17g, bins = %d are not finite and strictly ascending",
                     lo, hi, bins);
@@ -255,38 +188,29 @@ int slicer_peaks_edges(double lo, double hi, int32_t bins, double *edges)
 int slicer_peaks_create(slicer_handle h, int32_t npix, int32_t n_edges, const double *edges, slicer_peaks_handle *out)
 {
     // the numbers first: they need no handle, so a caller can have them checked before any device exists
+    const char *who = "slicer_peaks_create";
     if (out)
         *out = nullptr;
-    if (npix < 1)
-        return fail(h, SLICER_ERR_ARG, "slicer_peaks_create: npix must be positive");
-    if (npix > kMaxNpix)
-        return fail(h, SLICER_ERR_UNSUPPORTED, "slicer_peaks_create: npix = %d above %d", npix, kMaxNpix);
+    if (int rc = npix_in_range(h, who, npix, kMaxNpix))
+        return rc;
     if (n_edges < 2)
         return fail(h, SLICER_ERR_ARG, "slicer_peaks_create: fewer than 2 edges");
     if (n_edges > kMaxBins + 1)
         return fail(h, SLICER_ERR_ARG, "slicer_peaks_create: %d edges, at most %d", n_edges, kMaxBins + 1);
     if (!edges)
         return fail(h, SLICER_ERR_ARG, "slicer_peaks_create: null argument");
-    if (const char *what = edges_fault(n_edges, edges))
-        return fail(h, SLICER_ERR_ARG, "slicer_peaks_create: %s", what);
+    if (const char *what = ascending_fault(n_edges, edges))
+        return fail(h, SLICER_ERR_ARG, "slicer_peaks_create: edges must be %s", what);
     if (!h || !out)
         return fail(h, SLICER_ERR_ARG, "slicer_peaks_create: null argument");
-    const char *who = "slicer_peaks_create";
     hipStream_t st = nullptr;
-    int dev = 0;
-    if (int rc = sub_open(h, who, &st, &dev))
+    slicer_peaks_handle ph = nullptr;
+    if (int rc = sub_new(h, who, &st, &ph))
         return rc;
-    slicer_peaks_handle ph = new (std::nothrow) slicer_peaks;
-    if (!ph)
-        return fail(h, SLICER_ERR_NOMEM, "out of host memory");
-    ph->h = h;
-    ph->device = dev;
     ph->n = npix;
     ph->B = n_edges - 1;
-    // as many workgroups as are resident at once: by LDS (the window, the edges, the counters), kPerCu at most
-    const size_t lds = kRows * kPitch * sizeof(float) + peaks_dyn_lds(ph->B);
-    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(kPerCu, kLdsPerCu / lds));
-    ph->gmax = (int)std::min<int64_t>(tiles_of(npix), std::max(kMinGroups, per_cu * h->num_cus));
+    // the LDS of a workgroup: the window, the edges, the counters
+    ph->gmax = resident_groups(kRows * kPitch * sizeof(float) + peaks_dyn_lds(ph->B), tiles_of(npix), h->num_cus);
     ph->edges.assign(edges, edges + n_edges);
     const size_t nC = 3 * (size_t)ph->B + kOutside;
     int rc = SLICER_OK;
@@ -299,12 +223,7 @@ int slicer_peaks_create(slicer_handle h, int32_t npix, int32_t n_edges, const do
         if (e != hipSuccess)
             rc = fail(h, SLICER_ERR_HIP, "%s: copying the edges: %s", who, hipGetErrorString(e));
     }
-    if (rc != SLICER_OK) {
-        delete ph;
-        return rc;
-    }
-    *out = ph;
-    return SLICER_OK;
+    return sub_done(rc, ph, out);
 }
 
 int slicer_peaks_run_npix(slicer_peaks_handle ph, const float *d_map, int32_t npix)
@@ -324,13 +243,13 @@ int slicer_peaks_run_npix(slicer_peaks_handle ph, const float *d_map, int32_t np
     a.partial = ph->partial;
     a.n = npix;
     a.B = ph->B;
-    a.tiles_x = (npix + kT1 - 1) / kT1;
+    a.tiles_x = tiles_across(npix);
     a.ntiles = (int)tiles_of(npix);
     const int G = std::min(a.ntiles, ph->gmax);
     const size_t lds = peaks_dyn_lds(ph->B);
     {
         ProfScope ps(ph->h, KN_PEAKS);
-        if (npix % 4 == 0 && (uintptr_t)d_map % 16 == 0)
+        if (quads_aligned(d_map, npix))
             hipLaunchKernelGGL(k_peaks<true>, dim3((unsigned)G), dim3(kThreads), lds, st, a);
         else
             hipLaunchKernelGGL(k_peaks<false>, dim3((unsigned)G), dim3(kThreads), lds, st, a);
@@ -338,8 +257,7 @@ int slicer_peaks_run_npix(slicer_peaks_handle ph, const float *d_map, int32_t np
     }
     {
         ProfScope ps(ph->h, KN_PEAKS_FINISH);
-        hipLaunchKernelGGL(k_peaks_finish, dim3((unsigned)((nC + kFinCols - 1) / kFinCols)), dim3(kThreads), 0, st,
-                           ph->partial, G, nC, ph->res);
+        launch_column_sums(st, ph->partial, G, nC, ph->res);
         HIPCHK(ph->h, hipGetLastError());
     }
     ph->ran = true;
@@ -360,36 +278,10 @@ int slicer_peaks_read(slicer_peaks_handle ph, int64_t *pdf, int64_t *peaks, int6
         return fail(nullptr, SLICER_ERR_ARG, "slicer_peaks_read: null handle");
     if (!ph->ran)
         return fail(ph->h, SLICER_ERR_STATE, "slicer_peaks_read before any slicer_peaks_run");
-    hipStream_t st;
-    if (int rc = sub_stream(ph->h, ph->device, &st))
-        return rc;
     const size_t B = (size_t)ph->B;
-    std::vector<int64_t> r(3 * B + kOutside);
-    HIPCHK(ph->h, hipMemcpyAsync(r.data(), ph->res, r.size() * sizeof(int64_t), hipMemcpyDeviceToHost, st));
-    HIPCHK(ph->h, hipStreamSynchronize(st));
-    if (pdf)
-        std::copy_n(&r[0], B, pdf);
-    if (peaks)
-        std::copy_n(&r[B], B, peaks);
-    if (minima)
-        std::copy_n(&r[2 * B], B, minima);
-    if (below)
-        std::copy_n(&r[3 * B], 3, below);
-    if (above)
-        std::copy_n(&r[3 * B + 3], 3, above);
-    if (n_nan)
-        *n_nan = r[3 * B + 6];
-    return SLICER_OK;
+    return read_slices(*ph, ph->res, {{pdf, B}, {peaks, B}, {minima, B}, {below, 3}, {above, 3}, {n_nan, 1}});
 }
 
-int slicer_peaks_destroy(slicer_peaks_handle ph)
-{
-    if (!ph)
-        return SLICER_ERR_ARG;
-    (void)hipSetDevice(ph->device);
-    (void)hipStreamSynchronize(ph->h->stream);
-    delete ph;
-    return SLICER_OK;
-}
+int slicer_peaks_destroy(slicer_peaks_handle ph) { return sub_destroy(ph); }
 
 }  // extern "C"

@@ -261,10 +261,8 @@ void bin_modes(int n, const std::vector<double> &edges, std::vector<int64_t> &co
 
 }  // namespace
 
-struct slicer_power_s {
-    slicer_handle h = nullptr;
+struct slicer_power_s : SubHandle {
     slicer_fft_s *fft = nullptr;
-    int device = 0;
     int n = 0, H = 0, S = 0, cross = 0, B = 0, npairs = 0, nslices = 0;
     double ell_f = 0.0, norm = 0.0;
     std::vector<int64_t> counts;
@@ -274,7 +272,6 @@ struct slicer_power_s {
     int4 *slices = nullptr;
     int *slice_off = nullptr;
     bool ran = false;
-    DevAllocs mem;
     SLICER_FFT_INTERNAL ~slicer_power_s() { slicer_fft_destroy(fft); }
 };
 
@@ -355,16 +352,10 @@ int slicer_power_create(slicer_handle h, int32_t npix, double angle_deg, int32_t
         return fail(h, SLICER_ERR_ARG, "slicer_power_create: the angle must be positive and finite");
     const char *who = "slicer_power_create";
     hipStream_t st = nullptr;
-    int dev = 0;
-    if (int rc = sub_open(h, who, &st, &dev))
+    slicer_power_handle ph = nullptr;
+    if (int rc = sub_new(h, who, &st, &ph))
         return rc;
-
-    slicer_power_handle ph = new (std::nothrow) slicer_power_s;
-    if (!ph)
-        return fail(h, SLICER_ERR_NOMEM, "out of host memory");
     const int n = npix, H = n / 2 + 1, B = n_edges - 1;
-    ph->h = h;
-    ph->device = dev;
     ph->n = n;
     ph->H = H;
     ph->S = n_maps;
@@ -401,7 +392,7 @@ int slicer_power_create(slicer_handle h, int32_t npix, double angle_deg, int32_t
     off[B] = (int)sl.size();
     ph->nslices = (int)sl.size();
 
-    int rc = slicer_fft_create(h, n, h->opt.shear_split, st, dev, who, &ph->fft);
+    int rc = slicer_fft_create(h, n, h->opt.shear_split, st, ph->device, who, &ph->fft);
     rc = ph->mem.alloc(rc, h, who, (void **)&ph->spec, (size_t)(cross ? n_maps : 1) * n * H * sizeof(double2));
     rc = ph->mem.alloc(rc, h, who, (void **)&ph->e2, (B + 1) * sizeof(double));
     rc = ph->mem.alloc(rc, h, who, (void **)&ph->partial, (size_t)(cross ? ph->npairs : 1) * ph->nslices * sizeof(double));
@@ -422,12 +413,7 @@ int slicer_power_create(slicer_handle h, int32_t npix, double angle_deg, int32_t
     up(ph->slice_off, off.data(), (B + 1) * sizeof(int));
     if (rc == SLICER_OK && hipStreamSynchronize(st) != hipSuccess)  // the sources are host temporaries
         rc = fail(h, SLICER_ERR_HIP, "slicer_power_create: upload failed");
-    if (rc != SLICER_OK) {
-        delete ph;
-        return rc;
-    }
-    *out = ph;
-    return SLICER_OK;
+    return sub_done(rc, ph, out);
 }
 
 int slicer_power_run(slicer_power_handle ph, const float *const *d_maps)
@@ -478,14 +464,8 @@ int slicer_power_spectrum(slicer_power_handle ph, int32_t map, double *host)
         return fail(ph->h, SLICER_ERR_STATE, "slicer_power_spectrum before any slicer_power_run");
     if (!ph->cross && map != ph->S - 1)
         return fail(ph->h, SLICER_ERR_STATE, "slicer_power_spectrum: auto mode keeps only the last map's spectrum");
-    hipStream_t st;
-    if (int rc = sub_stream(ph->h, ph->device, &st))
-        return rc;
     const size_t stride = (size_t)ph->n * ph->H;
-    HIPCHK(ph->h, hipMemcpyAsync(host, ph->spec + (ph->cross ? map * stride : 0), stride * sizeof(double2),
-                               hipMemcpyDeviceToHost, st));
-    HIPCHK(ph->h, hipStreamSynchronize(st));
-    return SLICER_OK;
+    return sub_read(*ph, host, ph->spec + (ph->cross ? map * stride : 0), stride * sizeof(double2));
 }
 
 int slicer_power_read(slicer_power_handle ph, double *cl, double *ell_mean, int64_t *counts)
@@ -509,12 +489,4 @@ int slicer_power_read(slicer_power_handle ph, double *cl, double *ell_mean, int6
     return SLICER_OK;
 }
 
-int slicer_power_destroy(slicer_power_handle ph)
-{
-    if (!ph)
-        return SLICER_ERR_ARG;
-    (void)hipSetDevice(ph->device);
-    (void)hipStreamSynchronize(ph->h->stream);
-    delete ph;
-    return SLICER_OK;
-}
+int slicer_power_destroy(slicer_power_handle ph) { return sub_destroy(ph); }

@@ -244,15 +244,12 @@ bool positive_finite(double x) { return std::isfinite(x) && x > 0.0; }
 
 }  // namespace
 
-struct slicer_rays {
-    slicer_handle h = nullptr;
-    int device = 0;
+struct slicer_rays : SubHandle {
     int n = 0;
     double d = 0.0;
     double *s[kState] = {};
     int n_steps = 0;
     double chi_last = 0.0;
-    DevAllocs mem;
 };
 
 extern "C" {
@@ -260,37 +257,25 @@ extern "C" {
 int slicer_rays_create(slicer_handle h, int32_t npix, double spacing, slicer_rays_handle *out)
 {
     // the numbers first: they need no handle, so a caller can have them checked before any device exists
+    const char *who = "slicer_rays_create";
     if (out)
         *out = nullptr;
-    if (npix < 1)
-        return fail(h, SLICER_ERR_ARG, "slicer_rays_create: npix must be positive");
-    if (npix > kMaxNpix)
-        return fail(h, SLICER_ERR_UNSUPPORTED, "slicer_rays_create: npix = %d above %d", npix, kMaxNpix);
+    if (int rc = npix_in_range(h, who, npix, kMaxNpix))
+        return rc;
     if (!positive_finite(spacing))
         return fail(h, SLICER_ERR_ARG, "slicer_rays_create: the spacing must be positive and finite");
     if (!h || !out)
         return fail(h, SLICER_ERR_ARG, "slicer_rays_create: null argument");
-    const char *who = "slicer_rays_create";
     hipStream_t st = nullptr;
-    int dev = 0;
-    if (int rc = sub_open(h, who, &st, &dev))
+    slicer_rays_handle rh = nullptr;
+    if (int rc = sub_new(h, who, &st, &rh))
         return rc;
-    slicer_rays_handle rh = new (std::nothrow) slicer_rays;
-    if (!rh)
-        return fail(h, SLICER_ERR_NOMEM, "out of host memory");
-    rh->h = h;
-    rh->device = dev;
     rh->n = npix;
     rh->d = spacing;
     int rc = SLICER_OK;
     for (int k = 0; k < kState; k++)
         rc = rh->mem.alloc(rc, h, who, (void **)&rh->s[k], (size_t)npix * (size_t)npix * sizeof(double));
-    if (rc != SLICER_OK) {
-        delete rh;
-        return rc;
-    }
-    *out = rh;
-    return SLICER_OK;
+    return sub_done(rc, rh, out);
 }
 
 int slicer_rays_reset(slicer_rays_handle rh)
@@ -431,14 +416,6 @@ int slicer_rays_planes(slicer_rays_handle rh, int32_t *n_steps, double *chi_last
     return SLICER_OK;
 }
 
-int slicer_rays_destroy(slicer_rays_handle rh)
-{
-    if (!rh)
-        return SLICER_ERR_ARG;
-    (void)hipSetDevice(rh->device);
-    (void)hipStreamSynchronize(rh->h->stream);
-    delete rh;
-    return SLICER_OK;
-}
+int slicer_rays_destroy(slicer_rays_handle rh) { return sub_destroy(rh); }
 
 }  // extern "C"

@@ -369,8 +369,7 @@ struct slicer_fft_s {
     DevAllocs mem;
 };
 
-struct slicer_shear_s {
-    slicer_handle h = nullptr;
+struct slicer_shear_s : SubHandle {
     slicer_fft_s *fft = nullptr;
     double angle = 0.0;
     double2 *S = nullptr, *G = nullptr;  // complex f64, n * H each
@@ -379,7 +378,6 @@ struct slicer_shear_s {
     float *fd[SLICER_FD_COUNT] = {};       // allocated by the first slicer_shear_fd
     bool ran = false;
     bool alpha_ok = false, fd_ok = false;  // alpha / fd belong to the last run
-    DevAllocs mem;
     SLICER_FFT_INTERNAL ~slicer_shear_s() { slicer_fft_destroy(fft); }
 };
 
@@ -543,30 +541,20 @@ int slicer_shear_create(slicer_handle h, int32_t npix, double angle_deg, slicer_
                     "slicer_shear_create: npix = %d unsupported (2..%d, prime factors 2, 3, 5, 7 only)", npix, kMaxN);
     if (!std::isfinite(angle_deg) || angle_deg <= 0.0)
         return fail(h, SLICER_ERR_ARG, "slicer_shear_create: the angle must be positive and finite");
-    slicer_shear_handle sh = new (std::nothrow) slicer_shear_s;
-    if (!sh)
-        return fail(h, SLICER_ERR_NOMEM, "out of host memory");
-    const int n = npix;
-    sh->h = h;
-    sh->angle = angle_deg;
-
     const char *who = "slicer_shear_create";
     hipStream_t st = nullptr;
-    int dev = 0;
-    int rc = sub_open(h, who, &st, &dev);
-    if (rc == SLICER_OK)
-        rc = slicer_fft_create(h, n, h->opt.shear_split, st, dev, who, &sh->fft);
+    slicer_shear_handle sh = nullptr;
+    if (int rc = sub_new(h, who, &st, &sh))
+        return rc;
+    const int n = npix;
+    sh->angle = angle_deg;
+    int rc = slicer_fft_create(h, n, h->opt.shear_split, st, sh->device, who, &sh->fft);
     const size_t cbytes = (size_t)n * (n / 2 + 1) * sizeof(double2);
     rc = sh->mem.alloc(rc, h, who, (void **)&sh->S, cbytes);
     rc = sh->mem.alloc(rc, h, who, (void **)&sh->G, cbytes);
     for (float *&m : sh->maps)
         rc = sh->mem.alloc(rc, h, who, (void **)&m, (size_t)n * n * sizeof(float));
-    if (rc != SLICER_OK) {
-        delete sh;
-        return rc;
-    }
-    *out = sh;
-    return SLICER_OK;
+    return sub_done(rc, sh, out);
 }
 
 int slicer_shear_run(slicer_shear_handle sh, const float *d_kappa)
@@ -574,7 +562,7 @@ int slicer_shear_run(slicer_shear_handle sh, const float *d_kappa)
     if (!sh || !d_kappa)
         return fail(sh ? sh->h : nullptr, SLICER_ERR_ARG, "slicer_shear_run: null argument");
     hipStream_t st;
-    if (int rc = sub_stream(sh->h, sh->fft->device, &st))
+    if (int rc = sub_stream(sh->h, sh->device, &st))
         return rc;
     slicer_fft_s *f = sh->fft;
     const int n = f->n, H = f->H, len = f->len;
@@ -620,7 +608,7 @@ int slicer_shear_deflection(slicer_shear_handle sh)
     if (!sh->ran)
         return fail(sh->h, SLICER_ERR_STATE, "slicer_shear_deflection before any slicer_shear_run");
     hipStream_t st;
-    if (int rc = sub_stream(sh->h, sh->fft->device, &st))
+    if (int rc = sub_stream(sh->h, sh->device, &st))
         return rc;
     slicer_fft_s *f = sh->fft;
     const int n = f->n;
@@ -659,7 +647,7 @@ int slicer_shear_fd(slicer_shear_handle sh)
     if (!sh->ran)
         return fail(sh->h, SLICER_ERR_STATE, "slicer_shear_fd before any slicer_shear_run");
     hipStream_t st;
-    if (int rc = sub_stream(sh->h, sh->fft->device, &st))
+    if (int rc = sub_stream(sh->h, sh->device, &st))
         return rc;
     int rc = SLICER_OK;
     for (float *&m : sh->fd)
@@ -680,12 +668,7 @@ int slicer_shear_spectrum(slicer_shear_handle sh, double *host)
         return fail(sh ? sh->h : nullptr, SLICER_ERR_ARG, "slicer_shear_spectrum: null argument");
     if (!sh->ran)
         return fail(sh->h, SLICER_ERR_STATE, "slicer_shear_spectrum before any slicer_shear_run");
-    hipStream_t st;
-    if (int rc = sub_stream(sh->h, sh->fft->device, &st))
-        return rc;
-    HIPCHK(sh->h, hipMemcpyAsync(host, sh->S, (size_t)sh->fft->n * sh->fft->H * sizeof(double2), hipMemcpyDeviceToHost, st));
-    HIPCHK(sh->h, hipStreamSynchronize(st));
-    return SLICER_OK;
+    return sub_read(*sh, host, sh->S, (size_t)sh->fft->n * sh->fft->H * sizeof(double2));
 }
 
 int slicer_shear_device_map(slicer_shear_handle sh, int32_t which, float **d_map)
@@ -719,20 +702,7 @@ int slicer_shear_read(slicer_shear_handle sh, int32_t which, float *host)
         return rc;
     if (!host)
         return fail(sh->h, SLICER_ERR_ARG, "slicer_shear_read: null host pointer");
-    hipStream_t st;
-    if (int rc = sub_stream(sh->h, sh->fft->device, &st))
-        return rc;
-    HIPCHK(sh->h, hipMemcpyAsync(host, d, (size_t)sh->fft->n * sh->fft->n * sizeof(float), hipMemcpyDeviceToHost, st));
-    HIPCHK(sh->h, hipStreamSynchronize(st));
-    return SLICER_OK;
+    return sub_read(*sh, host, d, (size_t)sh->fft->n * sh->fft->n * sizeof(float));
 }
 
-int slicer_shear_destroy(slicer_shear_handle sh)
-{
-    if (!sh)
-        return SLICER_ERR_ARG;
-    (void)hipSetDevice(sh->fft->device);
-    (void)hipStreamSynchronize(sh->h->stream);
-    delete sh;
-    return SLICER_OK;
-}
+int slicer_shear_destroy(slicer_shear_handle sh) { return sub_destroy(sh); }

@@ -317,9 +317,7 @@ int radius_of(slicer_handle h, const char *who, double sigma_pix, double truncat
 
 }  // namespace
 
-struct slicer_smooth {
-    slicer_handle h = nullptr;
-    int device = 0;
+struct slicer_smooth : SubHandle {
     int n = 0, kind = 0, R = 0;
     double c = 0.0;  // MAP: 1 / (2 pi s s)
     ColsCfg cols;
@@ -328,7 +326,6 @@ struct slicer_smooth {
     double *mid = nullptr, *norm = nullptr;
     float *out = nullptr;
     int ran_n = 0;  // npix of the last run, 0 before any
-    DevAllocs mem;
 };
 
 extern "C" {
@@ -359,10 +356,8 @@ int slicer_smooth_create(slicer_handle h, int32_t npix, int32_t kind, double sig
     const char *who = "slicer_smooth_create";
     if (out)
         *out = nullptr;
-    if (npix < 1)
-        return fail(h, SLICER_ERR_ARG, "%s: npix must be positive", who);
-    if (npix > kMaxNpix)
-        return fail(h, SLICER_ERR_UNSUPPORTED, "%s: npix = %d above %d", who, npix, kMaxNpix);
+    if (int rc = npix_in_range(h, who, npix, kMaxNpix))
+        return rc;
     if (kind != SLICER_SMOOTH_GAUSS && kind != SLICER_SMOOTH_MAP)
         return fail(h, SLICER_ERR_ARG, "%s: kind = %d is neither SLICER_SMOOTH_GAUSS nor SLICER_SMOOTH_MAP", who, kind);
     int R = 0;
@@ -371,14 +366,9 @@ int slicer_smooth_create(slicer_handle h, int32_t npix, int32_t kind, double sig
     if (!h || !out)
         return fail(h, SLICER_ERR_ARG, "%s: null argument", who);
     hipStream_t st = nullptr;
-    int dev = 0;
-    if (int rc = sub_open(h, who, &st, &dev))
+    slicer_smooth_handle sh = nullptr;
+    if (int rc = sub_new(h, who, &st, &sh))
         return rc;
-    slicer_smooth_handle sh = new (std::nothrow) slicer_smooth;
-    if (!sh)
-        return fail(h, SLICER_ERR_NOMEM, "out of host memory");
-    sh->h = h;
-    sh->device = dev;
     sh->n = npix;
     sh->kind = kind;
     sh->R = R;
@@ -404,12 +394,7 @@ int slicer_smooth_create(slicer_handle h, int32_t npix, int32_t kind, double sig
         if (e != hipSuccess)
             rc = fail(h, SLICER_ERR_HIP, "%s: copying the weights: %s", who, hipGetErrorString(e));
     }
-    if (rc != SLICER_OK) {
-        delete sh;
-        return rc;
-    }
-    *out = sh;
-    return SLICER_OK;
+    return sub_done(rc, sh, out);
 }
 
 int slicer_smooth_run_npix(slicer_smooth_handle sh, const float *d_map, int32_t npix)
@@ -419,9 +404,7 @@ int slicer_smooth_run_npix(slicer_smooth_handle sh, const float *d_map, int32_t 
     if (npix < 1 || npix > sh->n)
         return fail(sh->h, SLICER_ERR_ARG, "slicer_smooth_run_npix: npix = %d outside 1..%d", npix, sh->n);
     const size_t np2 = (size_t)npix * (size_t)npix;
-    const uintptr_t in0 = (uintptr_t)d_map, in1 = in0 + np2 * sizeof(float);
-    const uintptr_t out0 = (uintptr_t)sh->out, out1 = out0 + (size_t)sh->n * (size_t)sh->n * sizeof(float);
-    if (in0 < out1 && out0 < in1)
+    if (ranges_overlap(d_map, np2 * sizeof(float), sh->out, (size_t)sh->n * (size_t)sh->n * sizeof(float)))
         return fail(sh->h, SLICER_ERR_ARG, "slicer_smooth_run_npix: the input overlaps the handle's own output");
     hipStream_t st;
     if (int rc = sub_stream(sh->h, sh->device, &st))
@@ -508,23 +491,9 @@ int slicer_smooth_read(slicer_smooth_handle sh, float *out)
         return fail(sh ? sh->h : nullptr, SLICER_ERR_ARG, "slicer_smooth_read: null argument");
     if (!sh->ran_n)
         return fail(sh->h, SLICER_ERR_STATE, "slicer_smooth_read before any slicer_smooth_run");
-    hipStream_t st;
-    if (int rc = sub_stream(sh->h, sh->device, &st))
-        return rc;
-    const size_t bytes = (size_t)sh->ran_n * (size_t)sh->ran_n * sizeof(float);
-    HIPCHK(sh->h, hipMemcpyAsync(out, sh->out, bytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(sh->h, hipStreamSynchronize(st));
-    return SLICER_OK;
+    return sub_read(*sh, out, sh->out, (size_t)sh->ran_n * (size_t)sh->ran_n * sizeof(float));
 }
 
-int slicer_smooth_destroy(slicer_smooth_handle sh)
-{
-    if (!sh)
-        return SLICER_ERR_ARG;
-    (void)hipSetDevice(sh->device);
-    (void)hipStreamSynchronize(sh->h->stream);
-    delete sh;
-    return SLICER_OK;
-}
+int slicer_smooth_destroy(slicer_smooth_handle sh) { return sub_destroy(sh); }
 
 }  // extern "C"
