@@ -194,7 +194,7 @@ __global__ __launch_bounds__(kSortBlock, SLICER_K3_WAVES) void k_bin_scatter(con
     // same L2.
     const int per_unit = 8 * ((nblocks + 7) / 8);
     const int per_xcd = per_unit / 8;
-    const int per = (tpp + kSortBlock - 1) / kSortBlock;  // tiles per lane in the scan (<= 8)
+    const int per = (tpp + kSortBlock - 1) / kSortBlock;  // tiles per lane in the scan (<= 16: tiles_per_unit <= 8192)
     auto get16 = [](const unsigned *tab, unsigned t) { return (tab[t >> 1] >> ((t & 1u) * 16u)) & 0xFFFFu; };
     constexpr int R = kSortBatch / kSortBlock;  // records per lane and sub-batch
     // largest selected mass of the species (as the deposit sees it: above MAX_M counts as 0) -> the quantum of integer

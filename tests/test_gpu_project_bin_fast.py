@@ -35,7 +35,9 @@ FIXA, F32A = slicer_amd.ACC_FIXED64, slicer_amd.ACC_F32
 M_CONST = 0.0123
 SLABS4 = [3.0, 3.25, 3.5, 3.75, 4.0]  # four consecutive slabs of one box replication (rcase 3)
 FAST, GENERAL = 1 << 4, 1 << 5
-OPTION_KEYS = ("k4_int", "tile_log2", "tile_h_log2", "bin_batch", "unit_rows", "k1_general", "k1_stack", "sort2", "pending")
+OPTION_KEYS = ("k4_int", "tile_log2", "tile_h_log2", "bin_batch", "unit_rows", "k1_general", "k1_stack", "sort2", "pending",
+               "k3_per_cu")
+GEOMETRY_KEYS = ("tile_log2", "tile_h_log2", "pending", "k3_per_cu")  # run() sets these only where a caller names them
 SERIES_MAX9 = 0.155  # slicer_device.hpp: kSeriesMax9 (fov 0.25 runs the 9-term series)
 
 
@@ -121,6 +123,10 @@ def run(S, ex, ngp, chunks=None, deposit=None, **options):
     ps, r, n = ex.ps, ex.ps.rnd, len(ex.pos)
     for k in ("k1_general", "k1_stack", "sort2", "unit_rows", "bin_batch"):
         S.set_option(k, options.get(k, {"k1_stack": -1}.get(k, 0)))
+    for k in GEOMETRY_KEYS:  # (tests/test_gpu_sort.py forces the whole geometry; the S fixture puts the values back)
+        if k in options:
+            S.set_option(k, options[k])
+    assert not set(options) - set(OPTION_KEYS), set(options) - set(OPTION_KEYS)
     S.plane_begin(ps.npix, ps.fov, [a for a, _ in ps.slabs], [b for _, b in ps.slabs], [ps.nrep] * len(ps.slabs),
                   mas=slicer_amd.MAS_NGP if ngp else slicer_amd.MAS_TSC, accum=F32A if ngp else FIXA,
                   algo=slicer_amd.ALGO_BINNED, hydro=ex.hydro)
