@@ -804,6 +804,74 @@ int slicer_noise_device_map(slicer_noise_handle nh, float **d_out);
 int slicer_noise_read(slicer_noise_handle nh, float *out);
 int slicer_noise_destroy(slicer_noise_handle nh);
 
+/* ---- Starlet transform of a map and binned absolute sums, the starlet l1-norm ----
+ * The starlet is the isotropic undecimated wavelet transform with the B3-spline (a trous).  The input is any device f32 map
+ * x of npix^2 pixels (row-major), 1 <= npix <= 131072, which is only read; the outputs are J + 1 f32 maps of npix^2 pixels
+ * owned by the handle, 1 <= J <= SLICER_STARLET_MAX_SCALES.
+ * Index rule: the map is mirrored about its edge pixels, which are not repeated.  refl(i) = 0 for npix = 1; otherwise
+ * m = i mod 2 (npix - 1) taken non-negative and refl(i) = m if m < npix, else 2 (npix - 1) - m.  The rule is applied as often
+ * as needed: the reach 2 * 2^j may exceed npix many times over.
+ * Line operator A_d along one axis, on f64 values v, step d = 2^j, every operation one IEEE f64 operation rounded once (RN),
+ * no FMA:  a = RN(v[refl(i - d)] + v[refl(i + d)]);  b = RN(v[refl(i - 2 d)] + v[refl(i + 2 d)]);
+ *   out[i] = RN(RN(RN(RN(6 v[i]) + RN(4 a)) + b) * 0.0625).
+ * Levels: c_0 is x widened exactly; for j = 0 ... J-1, c_{j+1} = A_d along axis 0 of (A_d along axis 1 of c_j) and
+ * w_{j+1} = RN32(RN(c_j - c_{j+1})); the coarse map is RN32(c_J).  The c_j are f64 and are never rounded to f32 between
+ * levels.
+ * NaN and +-inf pixels propagate by IEEE; NaN payloads and the sign of a zero are not part of the contract.  The same input
+ * gives the same bits on every run; a numpy restatement reproduces every output value.  It follows that a constant map has
+ * coarse == the map and every w_j == 0 exactly, and that, summed in f64, |coarse + sum_j w_j - x| <=
+ * 2^-24 (|coarse| + sum_j |w_j|) (1 + 2^-20) per pixel: the computed c_j telescope exactly, only the J + 1 roundings to f32
+ * remain.  Out of scope: the second-generation (positive-reconstruction) starlet, decimated transforms, masks, periodic
+ * boundaries.
+ *   slicer_starlet_gains       host only: gain_w [scales], the rms of w_1 ... w_scales, and gain_coarse, that of the coarse
+ *                              map, for white noise of unit variance at a pixel farther than the reach from every edge
+ *                              (either may be NULL).  In long double from the exact integer tables H_0 = delta, H_j =
+ *                              H_{j-1} * (1, 4, 6, 4, 1) / 16 dilated by 2^{j-1}: gain_j = sqrt(sum_ab (H_{j-1}[a] H_{j-1}[b] -
+ *                              H_j[a] H_j[b])^2), gain_coarse = sum_a H_J[a]^2; 0.8907963, 0.2006639, 0.0855075, ...  scales
+ *                              outside 1..12: SLICER_ERR_ARG (message through slicer_last_error(NULL))
+ *   slicer_starlet_create      on the device and stream of h (create it after any slicer_set_stream, destroy it before h).
+ *                              The numbers are checked before the handle, so that they can be checked without a device:
+ *                              npix < 1 or scales outside 1..12: SLICER_ERR_ARG; npix > 131072: SLICER_ERR_UNSUPPORTED.
+ *                              Device memory: 4 (J + 1) bytes a pixel of outputs and 16 of f64 levels (SLICER_ERR_NOMEM)
+ *   slicer_starlet_run         any device f32 map of the handle's npix^2 pixels; one kernel a level, enqueued, no
+ *                              synchronisation.  SLICER_ERR_ARG: a NULL map, a map that overlaps the handle's own buffers
+ *   slicer_starlet_run_npix    the same of a smaller map of npix^2 pixels, 1 <= npix <= the handle's (others:
+ *                              SLICER_ERR_ARG), so that one handle serves every level of a moments pyramid
+ *   slicer_starlet_device_map  scale 1 ... J: w_scale of the last run; scale 0: the coarse map (others: SLICER_ERR_ARG);
+ *                              npix^2 floats of that run, valid until the next run or destroy
+ *   slicer_starlet_read        the same to the host; waits for the stream.  Both before any run: SLICER_ERR_STATE
+ * Binned absolute sums.  The input is any device f32 map of npix^2 pixels, 1 <= npix <= 131072, which is only read; the edges
+ * are those of slicer_peaks_*: f64, finite, strictly ascending, 1 <= B <= SLICER_PEAKS_MAX_BINS.  The bin of a pixel is the
+ * PDF's of row N10: x widened exactly to f64 and compared in f64, the last bin closed, `below`, `above` and `nan` as there.
+ * Per bin the int64 count, exact and equal to slicer_peaks_read's pdf, and the f64 sum of |x| over the bin's pixels (|x|
+ * widened is exact); `below` and `above` have sums too; NaN pixels enter no sum.  The sums are accumulated in f64 over a
+ * fixed partition of the map with no floating-point atomics: two runs give the same bits; the order is otherwise the
+ * implementation's.  Against the exact sum S_b: |sum_b - S_b| <= count_b 2^-53 S_b (all terms are non-negative, so any order
+ * of count_b - 1 additions stays inside it).
+ *   slicer_l1norm_create    arguments, refusals and their order as slicer_peaks_create.  Device memory: the edges, 16 B + 40
+ *                           bytes of results and at most max(64, 8 per compute unit) rows of 12 B + 28 bytes
+ *   slicer_l1norm_run       any device f32 map of the handle's npix^2 pixels (e.g. slicer_starlet_device_map); enqueued, no
+ *                           synchronisation.  A NULL map: SLICER_ERR_ARG
+ *   slicer_l1norm_run_npix  the same of a smaller map of npix^2 pixels, 1 <= npix <= the handle's (others: SLICER_ERR_ARG)
+ *   slicer_l1norm_read      counts, sums [B] each, below, above, the NaN count, below_sum, above_sum [1] each, of the last run
+ *                           (any of them NULL); waits for the stream.  Before any run: SLICER_ERR_STATE */
+typedef struct slicer_starlet *slicer_starlet_handle;
+typedef struct slicer_l1norm *slicer_l1norm_handle;
+#define SLICER_STARLET_MAX_SCALES 12
+int slicer_starlet_gains(int32_t scales, double *gain_w, double *gain_coarse);
+int slicer_starlet_create(slicer_handle h, int32_t npix, int32_t scales, slicer_starlet_handle *out);
+int slicer_starlet_run(slicer_starlet_handle sh, const float *d_map);
+int slicer_starlet_run_npix(slicer_starlet_handle sh, const float *d_map, int32_t npix);
+int slicer_starlet_device_map(slicer_starlet_handle sh, int32_t scale, float **d_out);
+int slicer_starlet_read(slicer_starlet_handle sh, int32_t scale, float *host);
+int slicer_starlet_destroy(slicer_starlet_handle sh);
+int slicer_l1norm_create(slicer_handle h, int32_t npix, int32_t n_edges, const double *edges, slicer_l1norm_handle *out);
+int slicer_l1norm_run(slicer_l1norm_handle lh, const float *d_map);
+int slicer_l1norm_run_npix(slicer_l1norm_handle lh, const float *d_map, int32_t npix);
+int slicer_l1norm_read(slicer_l1norm_handle lh, int64_t *counts, double *sums, int64_t *below, int64_t *above, int64_t *n_nan,
+                       double *below_sum, double *above_sum);
+int slicer_l1norm_destroy(slicer_l1norm_handle lh);
+
 /* per-kernel HIP-event timing (off by default; adds two event records per launch) */
 int slicer_profile_enable(slicer_handle h, int on);
 int slicer_profile_reset(slicer_handle h);

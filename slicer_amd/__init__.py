@@ -17,6 +17,7 @@ from .lensing import MINKOWSKI_MAX_THRESHOLDS, Minkowski, minkowski_functionals 
 from .lensing import BISPECTRUM_MAX_BINS, Bispectrum, bispectrum_triangles, bispectrum_triples  # noqa: F401
 from .lensing import SMOOTH_GAUSS, SMOOTH_MAP, SMOOTH_MAX_RADIUS, Smooth, smooth_weights  # noqa: F401
 from .lensing import Noise, noise_sigma_pix, noise_words, smooth_noise_gain  # noqa: F401
+from .lensing import STARLET_MAX_SCALES, L1Norm, Starlet, starlet_gains  # noqa: F401
 from .lensing import (RAYS_COUNT, RAYS_DEFLECTION1, RAYS_DEFLECTION2, RAYS_GAMMA1, RAYS_GAMMA2, RAYS_KAPPA,  # noqa: F401
                       RAYS_OMEGA, RAYS_STATE, Rays, plane_strengths)
 

@@ -150,6 +150,18 @@ SYMBOLS = {
     "slicer_noise_device_map": (C.c_int, [_H, C.POINTER(C.c_void_p)]),
     "slicer_noise_read": (C.c_int, [_H, C.c_void_p]),
     "slicer_noise_destroy": (C.c_int, [_H]),
+    "slicer_starlet_gains": (C.c_int, [C.c_int32, C.c_void_p, C.POINTER(C.c_double)]),
+    "slicer_starlet_create": (C.c_int, [_H, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "slicer_starlet_run": (C.c_int, [_H, C.c_void_p]),
+    "slicer_starlet_run_npix": (C.c_int, [_H, C.c_void_p, C.c_int32]),
+    "slicer_starlet_device_map": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_void_p)]),
+    "slicer_starlet_read": (C.c_int, [_H, C.c_int32, C.c_void_p]),
+    "slicer_starlet_destroy": (C.c_int, [_H]),
+    "slicer_l1norm_create": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "slicer_l1norm_run": (C.c_int, [_H, C.c_void_p]),
+    "slicer_l1norm_run_npix": (C.c_int, [_H, C.c_void_p, C.c_int32]),
+    "slicer_l1norm_read": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "slicer_l1norm_destroy": (C.c_int, [_H]),
     "slicer_rays_create": (C.c_int, [_H, C.c_int32, C.c_double, C.POINTER(C.c_void_p)]),
     "slicer_rays_reset": (C.c_int, [_H]),
     "slicer_rays_step": (C.c_int, [_H, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

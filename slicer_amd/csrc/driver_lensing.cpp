@@ -50,6 +50,17 @@
 //     in units of), and the tables .noisy_smooth_moments_ and .noisy_smooth_peaks_ (leading columns `real scale`, a
 //     '# noise_sigma' line of the per-scale NOISESIG).  Refused for physical runs, whose pixels have no angle (DESIGN.md
 //     S8 row N13).
+//   * --starlet J:lo,hi,bins: per source the starlet transform of the kappa map (the isotropic undecimated wavelet
+//     transform, B3-spline, mirrored edges) into J (1 ... 12) wavelet maps .starlet<j>_kappa_z..., j = 1 ... J, and the
+//     coarse map .starlet0_kappa_z..., with the kappa file's header and the keys SCALE (j) and GAIN (the rms of that
+//     map for white noise of unit variance a pixel, 17 digits).  Two tables of the scales j = 1 ... J over `bins`
+//     (1 ... 1024) uniform bins from lo to hi: .starlet_peaks_, the histogram and the peak and minimum counts of --peaks
+//     per scale, and .starlet_l1_, per bin the pixel count and the sum of |w_j| (the starlet l1-norm); rows -1, bins,
+//     bins + 1 as in the --peaks table.  Without --shape-noise lo and hi are in units of kappa and all scales share the
+//     edges; with it they are signal-to-noise: scale j has the edges e_b sigma_j, sigma_j = sigma_pix GAIN_j (a
+//     '# sigma_scale' line), and per realisation r the same maps of the noisy map, .noisy<r>_starlet<j>_kappa_z...
+//     with the keys of the noisy file first, and the tables .noisy_starlet_peaks_ and .noisy_starlet_l1_ (a leading
+//     column `real`).  Refused for physical runs.
 #include "driver_lensing.hpp"
 
 #include <algorithm>
@@ -214,6 +225,20 @@ int LensingOptions::parse(int argc, char **argv, int &i)
         noise_seed = seed;
         noise_nreal = (int)nreal;
         shape_noise = true;
+    } else if (a == "--starlet") {
+        const string v = has_value ? argv[++i] : "";
+        const size_t colon = v.find(':');
+        const string scales = v.substr(0, colon);
+        char *end = nullptr;
+        const long J = strtol(scales.c_str(), &end, 10);
+        if (colon == string::npos || scales.empty() || isspace((unsigned char)scales[0]) || *end != '\0' || J < 1 ||
+            J > SLICER_STARLET_MAX_SCALES)
+            return bad("bad --starlet (J:lo,hi,bins: the number of scales, 1 ... " + std::to_string(SLICER_STARLET_MAX_SCALES) +
+                       ", then the first and the last edge and the number of bins)");
+        starlet_edges.clear();
+        if (const int rc = uniform_edges(a, v.c_str() + colon + 1, "after J: the first and the last edge", starlet_edges))
+            return rc;
+        starlet_scales = (int)J;
     } else
         return -1;
     return 0;
@@ -243,6 +268,7 @@ int LensingOptions::check() const
          "--minkowski needs --kappa (the Minkowski functionals are those of the kappa maps)"},
         {!smooth_kind.empty() && no_kappa, "--smooth needs --kappa (the smoothed maps are those of the kappa maps)"},
         {shape_noise && no_kappa, "--shape-noise needs --kappa (the noise is added to the kappa maps)"},
+        {starlet_scales > 0 && no_kappa, "--starlet needs --kappa (the transform is that of the kappa maps)"},
     };
     for (const auto &[broken, message] : rules)
         if (broken)
@@ -292,6 +318,8 @@ int LensingOptions::check_npix(const InputParams &p) const
             return bad("--smooth: scale " + std::to_string(k) + " for " + npix + ": " + slicer_last_error(nullptr));
     if (shape_noise && p.physical)
         return bad("--shape-noise: the galaxy density is per angle, and the pixels of a physical run have none");
+    if (starlet_scales > 0 && p.physical)
+        return bad("--starlet: the scales are read as angles, and the maps of a physical run have none");
     double sigma_pix = 0.0;
     if (shape_noise && slicer_noise_sigma_pix(noise_sigma_e, noise_ngal, p.fov, p.npix, &sigma_pix) != SLICER_OK)
         return bad("--shape-noise: " + npix + ": " + slicer_last_error(nullptr));
@@ -394,6 +422,25 @@ int LensingOutputs::create()
         }
         for (double z : zs)  // (sources at one redshift share their stream, and with it their noise)
             noise_stream.push_back((uint32_t)std::count_if(zs.begin(), zs.end(), [z](double other) { return other < z; }));
+    }
+    if (o.starlet_scales > 0) {
+        const int J = o.starlet_scales;
+        starlet_gain.resize(J + 1);
+        if (slicer_starlet_gains(J, &starlet_gain[1], &starlet_gain[0]) != SLICER_OK ||
+            slicer_starlet_create(h, p.npix, J, sth.out()) != SLICER_OK)
+            return fail(h, "slicer_amd: --starlet");
+        for (int j = 1; j <= (o.shape_noise ? J : 1); j++) {
+            vector<double> e = o.starlet_edges;
+            if (o.shape_noise) {
+                starlet_sigma.push_back(noise_sigma_pix * starlet_gain[j]);
+                for (double &v : e)
+                    v = v * starlet_sigma.back();
+            }
+            if (slicer_peaks_create(h, p.npix, (int)e.size(), e.data(), starlet_pkh.emplace_back().out()) != SLICER_OK ||
+                slicer_l1norm_create(h, p.npix, (int)e.size(), e.data(), starlet_l1h.emplace_back().out()) != SLICER_OK)
+                return fail(h, "slicer_amd: --starlet");
+            starlet_scale_edges.push_back(e);
+        }
     }
     if (!o.raytrace)
         return 0;
@@ -529,6 +576,8 @@ int LensingOutputs::write()
             return rc;
         if (const int rc = nh ? source_noise(s, d_kappa) : 0)
             return rc;
+        if (const int rc = sth ? source_starlet(s, d_kappa, false, ".", {}, "", "") : 0)
+            return rc;
     }
     if (const int rc = ph ? power_spectra() : 0)
         return rc;
@@ -551,6 +600,82 @@ int LensingOutputs::write()
                     write_table((string(statistic[t][0]) + kind[k][0]).c_str(), (string(kind[k][1]) + statistic[t][1]).c_str(),
                                 tables[t][k]))
                     return 1;
+    static const char *const starlet_table[2][2] = {{"starlet histograms and peak counts", "starlet_peaks_"},
+                                                    {"starlet l1-norms", "starlet_l1_"}};
+    for (int noisy = 0; noisy < (sth ? (nh ? 2 : 1) : 0); noisy++)
+        for (int t = 0; t < 2; t++)
+            if (write_table((string(starlet_table[t][0]) + kind[noisy ? NOISY : KAPPA][0]).c_str(),
+                            (string(kind[noisy ? NOISY : KAPPA][1]) + starlet_table[t][1]).c_str(), starlet_tables[t][noisy]))
+                return 1;
+    return 0;
+}
+
+// --starlet: the J + 1 maps of the map at d_map, and per scale j = 1 ... J the rows of the two tables.  Both tables: '#'
+// lines (npix, angle, scales, the edges as given, the gains of w_1 ... w_J, with --shape-noise its lines and sigma_scale,
+// the column names), then per (source, scale) one row per bin: -1 (below the first edge), 0 ... B-1, B (above the last),
+// B+1 (NaN pixels); edge_lo and edge_hi are the scale's own edges.
+int LensingOutputs::source_starlet(size_t s, const float *d_map, bool noisy, const string &prefix, const vector<FitsKey> &keys,
+                                   const string &lead_names, const string &lead)
+{
+    const char *who = "slicer_amd: --starlet";
+    const int J = o.starlet_scales, B = (int)o.starlet_edges.size() - 1;
+    string &pk = starlet_tables[0][noisy], &l1 = starlet_tables[1][noisy];
+    if (pk.empty()) {
+        string head;
+        add(head, "# npix %d\n# angle_deg %.17g\n# scales %d\n# edges", p.npix, p.fov, J);
+        for (double v : o.starlet_edges)
+            add(head, " %.17g", v);
+        add(head, "\n# gain");
+        for (int j = 1; j <= J; j++)
+            add(head, " %.17g", starlet_gain[j]);
+        head += "\n";
+        if (nh) {
+            head += noise_head() + "# sigma_scale";
+            for (double v : starlet_sigma)
+                add(head, " %.17g", v);
+            head += "\n";
+        }
+        pk = head + "# " + lead_names + "z scale bin edge_lo edge_hi n_pixels n_peaks n_minima\n";
+        l1 = head + "# " + lead_names + "z scale bin edge_lo edge_hi count l1\n";
+    }
+    if (slicer_starlet_run(sth, d_map) != SLICER_OK)
+        return fail(h, who);
+    vector<int64_t> c(3 * B + 7), n(B + 3);  // peaks: pdf, peaks, minima [B], below, above [3], nan; l1: counts [B], below, above, nan
+    vector<double> sum(B + 2);               // ... the sums [B], below, above
+    for (int j = 0; j <= J; j++) {
+        float *d_w = nullptr;
+        if (slicer_starlet_read(sth, j, map.data()) != SLICER_OK || slicer_starlet_device_map(sth, j, &d_w) != SLICER_OK)
+            return fail(h, who);
+        char gain[32];
+        snprintf(gain, sizeof gain, "%.17g", starlet_gain[j]);
+        vector<FitsKey> more = keys;
+        more.push_back({"SCALE", true, j, 0.0, " "});
+        more.push_back({"GAIN", false, 0, starlet_gain[j], " ", gain});
+        if (!save(noisy ? "noisy starlet" : "starlet", prefix + "starlet" + std::to_string(j) + "_kappa_z", s, more))
+            return fail(h, who);
+        if (j == 0)
+            continue;
+        const size_t set = std::min<size_t>(j - 1, starlet_scale_edges.size() - 1);
+        const vector<double> &e = starlet_scale_edges[set];
+        if (slicer_peaks_run(starlet_pkh[set], d_w) != SLICER_OK ||
+            slicer_peaks_read(starlet_pkh[set], &c[0], &c[B], &c[2 * B], &c[3 * B], &c[3 * B + 3], &c[3 * B + 6]) != SLICER_OK ||
+            slicer_l1norm_run(starlet_l1h[set], d_w) != SLICER_OK ||
+            slicer_l1norm_read(starlet_l1h[set], &n[0], &sum[0], &n[B], &n[B + 1], &n[B + 2], &sum[B], &sum[B + 1]) != SLICER_OK)
+            return fail(h, who);
+        const auto row = [&](int bin, double lo, double hi, int64_t n_pixels, int64_t n_peaks, int64_t n_minima, int64_t count,
+                             double total) {
+            pk += lead;
+            add(pk, "%.17g %d %d %.17g %.17g %lld %lld %lld\n", plan.zs[s], j, bin, lo, hi, (long long)n_pixels,
+                (long long)n_peaks, (long long)n_minima);
+            l1 += lead;
+            add(l1, "%.17g %d %d %.17g %.17g %lld %.17g\n", plan.zs[s], j, bin, lo, hi, (long long)count, total);
+        };
+        row(-1, -INFINITY, e[0], c[3 * B], c[3 * B + 1], c[3 * B + 2], n[B], sum[B]);
+        for (int b = 0; b < B; b++)
+            row(b, e[b], e[b + 1], c[b], c[B + b], c[2 * B + b], n[b], sum[b]);
+        row(B, e[B], INFINITY, c[3 * B + 3], c[3 * B + 4], c[3 * B + 5], n[B + 1], sum[B + 1]);
+        row(B + 1, NAN, NAN, c[3 * B + 6], 0, 0, n[B + 2], 0.0);
+    }
     return 0;
 }
 
@@ -621,6 +746,8 @@ int LensingOutputs::source_noise(size_t s, const float *d_kappa)
             if (const int rc = map_statistics(s, d_smooth, NOISY_SMOOTH, smoothed_head, "real scale ", lead))
                 return rc;
         }
+        if (const int rc = sth ? source_starlet(s, d_noisy, true, ".noisy" + real + "_", keys, "real ", real + " ") : 0)
+            return rc;
     }
     return 0;
 }

@@ -1,6 +1,6 @@
 // driver_lensing.hpp -- the lensing outputs of the SLICER_amd driver (slicer_main.cpp): their options, their host
 // planning and the device-0 work behind --kappa, --shear, --deflection, --raytrace, --power, --moments, --peaks,
-// --minkowski, --bispectrum, --smooth and --shape-noise (driver_lensing.cpp describes the options), with the small helpers the rest of the driver shares with them.
+// --minkowski, --bispectrum, --smooth, --shape-noise and --starlet (driver_lensing.cpp describes the options), with the small helpers the rest of the driver shares with them.
 #pragma once
 #include <deque>
 #include <string>
@@ -32,6 +32,8 @@ struct LensingOptions {
     double noise_sigma_e = 0.0, noise_ngal = 0.0;  // per component; per arcmin^2
     uint64_t noise_seed = 0;
     int noise_nreal = 1;
+    int starlet_scales = 0;              // --starlet J:lo,hi,bins: J, 0 without it
+    std::vector<double> starlet_edges;   // ... the bins + 1 uniform edges from lo to hi
 
     bool gradient() const { return shear_derivative == "gradient"; }
     int n_power_edges(int npix) const { return power_edges.empty() ? npix : (int)power_edges.size(); }
@@ -113,6 +115,16 @@ struct LensingOutputs {
     double noise_sigma_pix = 0.0;
     std::vector<double> noise_gain{};
     std::vector<uint32_t> noise_stream{};
+    // --starlet: one transform handle for all sources; the gains [J + 1] (the coarse map's, then w_1 ... w_J); the edges
+    // of the tables with a peaks and an l1norm handle on them: one set in kappa units, or with --shape-noise one per
+    // scale j = 1 ... J in units of sigma_j = noise_sigma_pix * gain_j.  The tables: peaks and l1, of the kappa and of
+    // the noisy maps
+    Owned<slicer_starlet_handle, slicer_starlet_destroy> sth{};
+    std::vector<double> starlet_gain{}, starlet_sigma{};
+    std::vector<std::vector<double>> starlet_scale_edges{};
+    std::deque<Owned<slicer_peaks_handle, slicer_peaks_destroy>> starlet_pkh{};
+    std::deque<Owned<slicer_l1norm_handle, slicer_l1norm_destroy>> starlet_l1h{};
+    std::string starlet_tables[2][2]{};
     // --raytrace: a one-source kappa handle that makes a plane's lens map, the rays, their six output buffers, and the
     // sources in ascending redshift with the position of the next one to observe
     Owned<slicer_kappa_handle, slicer_kappa_destroy> lkh{};
@@ -164,6 +176,10 @@ private:
     std::string noise_head() const;
     int source_smooth(size_t s, const float *d_kappa);
     int source_noise(size_t s, const float *d_kappa);
+    // --starlet of the map at d_map of source s: the files <prefix>starlet<j>_kappa_z with `keys`, SCALE and GAIN, and
+    // its rows of the two tables of the noisy (or not) maps; `lead_names` and `lead` as above
+    int source_starlet(size_t s, const float *d_map, bool noisy, const std::string &prefix, const std::vector<FitsKey> &keys,
+                       const std::string &lead_names, const std::string &lead);
     int source_shear(size_t s, const float *d_kappa);
     int power_spectra();
     int bispectra();

@@ -31,7 +31,7 @@ std::string fits_card(const FitsKey &k)
     std::string name = k.name;
     for (auto &c : name)
         c = (char)toupper((unsigned char)c);
-    const std::string val = k.is_int ? std::to_string(k.ival) : fmt_double(k.dval);
+    const std::string val = !k.text.empty() ? k.text : k.is_int ? std::to_string(k.ival) : fmt_double(k.dval);
     std::string head;
     if (name.size() <= 8) {
         head = name;

@@ -22,6 +22,7 @@ struct FitsKey {
     long ival;
     double dval;
     std::string comment;
+    std::string text = {};  // not empty: the value as it is written, instead of ival / dval (a number with more digits than the 15 of dval)
 };
 std::string fits_card(const FitsKey &k);
 // returns false if the file exists or cannot be written

@@ -4,7 +4,8 @@ maps and finite-difference derivatives of the potential (row N8), and the centra
 of 2x2 halvings (row N9), and the one-point PDF histogram and peak / minimum counts of such maps (row N10), and
 multi-plane ray tracing through the lens planes (row N11), and Gaussian and aperture-mass smoothing of such maps (row N12),
 and shape noise for such maps from a counter-based generator (row N13), and the Minkowski functionals of such maps'
-excursion sets as exact counts (row N14), and the binned bispectra of such maps (row N15).
+excursion sets as exact counts (row N14), and the binned bispectra of such maps (row N15), and the starlet transform of
+such maps with the binned absolute sums of its scales, the starlet l1-norm (row N16).
 
 plane_weights wraps the host weights of include/slicer_amd.h (slicer_lensing_weights); Kappa is the device accumulator
 (slicer_kappa_*) bound to a Slicer handle: it reads the finalized plane maps where they are, in HBM.  Shear (slicer_shear_*)
@@ -17,7 +18,9 @@ the planes' deflection, convergence and shear maps (plane_strengths scales a mas
 (slicer_smooth_*) filters a map with a truncated Gaussian or with the aperture-mass filter built from it; Noise
 (slicer_noise_*) adds Gaussian noise that is a pure function of (seed, stream, realisation, pixel) to a map;
 Minkowski (slicer_minkowski_*) counts the faces, edges and vertices of the pixel complex that lie in the sets x >= t_j;
-Bispectrum (slicer_bispectrum_*) contracts the band-filtered f64 maps of a map over a list of bin triples.
+Bispectrum (slicer_bispectrum_*) contracts the band-filtered f64 maps of a map over a list of bin triples; Starlet
+(slicer_starlet_*) splits a map into wavelet scales that sum back to it, and L1Norm (slicer_l1norm_*) sums |x| of a map's
+pixels bin by bin over Peaks' edges.
 """
 import ctypes as C
 import math
@@ -793,6 +796,109 @@ class Noise(_SubHandle):
         out = np.empty(self.last_shape or (1,), np.float32)
         self._s._chk(_L.slicer_noise_read(self._nh, out.ctypes.data))
         return out
+
+
+STARLET_MAX_SCALES = 12
+
+
+def starlet_gains(scales):
+    """(gain_w [scales], gain_coarse) as slicer_starlet_gains makes them: the rms of w_1 ... w_scales and of the coarse
+    map of Starlet for white noise of unit variance, at a pixel farther than the reach from every edge; host only, no
+    device needed."""
+    scales = int(scales)
+    g = np.zeros(max(scales, 0), np.float64)
+    coarse = C.c_double()
+    _host_chk(_L.slicer_starlet_gains(scales, g.ctypes.data, C.byref(coarse)))
+    return g, coarse.value
+
+
+class Starlet(_SubHandle):
+    """The starlet transform (isotropic undecimated wavelet transform, B3-spline a trous, mirrored edges) of an npix^2
+    map into `scales` wavelet maps w_1 ... w_J and one coarse map that sum back to it, on the device of `slicer`, on its
+    stream.  Scale j reaches 2 * 2^j pixels; scale 0 names the coarse map."""
+    _handle, _destroy = "_sh", "slicer_starlet_destroy"
+
+    def __init__(self, slicer: Slicer, npix, scales):
+        self._s = slicer
+        self.npix, self.scales = int(npix), int(scales)
+        self.last_npix = None  # of the last run
+        sh = C.c_void_p()
+        slicer._chk(_L.slicer_starlet_create(slicer._h, self.npix, self.scales, C.byref(sh)))
+        self._sh = sh
+
+    def run(self, d_map, npix=None):
+        """d_map: device address of an f32 map of npix^2 pixels (None: the handle's npix; otherwise at most that)."""
+        d = None if d_map is None else int(d_map)
+        if npix is None:
+            self._s._chk(_L.slicer_starlet_run(self._sh, d))
+        else:
+            self._s._chk(_L.slicer_starlet_run_npix(self._sh, d, int(npix)))
+        self.last_npix = self.npix if npix is None else int(npix)
+
+    def run_kappa(self, kappa: Kappa, s):
+        """The map of source s of a Kappa accumulator, where it is."""
+        self.run(kappa.device_map(s), kappa.npix)
+
+    def run_level(self, moments: Moments, level):
+        """Level `level` >= 1 of the last run of a Moments pyramid, where it is (level 0 is the caller's own map)."""
+        self.run(moments.device_map(level), moments.npix >> int(level))
+
+    def device_map(self, scale):
+        """Device address of w_scale (1 ... scales) or of the coarse map (0) of the last run, f32 [n, n] for its n."""
+        p = C.c_void_p()
+        self._s._chk(_L.slicer_starlet_device_map(self._sh, int(scale), C.byref(p)))
+        return p.value
+
+    def read(self, scale):
+        """w_scale (1 ... scales) or the coarse map (0) of the last run, f32 [n, n] for its n; waits for the stream."""
+        n = self.last_npix or 1
+        out = np.empty((n, n), np.float32)
+        self._s._chk(_L.slicer_starlet_read(self._sh, int(scale), out.ctypes.data))
+        return out
+
+    def read_all(self):
+        """[coarse, w_1, ..., w_scales] of the last run: read(0) ... read(scales)."""
+        return [self.read(j) for j in range(self.scales + 1)]
+
+
+class L1Norm(_SubHandle):
+    """Per bin of the f64 `edges` (Peaks' rule: the last bin closed) the exact int64 count of an npix^2 map's pixels
+    and the f64 sum of their |x|, on the device of `slicer`, on its stream: on the scales of a
+    Starlet, the starlet l1-norm."""
+    _handle, _destroy = "_lh", "slicer_l1norm_destroy"
+
+    def __init__(self, slicer: Slicer, npix, edges):
+        self._s = slicer
+        self.npix = int(npix)
+        self.edges = np.array(edges, np.float64).ravel()
+        self.n_bins = self.edges.size - 1
+        lh = C.c_void_p()
+        slicer._chk(_L.slicer_l1norm_create(slicer._h, self.npix, self.edges.size, _dptr(self.edges), C.byref(lh)))
+        self._lh = lh
+
+    def run(self, d_map, npix=None):
+        """d_map: device address of an f32 map of npix^2 pixels (None: the handle's npix; otherwise at most that)."""
+        d = None if d_map is None else int(d_map)
+        if npix is None:
+            self._s._chk(_L.slicer_l1norm_run(self._lh, d))
+        else:
+            self._s._chk(_L.slicer_l1norm_run_npix(self._lh, d, int(npix)))
+
+    def run_scale(self, starlet: Starlet, scale):
+        """Scale `scale` of the last run of a Starlet, where it is."""
+        self.run(starlet.device_map(scale), starlet.last_npix)
+
+    def read(self):
+        """dict: edges [B+1], counts (int64 [B]), l1 (f64 [B]: the sums of |x|), below, above, nan (int) and below_l1,
+        above_l1 (float)."""
+        B = max(self.n_bins, 0)
+        counts, l1 = np.empty(B, np.int64), np.empty(B, np.float64)
+        below, above, nan = (np.empty(1, np.int64) for _ in range(3))
+        below_l1, above_l1 = np.empty(1, np.float64), np.empty(1, np.float64)
+        self._s._chk(_L.slicer_l1norm_read(self._lh, counts.ctypes.data, l1.ctypes.data, below.ctypes.data,
+                                           above.ctypes.data, nan.ctypes.data, below_l1.ctypes.data, above_l1.ctypes.data))
+        return {"edges": self.edges.copy(), "counts": counts, "l1": l1, "below": int(below[0]), "above": int(above[0]),
+                "nan": int(nan[0]), "below_l1": float(below_l1[0]), "above_l1": float(above_l1[0])}
 
 
 RAYS_KAPPA, RAYS_GAMMA1, RAYS_GAMMA2, RAYS_OMEGA, RAYS_DEFLECTION1, RAYS_DEFLECTION2 = range(6)
