@@ -872,6 +872,62 @@ int slicer_l1norm_read(slicer_l1norm_handle lh, int64_t *counts, double *sums, i
                        double *below_sum, double *above_sum);
 int slicer_l1norm_destroy(slicer_l1norm_handle lh);
 
+/* ---- Masked pseudo-C_l: coupled bandpowers, mode-coupling matrix, decoupling ----
+ * Notation of the power spectra above (row N7): n = npix, theta, the [n][n/2+1] half plane, the integer m2, the edges
+ * r_0 < ... < r_B in units of l_f and their bins (the last one closed on the right).  H_b: the half-plane coefficients
+ * in bin b, each one mode, N_b = |H_b|.  F_b: the FULL-plane modes (both signs of both indices) whose m2 lies in bin b,
+ * m2 = 0 included when the bin holds it.  One mask w (f32, n^2 pixels, finite values) is shared by all maps:
+ *   masked map          w * kappa_s, the f32 product (one rounding), taken as the transform loads the map;
+ *                       khat_s = rfft2(w * kappa_s) in f64: bitwise slicer_shear_spectrum of the multiplied map under the
+ *                       same shear_split
+ *   coupled bandpowers  Ct_st,b = theta^2 / n^4 * (1 / N_b) * sum over H_b of Re(khat_s conj khat_t): bitwise what
+ *                       slicer_power_read gives for the multiplied maps
+ *   coupling matrix     M[b][b'] = 1 / (N_b n^4) * sum over k in H_b, k' in F_b' of |what(k - k')|^2, what = fft2(w)
+ *                       unnormalised; w = c everywhere gives M = c^2 I.  Computed as: A = irfft2(|rfft2 w|^2), the circular
+ *                       autocorrelation of the mask, in f64; per b', G = irfft2 of the indicator of F_b' in f64,
+ *                       Q = Re rfft2(A G) / n^2 and M[b][b'] = (1 / N_b) * the sum of Q over H_b, summed in the order of
+ *                       slicer_power_run.  Rows and columns of empty bins (N_b = 0) are 0.
+ *   decoupled           Ch_st = M_act^-1 Ct_st on the active bins, those with N_b > 0; NaN in the others.  An f64 LU with
+ *                       partial pivoting on the host, factorised once per mask; two substitutions per pair in
+ *                       slicer_pcl_read.  Modes outside all edges are dropped as in N7: power that the mask couples to or
+ *                       from them is not modelled, so the edges should span the modes that carry power.
+ *   mask moments        mean(w) and mean(w^2) in f64; fixed summation order, no floating-point atomics
+ *   border taper        (NaMaster's C1 apodisation, separable) on an axis x_i = min(i, n-1-i) + 0.5, t = x_i / width_pix,
+ *                       f_i = 1 if t >= 1, else t - sin(2 pi t) / (2 pi); w = (float)(f[i0] * f[i1]), the product in f64;
+ *                       with a user mask as well, that value times the user mask in f32
+ * Out of scope: spin-2 fields and E/B, purification, contaminant deprojection, bandpower window functions, a different
+ * mask per map, noise-bias subtraction, the curved sky.
+ *   slicer_pcl_taper     host only: f [npix] in f64.  npix < 2, or a width that is not positive and finite: SLICER_ERR_ARG
+ *   slicer_pcl_create    arguments and refusals as slicer_power_create, except that the edges are required (NULL:
+ *                        SLICER_ERR_ARG) and more than SLICER_PCL_MAX_BINS bins are SLICER_ERR_UNSUPPORTED.  Device memory
+ *                        beyond slicer_power_create's: A, G and one spectrum in f64 and w, 3 * 8 npix^2 + 4 npix^2 bytes
+ *                        (the spectrum 16 npix (npix/2+1)), and the taper table (SLICER_ERR_NOMEM)
+ *   slicer_pcl_set_mask  d_mask: a device f32 npix^2 map or NULL (the taper alone); taper_width_pix: 0 for the mask alone.
+ *                        Both absent, or a width that is negative or not finite: SLICER_ERR_ARG.  Builds w, the moments, A,
+ *                        M and the LU, and waits for the stream.  A mask with a value that is not finite, or whose active M
+ *                        has a zero or non-finite pivot (an all-zero mask is one; "coupling matrix singular"):
+ *                        SLICER_ERR_ARG.  A new mask replaces the old one and invalidates the last run; after a refused
+ *                        one the handle has no mask.
+ *   slicer_pcl_read_mask w, npix^2 f32; slicer_pcl_coupling: M [B][B] row-major, mean(w), mean(w^2) (any of them NULL).
+ *                        Before a mask: SLICER_ERR_STATE
+ *   slicer_pcl_run       n_maps device f32 maps; enqueued, no synchronisation.  Before a mask: SLICER_ERR_STATE
+ *   slicer_pcl_spectrum  khat of map `map` of the last run, as slicer_power_spectrum
+ *   slicer_pcl_read      cl (decoupled) and coupled [pairs][B] in the pair order of slicer_power_create, ell_mean and counts
+ *                        [B] (any of them NULL); waits for the stream.  Before a run: SLICER_ERR_STATE
+ * No atomics: the same mask and maps give bitwise the same M and bandpowers. */
+typedef struct slicer_pcl_s *slicer_pcl_handle;
+#define SLICER_PCL_MAX_BINS 512
+int slicer_pcl_taper(int32_t npix, double width_pix, double *f);
+int slicer_pcl_create(slicer_handle h, int32_t npix, double angle_deg, int32_t n_maps, int32_t cross, int32_t n_edges,
+                      const double *edges, slicer_pcl_handle *out);
+int slicer_pcl_set_mask(slicer_pcl_handle ph, const float *d_mask, double taper_width_pix);
+int slicer_pcl_read_mask(slicer_pcl_handle ph, float *host);
+int slicer_pcl_coupling(slicer_pcl_handle ph, double *M, double *mean_w, double *mean_w2);
+int slicer_pcl_run(slicer_pcl_handle ph, const float *const *d_maps);
+int slicer_pcl_spectrum(slicer_pcl_handle ph, int32_t map, double *host);
+int slicer_pcl_read(slicer_pcl_handle ph, double *cl, double *coupled, double *ell_mean, int64_t *counts);
+int slicer_pcl_destroy(slicer_pcl_handle ph);
+
 /* per-kernel HIP-event timing (off by default; adds two event records per launch) */
 int slicer_profile_enable(slicer_handle h, int on);
 int slicer_profile_reset(slicer_handle h);

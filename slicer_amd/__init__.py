@@ -18,6 +18,7 @@ from .lensing import BISPECTRUM_MAX_BINS, Bispectrum, bispectrum_triangles, bisp
 from .lensing import SMOOTH_GAUSS, SMOOTH_MAP, SMOOTH_MAX_RADIUS, Smooth, smooth_weights  # noqa: F401
 from .lensing import Noise, noise_sigma_pix, noise_words, smooth_noise_gain  # noqa: F401
 from .lensing import STARLET_MAX_SCALES, L1Norm, Starlet, starlet_gains  # noqa: F401
+from .lensing import PCL_MAX_BINS, Pcl, pcl_taper  # noqa: F401
 from .lensing import (RAYS_COUNT, RAYS_DEFLECTION1, RAYS_DEFLECTION2, RAYS_GAMMA1, RAYS_GAMMA2, RAYS_KAPPA,  # noqa: F401
                       RAYS_OMEGA, RAYS_STATE, Rays, plane_strengths)
 

@@ -162,6 +162,16 @@ SYMBOLS = {
     "slicer_l1norm_run_npix": (C.c_int, [_H, C.c_void_p, C.c_int32]),
     "slicer_l1norm_read": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "slicer_l1norm_destroy": (C.c_int, [_H]),
+    "slicer_pcl_taper": (C.c_int, [C.c_int32, C.c_double, C.c_void_p]),
+    "slicer_pcl_create": (C.c_int, [_H, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                    C.POINTER(C.c_void_p)]),
+    "slicer_pcl_set_mask": (C.c_int, [_H, C.c_void_p, C.c_double]),
+    "slicer_pcl_read_mask": (C.c_int, [_H, C.c_void_p]),
+    "slicer_pcl_coupling": (C.c_int, [_H, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "slicer_pcl_run": (C.c_int, [_H, C.POINTER(C.c_void_p)]),
+    "slicer_pcl_spectrum": (C.c_int, [_H, C.c_int32, C.c_void_p]),
+    "slicer_pcl_read": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "slicer_pcl_destroy": (C.c_int, [_H]),
     "slicer_rays_create": (C.c_int, [_H, C.c_int32, C.c_double, C.POINTER(C.c_void_p)]),
     "slicer_rays_reset": (C.c_int, [_H]),
     "slicer_rays_step": (C.c_int, [_H, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

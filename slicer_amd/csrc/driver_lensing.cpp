@@ -16,6 +16,12 @@
 //   * --power auto|cross: <directory><simulation>.cl_<npix>_<suffix>.txt, the binned auto (or auto and cross) power
 //     spectra C_l of the kappa maps (Lens/smr.py's PS without its defects); --power-edges r0,r1,...
 //     sets the bin edges in units of l_f = 2 pi / ANGLE (default 0, 1, ..., npix-1).
+//   * --pcl auto|cross with --pcl-edges r0,r1,... (required; at most 513 edges in the units of --power-edges) and at
+//     least one of --pcl-taper ARCMIN (a border taper of that width, ARCMIN npix / (60 ANGLE) pixels) and --pcl-mask
+//     FILE.fits (an image of the maps' size, BITPIX -32 or -64): <directory><simulation>.pcl_<npix>_<suffix>.txt, the
+//     masked pseudo-C_l of the kappa maps, the layout of the .cl_ file with '#' lines for the mask (mean_w, mean_w2,
+//     taper_arcmin, taper_pix, mask) and per pair the decoupled bandpower C_s_t followed by the coupled one Ct_s_t; and
+//     .pclm_<npix>_<suffix>.txt, the mode-coupling matrix M, one row per line.
 //   * --moments: <directory><simulation>.moments_<npix>_<suffix>.txt, the raw central power sums S_2 ... S_8 and the
 //     mean of every kappa map and of --moments-levels L (default 0) successive 2x2 block means of it, about each level's
 //     own mean (Lens/moment.py and Lens/halve.py).
@@ -166,7 +172,19 @@ int LensingOptions::parse(int argc, char **argv, int &i)
     else if (a == "--power-edges" && has_value) {
         if (!parse_doubles(argv[++i], power_edges))
             return bad("bad --power-edges (a comma-separated list of radii in units of l_f)");
-    } else if (a == "--bispectrum" && has_value) bispectrum = argv[++i];
+    } else if (a == "--pcl" && has_value) pcl = argv[++i];
+    else if (a == "--pcl-edges" && has_value) {
+        if (!parse_doubles(argv[++i], pcl_edges))
+            return bad("bad --pcl-edges (a comma-separated list of radii in units of l_f)");
+        if (pcl_edges.size() > SLICER_PCL_MAX_BINS + 1)
+            return bad("bad --pcl-edges (" + std::to_string(pcl_edges.size()) + " edges, at most " +
+                       std::to_string(SLICER_PCL_MAX_BINS + 1) + ")");
+    } else if (a == "--pcl-taper" && has_value) {
+        if (!whole_double(argv[++i], &pcl_taper_arcmin) || !std::isfinite(pcl_taper_arcmin) || !(pcl_taper_arcmin > 0))
+            return bad("bad --pcl-taper (the width of the border taper in arcminutes, positive)");
+        pcl_taper_given = true;
+    } else if (a == "--pcl-mask" && has_value) pcl_mask = argv[++i];
+    else if (a == "--bispectrum" && has_value) bispectrum = argv[++i];
     else if (a == "--bispectrum-edges" && has_value) {
         if (!parse_doubles(argv[++i], bispectrum_edges))
             return bad("bad --bispectrum-edges (a comma-separated list of radii in units of l_f)");
@@ -247,7 +265,7 @@ int LensingOptions::parse(int argc, char **argv, int &i)
 int LensingOptions::check() const
 {
     const bool no_kappa = kappa.empty(), derivative = !shear_derivative.empty(), pw = !power.empty();
-    const bool bs = !bispectrum.empty();
+    const bool bs = !bispectrum.empty(), pc = !pcl.empty();
     const std::pair<bool, const char *> rules[] = {
         {shear && no_kappa, "--shear needs --kappa (the shear maps are computed from the kappa maps)"},
         {raytrace && no_kappa, "--raytrace needs --kappa (the rays are observed at the source redshifts of the kappa maps)"},
@@ -257,6 +275,13 @@ int LensingOptions::check() const
         {pw && power != "auto" && power != "cross", "bad --power (auto or cross)"},
         {pw && no_kappa, "--power needs --kappa (the power spectra are those of the kappa maps)"},
         {!power_edges.empty() && !pw, "--power-edges needs --power"},
+        {pc && pcl != "auto" && pcl != "cross", "bad --pcl (auto or cross)"},
+        {pc && no_kappa, "--pcl needs --kappa (the pseudo-spectra are those of the kappa maps)"},
+        {!pcl_edges.empty() && !pc, "--pcl-edges needs --pcl"},
+        {pcl_taper_given && !pc, "--pcl-taper needs --pcl"},
+        {!pcl_mask.empty() && !pc, "--pcl-mask needs --pcl"},
+        {pc && pcl_edges.empty(), "--pcl needs --pcl-edges (the bin edges in units of l_f)"},
+        {pc && !pcl_taper_given && pcl_mask.empty(), "--pcl needs --pcl-taper or --pcl-mask (or both)"},
         {bs && bispectrum != "all" && bispectrum != "equilateral", "bad --bispectrum (all or equilateral)"},
         {bs && no_kappa, "--bispectrum needs --kappa (the bispectra are those of the kappa maps)"},
         {!bispectrum_edges.empty() && !bs, "--bispectrum-edges needs --bispectrum"},
@@ -294,6 +319,23 @@ int LensingOptions::check_npix(const InputParams &p) const
         vector<double> mr(cnt.size());
         if (slicer_power_bins(p.npix, ne, power_edges_or_null(), cnt.data(), mr.data()) != SLICER_OK)
             return bad(string("--power-edges: ") + slicer_last_error(nullptr));
+    }
+    if (!pcl.empty() && !slicer_shear_supported(p.npix))
+        return bad("--pcl: " + npix + fft_sizes);
+    if (!pcl.empty()) {  // the edges, the taper, the mask file
+        vector<int64_t> cnt(std::max<size_t>(pcl_edges.size(), 2) - 1);
+        vector<double> mr(cnt.size());
+        if (slicer_power_bins(p.npix, (int)pcl_edges.size(), pcl_edges.data(), cnt.data(), mr.data()) != SLICER_OK)
+            return bad(string("--pcl-edges: ") + slicer_last_error(nullptr));
+        if (pcl_taper_given && p.physical)
+            return bad("--pcl-taper: the width is an angle, and the maps of a physical run have none");
+        vector<double> f(p.npix);
+        if (pcl_taper_given && slicer_pcl_taper(p.npix, pcl_taper_pix(p.npix, p.fov), f.data()) != SLICER_OK)
+            return bad("--pcl-taper: " + npix + ": " + slicer_last_error(nullptr));
+        vector<float> w((size_t)p.npix * (size_t)p.npix);
+        const string why = pcl_mask.empty() ? "" : fits_read_mask(pcl_mask, p.npix, w.data());
+        if (!why.empty())
+            return bad("--pcl-mask: " + why);
     }
     if (!bispectrum.empty() && !slicer_shear_supported(p.npix))
         return bad("--bispectrum: " + npix + fft_sizes);
@@ -382,6 +424,13 @@ int LensingOutputs::create()
     if (!o.power.empty() && slicer_power_create(h, p.npix, p.fov, (int)zs.size(), o.power == "cross", o.n_power_edges(p.npix),
                                                 o.power_edges_or_null(), ph.out()) != SLICER_OK)
         return fail(h, "slicer_amd: --power");
+    if (!o.pcl.empty() && zs.size() > 128) {
+        cerr << "slicer_amd: --pcl: " << zs.size() << " sources, at most 128" << endl;
+        return 2;
+    }
+    if (!o.pcl.empty() && slicer_pcl_create(h, p.npix, p.fov, (int)zs.size(), o.pcl == "cross", (int)o.pcl_edges.size(),
+                                            o.pcl_edges.data(), pclh.out()) != SLICER_OK)
+        return fail(h, "slicer_amd: --pcl");
     if (o.moments && slicer_moments_create(h, p.npix, o.moments_levels, SLICER_HALVE_MEAN, mh.out()) != SLICER_OK)
         return fail(h, "slicer_amd: --moments");
     if (!o.peaks_edges.empty() &&
@@ -580,6 +629,8 @@ int LensingOutputs::write()
             return rc;
     }
     if (const int rc = ph ? power_spectra() : 0)
+        return rc;
+    if (const int rc = pclh ? pseudo_spectra() : 0)
         return rc;
     if (const int rc = bsh ? bispectra() : 0)
         return rc;
@@ -946,6 +997,74 @@ int LensingOutputs::power_spectra()
         add(cl, "\n");
     }
     return write_table("power spectra", ".cl_", cl);
+}
+
+// --pcl.  The pseudo-spectra table: the '#' lines of the spectra table with mean_w, mean_w2, taper_arcmin, taper_pix (0
+// without --pcl-taper) and mask (the file as given, "none" without --pcl-mask) before the column names, then per bin
+// ell_lo ell_hi ell_mean n_modes and per pair the decoupled C and the coupled Ct (%.17g; nan for an empty bin).  The matrix
+// table: '#' lines (npix, the bin edges in multipoles), then row b of M per line (%.17g).
+int LensingOutputs::pseudo_spectra()
+{
+    const char *who = "slicer_amd: --pcl";
+    const int S = (int)plan.zs.size(), B = (int)o.pcl_edges.size() - 1;
+    const bool cross = o.pcl == "cross";
+    const size_t n_pairs = cross ? (size_t)S * (S + 1) / 2 : S;
+    const double taper_pix = o.pcl_taper_given ? o.pcl_taper_pix(p.npix, p.fov) : 0.0;
+    DeviceMaps mask(h);
+    if (!o.pcl_mask.empty()) {
+        vector<float> w((size_t)p.npix * (size_t)p.npix);
+        const string why = fits_read_mask(o.pcl_mask, p.npix, w.data());
+        if (!why.empty()) {
+            cerr << who << "-mask: " << why << endl;
+            return 1;
+        }
+        if (!mask.add(p.npix) || slicer_copy_to_device(h, mask.maps[0], w.data(), w.size() * sizeof(float)) != SLICER_OK)
+            return fail(h, who);
+    }
+    // (slicer_pcl_set_mask waits for the stream: the host copy of the mask is no longer read when it returns)
+    if (slicer_pcl_set_mask(pclh, mask.maps.empty() ? nullptr : mask.maps[0], taper_pix) != SLICER_OK)
+        return fail(h, who);
+    vector<float *> maps(S);
+    for (int s = 0; s < S; s++)
+        if (slicer_kappa_device_map(kh, s, &maps[s]) != SLICER_OK)
+            return fail(h, who);
+    vector<double> c(n_pairs * B), ct(n_pairs * B), ell(B), M((size_t)B * B);
+    vector<int64_t> counts(B);
+    double mean_w = 0.0, mean_w2 = 0.0;
+    if (slicer_pcl_run(pclh, maps.data()) != SLICER_OK ||
+        slicer_pcl_read(pclh, c.data(), ct.data(), ell.data(), counts.data()) != SLICER_OK ||
+        slicer_pcl_coupling(pclh, M.data(), &mean_w, &mean_w2) != SLICER_OK)
+        return fail(h, who);
+    const double ell_f = 2.0 * M_PI / (p.fov * M_PI / 180.0);
+    string cl;
+    add(cl, "# npix %d\n# angle_deg %.17g\n# zs", p.npix, p.fov);
+    for (double z : plan.zs)
+        add(cl, " %.17g", z);
+    add(cl, "\n# mean_w %.17g\n# mean_w2 %.17g\n# taper_arcmin %.17g\n# taper_pix %.17g\n# mask ", mean_w, mean_w2,
+        o.pcl_taper_arcmin, taper_pix);
+    cl += o.pcl_mask.empty() ? "none" : o.pcl_mask;
+    add(cl, "\n# ell_lo ell_hi ell_mean n_modes");
+    for (int s = 0; s < S; s++)
+        for (int t = s; t < (cross ? S : s + 1); t++)
+            add(cl, " C_%d_%d Ct_%d_%d", s, t, s, t);
+    add(cl, "\n");
+    for (int b = 0; b < B; b++) {
+        add(cl, "%.17g %.17g %.17g %lld", o.pcl_edges[b] * ell_f, o.pcl_edges[b + 1] * ell_f, ell[b], (long long)counts[b]);
+        for (size_t q = 0; q < n_pairs; q++)
+            add(cl, " %.17g %.17g", c[q * B + b], ct[q * B + b]);
+        add(cl, "\n");
+    }
+    if (const int rc = write_table("pseudo-spectra", ".pcl_", cl))
+        return rc;
+    string m;
+    add(m, "# npix %d\n# ell_edges", p.npix);
+    for (double r : o.pcl_edges)
+        add(m, " %.17g", r * ell_f);
+    add(m, "\n");
+    for (int b = 0; b < B; b++)
+        for (int k = 0; k < B; k++)
+            add(m, k + 1 < B ? "%.17g " : "%.17g\n", M[(size_t)b * B + k]);
+    return write_table("mode-coupling matrix", ".pclm_", m);
 }
 
 // The bispectra table: '#' lines (npix, angle, source redshifts, the bin edges in multipoles, column names), then per

@@ -1,5 +1,5 @@
 // driver_lensing.hpp -- the lensing outputs of the SLICER_amd driver (slicer_main.cpp): their options, their host
-// planning and the device-0 work behind --kappa, --shear, --deflection, --raytrace, --power, --moments, --peaks,
+// planning and the device-0 work behind --kappa, --shear, --deflection, --raytrace, --power, --pcl, --moments, --peaks,
 // --minkowski, --bispectrum, --smooth, --shape-noise and --starlet (driver_lensing.cpp describes the options), with the small helpers the rest of the driver shares with them.
 #pragma once
 #include <deque>
@@ -20,6 +20,11 @@ struct LensingOptions {
     std::string shear_derivative;     // "" (not given: fft), "fft" or "gradient"
     std::string power;                // "", "auto" or "cross"
     std::vector<double> power_edges;  // empty: the default edges 0 .. npix-1
+    std::string pcl;                  // "" (no --pcl), "auto" or "cross"
+    std::vector<double> pcl_edges;    // --pcl-edges, required with it: at most 513
+    bool pcl_taper_given = false;
+    double pcl_taper_arcmin = 0.0;    // --pcl-taper: the width of the border taper, 0 without it
+    std::string pcl_mask;             // --pcl-mask: a FITS image of the map's size, "" without it
     bool moments = false, moments_levels_given = false;
     int moments_levels = 0;
     std::vector<double> peaks_edges;  // empty: no --peaks
@@ -38,6 +43,7 @@ struct LensingOptions {
     bool gradient() const { return shear_derivative == "gradient"; }
     int n_power_edges(int npix) const { return power_edges.empty() ? npix : (int)power_edges.size(); }
     const double *power_edges_or_null() const { return power_edges.empty() ? nullptr : power_edges.data(); }
+    double pcl_taper_pix(int npix, double angle_deg) const { return pcl_taper_arcmin * npix / (60.0 * angle_deg); }
     // scale k of --smooth in pixels of a map of npix pixels and angle_deg degrees a side
     double smooth_sigma_pix(size_t k, int npix, double angle_deg) const { return smooth_arcmin[k] * npix / (60.0 * angle_deg); }
 
@@ -102,6 +108,7 @@ struct LensingOutputs {
     Owned<slicer_kappa_handle, slicer_kappa_destroy> kh{};  // null without --kappa, and then all below are unused
     Owned<slicer_shear_handle, slicer_shear_destroy> shh{};  // --shear and --raytrace
     Owned<slicer_power_handle, slicer_power_destroy> ph{};
+    Owned<slicer_pcl_handle, slicer_pcl_destroy> pclh{};  // --pcl
     Owned<slicer_moments_handle, slicer_moments_destroy> mh{};
     Owned<slicer_peaks_handle, slicer_peaks_destroy> pkh{};
     Owned<slicer_minkowski_handle, slicer_minkowski_destroy> mkh{};
@@ -182,6 +189,7 @@ private:
                        const std::string &lead_names, const std::string &lead);
     int source_shear(size_t s, const float *d_kappa);
     int power_spectra();
+    int pseudo_spectra();
     int bispectra();
     int write_table(const char *what, const char *token, const std::string &text) const;
 };

@@ -128,6 +128,71 @@ bool fits_read_image(const std::string &path, int npix, float *image)
     return true;
 }
 
+std::string fits_read_mask(const std::string &path, int npix, float *image)
+{
+    FILE *f = fopen(path.c_str(), "rb");
+    if (!f)
+        return "cannot open " + path;
+    long bitpix = 0, naxis = -1, naxis1 = -1, naxis2 = -1;
+    bool end = false, simple = false, scaled = false, first = true;
+    char block[2880];
+    while (!end && fread(block, 1, sizeof block, f) == sizeof block) {
+        for (int c = 0; c < 36 && !end; c++) {
+            const std::string card(block + 80 * c, 80);
+            const std::string key = card.substr(0, 8);
+            const bool value = card[8] == '=';
+            if (first)
+                simple = value && key == "SIMPLE  " && card.find('T', 10) != std::string::npos;
+            first = false;
+            if (key == "END     ")
+                end = true;
+            else if (value && key == "BITPIX  ")
+                bitpix = atol(card.c_str() + 10);
+            else if (value && key == "NAXIS   ")
+                naxis = atol(card.c_str() + 10);
+            else if (value && key == "NAXIS1  ")
+                naxis1 = atol(card.c_str() + 10);
+            else if (value && key == "NAXIS2  ")
+                naxis2 = atol(card.c_str() + 10);
+            else if (value && (key == "BSCALE  " || key == "BZERO   "))
+                scaled = true;
+        }
+    }
+    std::string why;
+    if (!simple || !end)
+        why = path + " is not a FITS file";
+    else if (bitpix != -32 && bitpix != -64)
+        why = path + ": BITPIX = " + std::to_string(bitpix) + ", expected -32 or -64";
+    else if (naxis != 2 || naxis1 != npix || naxis2 != npix)
+        why = path + ": not an image of " + std::to_string(npix) + " x " + std::to_string(npix) + " pixels";
+    else if (scaled)
+        why = path + ": BSCALE / BZERO are not supported";
+    const size_t n = (size_t)npix * (size_t)npix, width = bitpix == -64 ? 8 : 4;
+    std::vector<unsigned char> data;
+    if (why.empty()) {
+        data.resize(n * width);
+        if (fread(data.data(), 1, data.size(), f) != data.size())
+            why = path + " is shorter than its header says";
+    }
+    fclose(f);
+    if (!why.empty())
+        return why;
+    for (size_t i = 0; i < n; i++) {  // big-endian IEEE
+        uint64_t u = 0;
+        for (size_t k = 0; k < width; k++)
+            u = u << 8 | data[width * i + k];
+        if (width == 4) {
+            const uint32_t v = (uint32_t)u;
+            memcpy(&image[i], &v, 4);
+        } else {
+            double d;
+            memcpy(&d, &u, 8);
+            image[i] = (float)d;
+        }
+    }
+    return "";
+}
+
 }  // namespace slicer_amd
 
 using slicer_amd::FitsKey;

@@ -30,4 +30,7 @@ bool fits_write_image(const std::string &path, const float *image, int npix, con
 // Reads back what fits_write_image writes (BITPIX -32, NAXIS1 = NAXIS2 = npix) into image[npix * npix]; false if the
 // file is missing, short or of another shape.
 bool fits_read_image(const std::string &path, int npix, float *image);
+// Reads the image of the primary HDU of any FITS file into image[npix * npix]: BITPIX -32, or -64 (every value rounded
+// to f32), NAXIS = 2, NAXIS1 = NAXIS2 = npix, no BSCALE / BZERO.  Everything else is refused: "" or why not.
+std::string fits_read_mask(const std::string &path, int npix, float *image);
 }  // namespace slicer_amd

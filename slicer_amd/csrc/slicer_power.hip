@@ -76,7 +76,8 @@ struct BinArgs {
 
 __device__ inline int pair_index(int s, int t, int S) { return s * S - s * (s - 1) / 2 + (t - s); }
 
-template <int BW>
+// RE (BW = 1, the pseudo-C_l handle's coupling matrix): the sum of the real parts instead of the squared moduli.
+template <int BW, bool RE = false>
 __global__ __launch_bounds__(kBinThreads) void k_power_bin(BinArgs a)
 {
     __shared__ int run_row[kBinThreads], run_lo[kBinThreads], run_off[kBinThreads + 1];
@@ -150,7 +151,7 @@ __global__ __launch_bounds__(kBinThreads) void k_power_bin(BinArgs a)
             for (int s = 0; s < BW; s++)
 #pragma unroll
                 for (int t = 0; t < BW; t++) {
-                    const double p = x[s].x * y[t].x + x[s].y * y[t].y;
+                    const double p = RE ? x[s].x : x[s].x * y[t].x + x[s].y * y[t].y;
                     acc[s][t] += p;
                 }
         }
@@ -416,6 +417,35 @@ int slicer_power_create(slicer_handle h, int32_t npix, double angle_deg, int32_t
     return sub_done(rc, ph, out);
 }
 
+slicer_fft_s *slicer_power_plan(slicer_power_handle ph) { return ph->fft; }
+
+int slicer_power_bin_real(slicer_power_handle ph, hipStream_t st, const double2 *spec, double norm, int column,
+                          double *d_out)
+{
+    BinArgs a{};
+    a.spec = spec;
+    a.stride = (size_t)ph->n * ph->H;
+    a.e2 = ph->e2;
+    a.slices = ph->slices;
+    a.partial = ph->partial;
+    a.n = ph->n;
+    a.H = ph->H;
+    a.B = ph->B;
+    a.nslices = ph->nslices;
+    a.S = 1;
+    a.nblocks = 1;
+    a.pair_auto = 0;
+    if (ph->nslices) {
+        hipLaunchKernelGGL((k_power_bin<1, true>), dim3((unsigned)ph->nslices), dim3(kBinThreads), 0, st, a);
+        HIPCHK(ph->h, hipGetLastError());
+    }
+    const int tpb = 256;
+    hipLaunchKernelGGL(k_power_finish, dim3((unsigned)((ph->B + tpb - 1) / tpb)), dim3(tpb), 0, st, ph->partial,
+                       ph->slice_off, ph->nmodes, d_out, 1, ph->B, ph->nslices, column, norm);
+    HIPCHK(ph->h, hipGetLastError());
+    return SLICER_OK;
+}
+
 int slicer_power_run(slicer_power_handle ph, const float *const *d_maps)
 {
     if (!ph || !d_maps)
@@ -423,13 +453,20 @@ int slicer_power_run(slicer_power_handle ph, const float *const *d_maps)
     for (int s = 0; s < ph->S; s++)
         if (!d_maps[s])
             return fail(ph->h, SLICER_ERR_ARG, "slicer_power_run: map %d is null", s);
+    return slicer_power_run_masked(ph, d_maps, nullptr);
+}
+
+int slicer_power_run_masked(slicer_power_handle ph, const float *const *d_maps, const float *d_w)
+{
     hipStream_t st;
     if (int rc = sub_stream(ph->h, ph->device, &st))
         return rc;
     const size_t stride = (size_t)ph->n * ph->H;
     auto forward = [&](int s) {
         ProfScope ps(ph->h, KN_POWER_FFT);
-        return slicer_fft_forward(ph->fft, st, d_maps[s], ph->spec + (ph->cross ? s * stride : 0));
+        double2 *khat = ph->spec + (ph->cross ? s * stride : 0);
+        return d_w ? slicer_fft_forward_masked(ph->fft, st, d_maps[s], d_w, khat)
+                   : slicer_fft_forward(ph->fft, st, d_maps[s], khat);
     };
     auto binning = [&](int s) {
         ProfScope ps(ph->h, KN_POWER_BIN);

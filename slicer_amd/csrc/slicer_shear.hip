@@ -22,7 +22,9 @@
 // no work handed between workgroups: the results are bitwise repeatable.  The plan and the forward chains are shared
 // with the power-spectrum handle (slicer_power.hip) through slicer_fft.hpp.  The bispectrum handle (slicer_bispectrum.hip,
 // row N15) also runs the inverse chains, through slicer_fft_inverse_band: a band load instead of the filter and an f64
-// store instead of the f32 one, both compiled into a second instantiation of k_fft_pass only.
+// store instead of the f32 one, both compiled into a second instantiation of k_fft_pass only.  The pseudo-C_l handle
+// (slicer_pcl.hip, row N17) adds a third with its own first-pass loads: the products of two maps on the forward row load
+// (f32 mask times f32 map, f64 times f64) and |khat|^2 on the inverse column load.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -43,13 +45,20 @@ constexpr int kColCap = kLdsPoints / 8;          // column passes: at least 8 ad
 constexpr int kMaxLines = 64;
 constexpr int kMaxStages = 16;
 
-enum Load { L_COMPLEX = 0, L_REAL_EVEN, L_REAL_PAIR, L_SPLIT_EVEN, L_SPLIT_PAIR, L_FILTER, L_C2R_EVEN, L_C2R_PAIR, L_BAND };
+enum Load {
+    L_COMPLEX = 0, L_REAL_EVEN, L_REAL_PAIR, L_SPLIT_EVEN, L_SPLIT_PAIR, L_FILTER, L_C2R_EVEN, L_C2R_PAIR, L_BAND,
+    L_REALW_EVEN, L_REALW_PAIR, L_PROD64_EVEN, L_PROD64_PAIR, L_ABS2
+};
 enum Store { S_COMPLEX = 0, S_REAL_EVEN, S_REAL_PAIR, S_GAMMA_EVEN, S_GAMMA_PAIR, S_REAL64_EVEN, S_REAL64_PAIR };
-// L_BAND and S_REAL64_* (slicer_fft_inverse_band) exist only in the BAND instantiation of k_fft_pass: the kernel behind
-// the shear, deflection and power outputs is compiled without them and keeps its registers.
+// The instantiations of k_fft_pass.  V_PLAIN, the kernel behind the shear, deflection and power outputs, is compiled
+// without the loads and stores below and keeps its registers.  V_BAND adds L_BAND and S_REAL64_*
+// (slicer_fft_inverse_band); V_PCL adds L_REALW_*, L_PROD64_*, L_ABS2 and S_REAL64_* (the masked pseudo-C_l handle,
+// slicer_pcl.hip).
+enum Variant { V_PLAIN = 0, V_BAND, V_PCL };
 
 struct PassArgs {
     const void *in;
+    const void *in2;    // L_REALW_*: the f32 mask; L_PROD64_*: the second f64 map
     void *out;          // complex f64 (S_COMPLEX) or the f32 map (gamma1 for S_GAMMA_*)
     float *out2, *out3;  // S_GAMMA_*: gamma2, |gamma|
     const double2 *aux;  // S_GAMMA_*: gamma1 in f64, as its last row pass left it
@@ -65,6 +74,8 @@ struct PassArgs {
     double scale;                      // S_REAL_* / S_GAMMA_* / S_REAL64_*: 1 / n^2
     double band_lo2, band_hi2;         // L_BAND: the mode is kept iff lo2 <= m2 < hi2 (<= with band_closed) and m2 != 0
     int band_closed, band_ones;        // L_BAND: band_ones = the spectrum is not read, every kept mode is 1
+    int band_dc;                       // L_BAND: m2 = 0 is kept as well (if the band holds it)
+    int variant;                       // host only: V_PCL sends every pass of the chain to that instantiation
     int nst;
     int rad[kMaxStages];
 };
@@ -84,14 +95,43 @@ __device__ inline double2 twid(const PassArgs &a, int x, int M)
     return a.inv ? conjg(w) : w;
 }
 
-template <bool BAND>
+template <int V>
 __device__ double2 load_point(const PassArgs &a, int l, int e)
 {
     const int n = a.n, H = a.H;
-    if (BAND && a.load == L_BAND) {  // khat[e][l] (or 1) inside the band of the exact integer m2, 0 outside and at m2 = 0
+    if (V == V_PCL) {
+        switch (a.load) {
+        case L_REALW_EVEN: {  // L_REAL_EVEN of the f32 products mask * map, one rounding each
+            const size_t i = (size_t)l * n + 2 * e;
+            const float *k = (const float *)a.in + i, *w = (const float *)a.in2 + i;
+            return make_double2((double)(w[0] * k[0]), (double)(w[1] * k[1]));
+        }
+        case L_REALW_PAIR: {  // L_REAL_PAIR likewise
+            const size_t i = (size_t)(2 * l) * n + e;
+            const float *k = (const float *)a.in + i, *w = (const float *)a.in2 + i;
+            return make_double2((double)(w[0] * k[0]), 2 * l + 1 < n ? (double)(w[n] * k[n]) : 0.0);
+        }
+        case L_PROD64_EVEN: {  // L_REAL_EVEN of the f64 products of two f64 maps
+            const size_t i = (size_t)l * n + 2 * e;
+            const double *x = (const double *)a.in + i, *y = (const double *)a.in2 + i;
+            return make_double2(x[0] * y[0], x[1] * y[1]);
+        }
+        case L_PROD64_PAIR: {
+            const size_t i = (size_t)(2 * l) * n + e;
+            const double *x = (const double *)a.in + i, *y = (const double *)a.in2 + i;
+            return make_double2(x[0] * y[0], 2 * l + 1 < n ? x[n] * y[n] : 0.0);
+        }
+        case L_ABS2: {  // |khat[e][l]|^2
+            const double2 s = ((const double2 *)a.in)[(size_t)e * H + l];
+            return make_double2(s.x * s.x + s.y * s.y, 0.0);
+        }
+        default: break;
+        }
+    }
+    if (V == V_BAND && a.load == L_BAND) {  // khat[e][l] (or 1) inside the band of the exact integer m2, 0 outside and at m2 = 0
         const double f0 = (double)(e < (n + 1) / 2 ? e : e - n), f1 = (double)l;
         const double m2 = f0 * f0 + f1 * f1;  // exact: integers below 2^28
-        const bool in = m2 != 0.0 && m2 >= a.band_lo2 && (a.band_closed ? m2 <= a.band_hi2 : m2 < a.band_hi2);
+        const bool in = (m2 != 0.0 || a.band_dc) && m2 >= a.band_lo2 && (a.band_closed ? m2 <= a.band_hi2 : m2 < a.band_hi2);
         if (!in)
             return make_double2(0.0, 0.0);
         return a.band_ones ? make_double2(1.0, 0.0) : ((const double2 *)a.in)[(size_t)e * H + l];
@@ -170,17 +210,17 @@ __device__ double2 load_point(const PassArgs &a, int l, int e)
     }
 }
 
-template <bool BAND>
+template <int V>
 __device__ void store_point(const PassArgs &a, int l, int e, double2 v)
 {
     const int n = a.n;
-    if (BAND && a.store == S_REAL64_EVEN) {  // S_REAL_EVEN without the cast
+    if (V != V_PLAIN && a.store == S_REAL64_EVEN) {  // S_REAL_EVEN without the cast
         double *o = (double *)a.out + (size_t)l * n + 2 * e;
         o[0] = v.x * a.scale;
         o[1] = v.y * a.scale;
         return;
     }
-    if (BAND && a.store == S_REAL64_PAIR) {  // S_REAL_PAIR without the cast
+    if (V != V_PLAIN && a.store == S_REAL64_PAIR) {  // S_REAL_PAIR without the cast
         double *o = (double *)a.out + (size_t)(2 * l) * n + e;
         o[0] = v.x * a.scale;
         if (2 * l + 1 < n)
@@ -278,7 +318,7 @@ __device__ void lds_stage(const PassArgs &a, double2 *lds, int C, int R, int Ns)
     __syncthreads();
 }
 
-template <bool BAND>
+template <int V>
 __global__ __launch_bounds__(kThreads) void k_fft_pass(PassArgs a)
 {
     extern __shared__ double2 lds[];
@@ -287,7 +327,7 @@ __global__ __launch_bounds__(kThreads) void k_fft_pass(PassArgs a)
         const int c = a.cfast ? t % C : t / R, r = a.cfast ? t / C : t % R, l = l0 + c;
         double2 v = make_double2(0.0, 0.0);
         if (l < a.nlines) {
-            v = load_point<BAND>(a, l, j + r * stride);
+            v = load_point<V>(a, l, j + r * stride);
             if (k && r)
                 v = cmul(v, twid(a, r * k, a.Ns * R));
         }
@@ -310,7 +350,7 @@ __global__ __launch_bounds__(kThreads) void k_fft_pass(PassArgs a)
     for (int t = threadIdx.x; t < C * R; t += kThreads) {
         const int c = a.cfast ? t % C : t / R, q = a.cfast ? t / C : t % R, l = l0 + c;
         if (l < a.nlines)
-            store_point<BAND>(a, l, base + q * a.Ns, lds[c * a.Rp + q]);
+            store_point<V>(a, l, base + q * a.Ns, lds[c * a.Rp + q]);
     }
 }
 
@@ -433,10 +473,12 @@ int run_chain(slicer_fft_s *f, hipStream_t st, const std::vector<Pass> &passes, 
         }
         const size_t lds = (size_t)ps.C * ps.Rp * sizeof(double2);
         const dim3 grid((unsigned)((a.nlines + ps.C - 1) / ps.C), (unsigned)(a.L / ps.R));
-        if (a.load == L_BAND || a.store == S_REAL64_EVEN || a.store == S_REAL64_PAIR)
-            hipLaunchKernelGGL(k_fft_pass<true>, grid, dim3(kThreads), lds, st, a);
+        if (proto.variant == V_PCL)
+            hipLaunchKernelGGL(k_fft_pass<V_PCL>, grid, dim3(kThreads), lds, st, a);
+        else if (a.load == L_BAND || a.store == S_REAL64_EVEN || a.store == S_REAL64_PAIR)
+            hipLaunchKernelGGL(k_fft_pass<V_BAND>, grid, dim3(kThreads), lds, st, a);
         else
-            hipLaunchKernelGGL(k_fft_pass<false>, grid, dim3(kThreads), lds, st, a);
+            hipLaunchKernelGGL(k_fft_pass<V_PLAIN>, grid, dim3(kThreads), lds, st, a);
         HIPCHK(f->h, hipGetLastError());
         in = a.out;
     }
@@ -465,7 +507,8 @@ int slicer_fft_create(slicer_handle h, int npix, int split, hipStream_t st, int 
     const size_t passes = std::max(f->row_chain.size(), f->col_chain.size());
 
     int rc = SLICER_OK;
-    for (const void *kernel : {(const void *)k_fft_pass<false>, (const void *)k_fft_pass<true>})
+    for (const void *kernel : {(const void *)k_fft_pass<V_PLAIN>, (const void *)k_fft_pass<V_BAND>,
+                               (const void *)k_fft_pass<V_PCL>})
         if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)((kLdsPoints + kMaxLines) * sizeof(double2))) != hipSuccess)
             rc = fail(h, SLICER_ERR_HIP, "%s: cannot raise the LDS limit of the FFT kernel", who);
@@ -509,8 +552,49 @@ int slicer_fft_forward(slicer_fft_s *f, hipStream_t st, const float *map, double
     return run_chain(f, st, f->col_chain, true, false, e, proto);
 }
 
+int slicer_fft_forward_masked(slicer_fft_s *f, hipStream_t st, const float *map, const float *mask, double2 *khat)
+{
+    const bool even = f->n % 2 == 0;
+    PassArgs p{};
+    p.variant = V_PCL;
+    p.in2 = mask;
+    // as slicer_fft_forward, the row load taking the products
+    End e{map, f->A, even ? L_REALW_EVEN : L_REALW_PAIR, S_COMPLEX, 0, 0, f->len, 1};
+    if (int rc = run_chain(f, st, f->row_chain, false, false, e, p))
+        return rc;
+    e = End{f->A, khat, even ? L_SPLIT_EVEN : L_SPLIT_PAIR, S_COMPLEX, 0, 0, 1, f->H};
+    return run_chain(f, st, f->col_chain, true, false, e, p);
+}
+
+int slicer_fft_forward_product(slicer_fft_s *f, hipStream_t st, const double *x, const double *y, double2 *khat)
+{
+    const bool even = f->n % 2 == 0;
+    PassArgs p{};
+    p.variant = V_PCL;
+    p.in2 = y;
+    End e{x, f->A, even ? L_PROD64_EVEN : L_PROD64_PAIR, S_COMPLEX, 0, 0, f->len, 1};
+    if (int rc = run_chain(f, st, f->row_chain, false, false, e, p))
+        return rc;
+    e = End{f->A, khat, even ? L_SPLIT_EVEN : L_SPLIT_PAIR, S_COMPLEX, 0, 0, 1, f->H};
+    return run_chain(f, st, f->col_chain, true, false, e, p);
+}
+
+int slicer_fft_inverse_abs2(slicer_fft_s *f, hipStream_t st, const double2 *khat, double *out)
+{
+    const bool even = f->n % 2 == 0;
+    PassArgs p{};
+    p.variant = V_PCL;
+    p.scale = 1.0 / ((double)f->n * (double)f->n);
+    // |khat|^2 + columns khat -> A; c2r rows A -> out in f64, as slicer_fft_inverse_band
+    End e{khat, f->A, L_ABS2, S_COMPLEX, 0, 0, 1, f->H};
+    if (int rc = run_chain(f, st, f->col_chain, true, true, e, p))
+        return rc;
+    e = End{f->A, out, even ? L_C2R_EVEN : L_C2R_PAIR, even ? S_REAL64_EVEN : S_REAL64_PAIR, 0, 0, 0, 0};
+    return run_chain(f, st, f->row_chain, false, true, e, p);
+}
+
 int slicer_fft_inverse_band(slicer_fft_s *f, hipStream_t st, const double2 *khat, double lo2, double hi2, int closed,
-                            double *out)
+                            double *out, int keep_dc)
 {
     const bool even = f->n % 2 == 0;
     PassArgs p{};
@@ -518,6 +602,7 @@ int slicer_fft_inverse_band(slicer_fft_s *f, hipStream_t st, const double2 *khat
     p.band_hi2 = hi2;
     p.band_closed = closed;
     p.band_ones = khat == nullptr;
+    p.band_dc = keep_dc;
     p.scale = 1.0 / ((double)f->n * (double)f->n);
     // band + columns khat -> A; c2r rows A -> out, as the shear handle's inverses with the f64 store
     End e{khat, f->A, L_BAND, S_COMPLEX, 0, 0, 1, f->H};

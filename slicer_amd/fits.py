@@ -32,9 +32,9 @@ def card(name, value, comment=" "):
     return c[:80].ljust(80)
 
 
-def header_bytes(npix, keys):
+def header_bytes(npix, keys, bitpix=-32):
     cards = ["SIMPLE  =                    T / file does conform to FITS standard",
-             "BITPIX  =                  -32 / number of bits per data pixel",
+             "BITPIX  = %20d / number of bits per data pixel" % bitpix,
              "NAXIS   =                    2 / number of data axes",
              "NAXIS1  = %20d / length of data axis 1" % npix,
              "NAXIS2  = %20d / length of data axis 2" % npix,
@@ -46,15 +46,17 @@ def header_bytes(npix, keys):
     return raw + b" " * (-len(raw) % 2880)
 
 
-def write_image(path, image, keys):
-    """Refuses to overwrite, like CCfits' FITS(name, FLOAT_IMG, ...) without a leading '!' (FITS::CantCreate)."""
-    image = np.asarray(image, dtype=np.float32)
+def write_image(path, image, keys, bitpix=-32):
+    """Refuses to overwrite, like CCfits' FITS(name, FLOAT_IMG, ...) without a leading '!' (FITS::CantCreate).
+    bitpix -32 (f32, what the reference writes) or -64 (f64, DOUBLE_IMG)."""
+    assert bitpix in (-32, -64)
+    image = np.asarray(image, dtype=np.float32 if bitpix == -32 else np.float64)
     assert image.ndim == 2 and image.shape[0] == image.shape[1]
     if os.path.exists(path):
         raise FileExistsError(f"It was not possible to create the map: {path}")
-    data = image.astype(">f4").tobytes()
+    data = image.astype(">f4" if bitpix == -32 else ">f8").tobytes()
     with open(path, "wb") as f:
-        f.write(header_bytes(image.shape[0], keys))
+        f.write(header_bytes(image.shape[0], keys, bitpix))
         f.write(data + b"\0" * (-len(data) % 2880))
 
 

@@ -5,7 +5,8 @@ of 2x2 halvings (row N9), and the one-point PDF histogram and peak / minimum cou
 multi-plane ray tracing through the lens planes (row N11), and Gaussian and aperture-mass smoothing of such maps (row N12),
 and shape noise for such maps from a counter-based generator (row N13), and the Minkowski functionals of such maps'
 excursion sets as exact counts (row N14), and the binned bispectra of such maps (row N15), and the starlet transform of
-such maps with the binned absolute sums of its scales, the starlet l1-norm (row N16).
+such maps with the binned absolute sums of its scales, the starlet l1-norm (row N16), and the masked pseudo-C_l of such
+maps: coupled bandpowers, the mask's mode-coupling matrix and the decoupled bandpowers (row N17).
 
 plane_weights wraps the host weights of include/slicer_amd.h (slicer_lensing_weights); Kappa is the device accumulator
 (slicer_kappa_*) bound to a Slicer handle: it reads the finalized plane maps where they are, in HBM.  Shear (slicer_shear_*)
@@ -20,7 +21,8 @@ the planes' deflection, convergence and shear maps (plane_strengths scales a mas
 Minkowski (slicer_minkowski_*) counts the faces, edges and vertices of the pixel complex that lie in the sets x >= t_j;
 Bispectrum (slicer_bispectrum_*) contracts the band-filtered f64 maps of a map over a list of bin triples; Starlet
 (slicer_starlet_*) splits a map into wavelet scales that sum back to it, and L1Norm (slicer_l1norm_*) sums |x| of a map's
-pixels bin by bin over Peaks' edges.
+pixels bin by bin over Peaks' edges; Pcl (slicer_pcl_*) is Power under a mask (a border taper, a user mask or both),
+with the coupling matrix of the mask and the bandpowers decoupled by it.
 """
 import ctypes as C
 import math
@@ -899,6 +901,101 @@ class L1Norm(_SubHandle):
                                            above.ctypes.data, nan.ctypes.data, below_l1.ctypes.data, above_l1.ctypes.data))
         return {"edges": self.edges.copy(), "counts": counts, "l1": l1, "below": int(below[0]), "above": int(above[0]),
                 "nan": int(nan[0]), "below_l1": float(below_l1[0]), "above_l1": float(above_l1[0])}
+
+
+PCL_MAX_BINS = 512
+
+
+def pcl_taper(npix, width_pix):
+    """The border taper table f [npix] (f64) as slicer_pcl_taper makes it: with x_i = min(i, npix-1-i) + 0.5 and
+    t = x_i / width_pix, f_i = 1 for t >= 1, else t - sin(2 pi t) / (2 pi); host only, no device needed."""
+    f = np.zeros(max(int(npix), 0), np.float64)
+    _host_chk(_L.slicer_pcl_taper(int(npix), float(width_pix), f.ctypes.data))
+    return f
+
+
+class Pcl(_SubHandle):
+    """Masked pseudo-C_l of n_maps npix^2 maps of side angle_deg degrees under one shared mask, on the device of
+    `slicer`, on its stream: the coupled bandpowers of the masked maps, the mode-coupling matrix
+    of the mask and the decoupled bandpowers.  cross and the edges (required; units of l_f, or ell_edges in multipoles;
+    at most 512 bins) as for Power."""
+    _handle, _destroy = "_ph", "slicer_pcl_destroy"
+
+    def __init__(self, slicer: Slicer, npix, angle_deg, n_maps, cross=False, edges=None, ell_edges=None):
+        self._s = slicer
+        self.npix, self.angle_deg, self.n_maps, self.cross = int(npix), float(angle_deg), int(n_maps), bool(cross)
+        ok = math.isfinite(self.angle_deg) and self.angle_deg > 0  # otherwise slicer_pcl_create refuses it
+        self.ell_f = ell_fundamental(self.angle_deg) if ok else math.nan
+        if edges is None and ell_edges is None:
+            raise ValueError("Pcl needs edges or ell_edges")
+        n_edges, e = _edges(self.npix, edges, ell_edges, self.angle_deg)
+        self.edges = e.copy()
+        self.n_bins = n_edges - 1
+        ph = C.c_void_p()
+        slicer._chk(_L.slicer_pcl_create(slicer._h, self.npix, self.angle_deg, self.n_maps, int(self.cross), n_edges,
+                                         _dptr(e), C.byref(ph)))
+        self._ph = ph
+
+    def set_mask(self, d_mask=None, taper_pix=0.0):
+        """d_mask: device address of an f32 npix^2 mask, or None for the border taper alone; taper_pix: the taper's
+        width in pixels, 0 for the mask alone.  Builds the coupling matrix; waits for the stream."""
+        self._s._chk(_L.slicer_pcl_set_mask(self._ph, None if d_mask is None else int(d_mask), float(taper_pix)))
+
+    def mask(self):
+        """The mask in use, f32 [npix, npix]."""
+        out = np.empty((self.npix, self.npix), np.float32)
+        self._s._chk(_L.slicer_pcl_read_mask(self._ph, out.ctypes.data))
+        return out
+
+    def coupling(self):
+        """dict: M [B, B] (rows and columns of empty bins are 0), mean_w, mean_w2."""
+        B = max(self.n_bins, 0)
+        M = np.empty((B, B), np.float64)
+        m1, m2 = C.c_double(), C.c_double()
+        self._s._chk(_L.slicer_pcl_coupling(self._ph, M.ctypes.data, C.byref(m1), C.byref(m2)))
+        return {"M": M, "mean_w": m1.value, "mean_w2": m2.value}
+
+    def run(self, ptrs):
+        """ptrs: device addresses of the n_maps f32 npix^2 maps (unmasked: the mask is applied as they are loaded)."""
+        ptrs = [int(p) for p in ptrs]
+        if len(ptrs) != self.n_maps:
+            raise ValueError(f"expected {self.n_maps} maps, got {len(ptrs)}")
+        arr = (C.c_void_p * len(ptrs))(*ptrs)
+        self._s._chk(_L.slicer_pcl_run(self._ph, arr))
+
+    def run_kappa(self, kappa: Kappa):
+        """The maps of every source of a Kappa accumulator, where they are."""
+        self.run([kappa.device_map(s) for s in range(kappa.n_sources)])
+
+    def spectrum(self, map):
+        """rfft2 of the masked map `map` of the last run, [npix, npix // 2 + 1] complex128 (auto mode: the last only)."""
+        out = np.empty((self.npix, self.npix // 2 + 1), np.complex128)
+        self._s._chk(_L.slicer_pcl_spectrum(self._ph, int(map), out.ctypes.data))
+        return out
+
+    def read(self):
+        """dict: ell_lo, ell_hi, ell (mean l), counts, and cl (decoupled; NaN in empty bins) and coupled, each
+        [S][S][B], symmetric (cross) or [S][B] (auto)."""
+        S, B = self.n_maps, self.n_bins
+        npairs = S * (S + 1) // 2 if self.cross else S
+        flat, cflat = np.empty((npairs, B), np.float64), np.empty((npairs, B), np.float64)
+        ell = np.empty(B, np.float64)
+        counts = np.empty(B, np.int64)
+        self._s._chk(_L.slicer_pcl_read(self._ph, flat.ctypes.data, cflat.ctypes.data, ell.ctypes.data,
+                                        counts.ctypes.data))
+
+        def square(x):
+            if not self.cross:
+                return x
+            out = np.empty((S, S, B), np.float64)
+            p = 0
+            for s in range(S):
+                for t in range(s, S):
+                    out[s, t] = out[t, s] = x[p]
+                    p += 1
+            return out
+        return {"ell_lo": self.edges[:-1] * self.ell_f, "ell_hi": self.edges[1:] * self.ell_f, "ell": ell,
+                "counts": counts, "cl": square(flat), "coupled": square(cflat)}
 
 
 RAYS_KAPPA, RAYS_GAMMA1, RAYS_GAMMA2, RAYS_OMEGA, RAYS_DEFLECTION1, RAYS_DEFLECTION2 = range(6)
