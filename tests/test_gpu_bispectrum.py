@@ -188,6 +188,47 @@ def test_two_pass_column_chain():
     assert np.array_equal(np.rint(got["triangles"]).astype(np.int64), exact) and np.all(exact > 0)
 
 
+def chunking(n):
+    """(pixels of a chunk, chunks) of k_bispectrum as slicer_bispectrum_create of slicer_amd/csrc/slicer_bispectrum.hip
+    sets them: at most kMaxChunks = 1024 chunks of at least kMinChunk = 4096 pixels, a multiple of 64."""
+    npix2 = n * n
+    want = min(1024, (npix2 + 4095) // 4096)
+    chunk = ((npix2 + want - 1) // want + 63) // 64 * 64
+    return chunk, (npix2 + chunk - 1) // chunk
+
+
+# A lane sums its products in blocks of kInner = 64 wave-wide steps, and a chunk has chunk / 64 steps: up to n = 2048
+# (1024 chunks of 4096) every chunk is one block, only past it a second one adds into the accumulators in LDS.  One chunk
+# (n <= 64), fewer chunks than the 64 lanes of k_bispectrum_finish (100: 3), more (1000: 245, four a lane, the last two
+# lanes idle) and a ragged last chunk (every size but the powers of two) are met by CASES.
+assert all(chunking(n)[0] <= 64 * 64 for n in (16, 30, 45, 49, 100, 1000, 1024, 2048)) and chunking(2048) == (4096, 1024)
+assert [chunking(n)[1] for n in (49, 100, 1000, 1024)] == [1, 3, 245, 256]
+assert chunking(2058) == (4160, 1019) and 2058 * 2058 - 1018 * 4160 == 484  # 65 steps; the last chunk is ragged
+
+
+@pytest.mark.gpu
+def test_chunks_past_one_inner_block():
+    """n = 2058 = 2 * 3 * 7^3 is the smallest size the transform takes past 2048: kMaxChunks caps the chunks at 1024, a
+    chunk grows to 4160 pixels and its 65th step is a second inner block.  Two unit bins and their four triples; stage
+    (c) as above, and the triangle counts, which the same contraction forms at create."""
+    n, angle = 2058, 10.0
+    edges = np.array([2.0, 3.0, 4.0])
+    tr = bispectrum_np.all_triples(2)
+    kappa = shear_np.clustered(n, 11)
+    with slicer_amd.Slicer(0) as s:
+        d = s.to_device(kappa)
+        try:
+            got = run_bispectrum(s, d, n, angle, edges, tr, maps=True)
+        finally:
+            s.free(d)
+    for t, (i, j, k) in enumerate(tr):
+        prod = ((got["F"][i] * got["F"][j]) * got["F"][k]).ravel()
+        want, scale = math.fsum(prod), math.fsum(np.abs(prod))
+        assert scale > 0 and abs(got["sums"][t] - want) <= 1e-13 * scale, (i, j, k)
+    exact = np.rint(bispectrum_np.triangles(n, edges, tr)).astype(np.int64)
+    assert np.array_equal(np.rint(got["triangles"]).astype(np.int64), exact) and np.all(exact > 0)
+
+
 @pytest.mark.gpu
 def test_runs_repeat_and_carry_nothing_over():
     n, angle = 45, 5.0

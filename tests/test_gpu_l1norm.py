@@ -15,8 +15,57 @@ pytestmark = pytest.mark.gpu
 
 L = lensing._L
 ERR_ARG, ERR_STATE = 2, 3
-SIZES = [1, 2, 3, 63, 64, 65, 257, 1000]  # 257^2 and 1000^2 are no multiple of a chunk of 256 pixels; 1000^2 is many chunks a workgroup
+# A chunk is 512 pixels (kL1Chunk = 64 lanes x 8), and workgroup g of G takes chunks g, g + G, ...  257^2 and 1000^2 are
+# no multiple of a chunk.  1000^2 is 1954 chunks: on 256 CUs B = 1, 7, 64 run 1954 workgroups of one chunk each, and
+# only B = 1024 (1280 workgroups) gives 674 of them a second chunk.  A third chunk, and with it the second rotation of
+# the prefetched one, is met at ROUNDS_N alone (test_every_workgroup_takes_several_chunks).
+SIZES = [1, 2, 3, 63, 64, 65, 257, 1000]
 BINS = [1, 7, 64, 1024]                   # 1024: two copies of the sums a wave, 64: thirty-two, 1 and 7: sixty-four
+ROUNDS_N, ROUNDS_CUS = 1801, 256          # the map on which every workgroup takes three chunks or more, and the CUs it was sized for
+
+
+def resident_groups(lds_bytes, tiles, num_cus):
+    """resident_groups of slicer_amd/csrc/slicer_rank_counts.hpp: kPerCu = 8, kMinGroups = 64, 160 KiB of LDS a CU."""
+    per_cu = max(1, min(8, 160 * 1024 // lds_bytes))
+    return min(tiles, max(64, per_cu * num_cus))
+
+
+def l1_grid(n, B, num_cus):
+    """(chunks, workgroups) of k_l1norm for an n x n map: l1_copies_log2, l1_lds and slicer_l1norm_create of
+    slicer_amd/csrc/slicer_starlet.hip."""
+    cl = 0
+    while cl < 6 and ((B + 2) * 8 << (cl + 1)) <= 32 * 1024:
+        cl += 1
+    lds = (B + 1) * 8 + ((B + 2) * 8 << cl) + (B + 3) * 4
+    chunks = (n * n + 511) // 512
+    return chunks, resident_groups(lds, chunks, num_cus)
+
+
+def device_cus():
+    """The CUs of device 0 as slicer_create reads them: hipDeviceGetAttribute of hipDeviceAttributeMultiprocessorCount
+    (63 in ROCm 7's hip_runtime_api.h), looked up through the library's own handle and so in the HIP runtime it is
+    linked to.  (torch.cuda cannot be asked in this process: the wheel loads its own copy of the runtime, which finds no
+    device once the library's has opened it.)"""
+    value = C.c_int(0)
+    L.hipDeviceGetAttribute.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_int]
+    assert L.hipDeviceGetAttribute(C.byref(value), 63, 0) == 0 and 1 <= value.value <= 4096, value.value
+    return value.value
+
+
+def fewest_chunks(n, B, num_cus):
+    """The chunks of the workgroup that takes the fewest (the last one)."""
+    chunks, G = l1_grid(n, B, num_cus)
+    return chunks // G
+
+
+# What the comments above and the sizing of ROUNDS_N claim, on ROUNDS_CUS CUs (no device needed)
+assert [l1_grid(1000, B, ROUNDS_CUS) for B in BINS] == [(1954, 1954)] * 3 + [(1954, 1280)]
+assert [l1_grid(ROUNDS_N, B, ROUNDS_CUS) for B in BINS] == [(6336, 2048)] * 3 + [(6336, 1280)]  # 192 workgroups take four
+assert ROUNDS_N * ROUNDS_N - 6335 * 512 == 81                                                   # the last chunk is ragged
+assert all(fewest_chunks(ROUNDS_N, B, ROUNDS_CUS) >= 3 for B in BINS)
+# ... and 1775 is the smallest odd n with more than 3 * 8 * 256 chunks, the last of them ragged
+assert min(n for n in range(1, 2000, 2) if (n * n + 511) // 512 > 3 * 8 * ROUNDS_CUS and n * n % 512) == 1775
+assert all(fewest_chunks(1775, B, ROUNDS_CUS) >= 3 for B in BINS) and fewest_chunks(1773, 7, ROUNDS_CUS) == 2
 
 
 @pytest.fixture(scope="module")
@@ -131,6 +180,43 @@ def test_an_integer_valued_map_sums_exactly(slicer, n):
         ref = W.l1norm(x, edges)
         assert got["l1"].tolist() == ref["l1"].tolist() and np.array_equal(got["counts"], ref["counts"])
         assert (got["below_l1"], got["above_l1"]) == (ref["below_l1"], ref["above_l1"])
+
+
+@pytest.mark.parametrize("part", ["lognormal", "integers", "non_finite"])
+def test_every_workgroup_takes_several_chunks(slicer, part):
+    """ROUNDS_N^2 pixels are 6336 chunks: on 256 CUs workgroups 0 ... 191 of 2048 (B = 1, 7, 64) take four chunks and the
+    rest three, the 1280 of B = 1024 four or five, so the grid-stride loop, the prefetch of the next chunk and the
+    rotation cur = nxt run more than twice in every workgroup; the last chunk holds 81 pixels.  The bounds are the
+    header's: counts exact, |sum - S| <= count 2^-53 S against math.fsum."""
+    n, cus = ROUNDS_N, device_cus()
+    print(f"{cus} CUs: (chunks, workgroups) = {[l1_grid(n, B, cus) for B in BINS]}")
+    for B in BINS:  # on another device the map has to be sized anew: fail, do not pass beside the point
+        assert fewest_chunks(n, B, cus) >= 3, (cus, B, l1_grid(n, B, cus))
+    if part == "lognormal":
+        for B in BINS:
+            got = check(slicer, make_map(n), slicer_amd.peaks_edges(-1.2, 2.5, B), twice=True)
+            assert got["below"] > 0 and got["above"] > 0
+    elif part == "integers":  # a dropped, repeated or misplaced chunk changes a sum or a count exactly
+        x = np.random.default_rng(n).integers(-40, 41, size=(n, n)).astype(np.float32)
+        for B in (7, 1024):
+            edges = slicer_amd.peaks_edges(-32.0, 32.0, B)
+            got, _ = run(slicer, x, edges, twice=True)
+            ref = W.l1norm(x, edges)
+            assert got["l1"].tolist() == ref["l1"].tolist() and np.array_equal(got["counts"], ref["counts"])
+            assert (got["below_l1"], got["above_l1"]) == (ref["below_l1"], ref["above_l1"])
+            assert (got["below"], got["above"], got["nan"]) == (ref["below"], ref["above"], 0)
+    else:  # three NaNs, +inf and -inf in the last, ragged chunk and in a chunk of a workgroup's third round
+        B = 7
+        chunks, G = l1_grid(n, B, cus)
+        flat = make_map(n).copy().ravel()
+        for chunk in (chunks - 1, 2 * G + G // 3):
+            assert 2 * G <= chunk < chunks
+            at = chunk * 512 + np.array([0, 17, 64, 70, 80])  # lanes 0 and 17 of q = 0; lanes 0, 6 and 16 of q = 1 (the map's last pixel)
+            assert at[-1] < n * n
+            flat[at] = [np.nan, np.inf, np.nan, -np.inf, np.nan]
+        got = check(slicer, flat.reshape(n, n), slicer_amd.peaks_edges(-1.2, 2.5, B), twice=True)
+        assert got["nan"] == 6 and got["below_l1"] == math.inf and got["above_l1"] == math.inf
+        assert got["counts"].sum() + got["below"] + got["above"] == n * n - 6 and np.isfinite(got["l1"]).all()
 
 
 def test_run_npix_and_the_scales_of_a_starlet(slicer):

@@ -16,7 +16,10 @@ pytestmark = pytest.mark.gpu
 L = lensing._L
 ERR_ARG, ERR_STATE = 2, 3
 # The cell grid is n + 1 wide: tile seams fall between n = 15 / 16 (rows) and 63 / 64 (columns); maps that are all border
-# (1, 2); both load paths (4 | n or not); more tiles than workgroups (4096: 16705 tiles)
+# (1, 2); both load paths (4 | n or not); more tiles than workgroups (4096: 16705 tiles).  The grid is at most 8
+# workgroups a CU (5 at T = 1025, whose LDS is 31172 B), 2048 and 1280 on 256 CUs, so the tile loop takes a second round
+# from 2049 (1281) tiles on: 4096 runs it eight to fourteen times on the float4 path; 1425 (1426 cells: 90 x 23 = 2070
+# tiles, the smallest odd n past 2048) runs it twice on the scalar path with a short last tile row and column
 SMALL = [1, 2, 3, 4, 5, 15, 16, 17, 18, 33, 63, 64, 65, 66, 67, 68, 100, 129]
 KINDS = ("white", "lognormal", "integers")
 COUNTS = (1, 2, 8, 65, 1025)
@@ -92,6 +95,7 @@ def test_counts_are_the_restatement(slicer, n):
     (1000, "white", 8, "log"), (1000, "lognormal", 1025, "uniform"), (1000, "integers", 65, "uniform"),
     (1023, "white", 1025, "log"), (1023, "lognormal", 1, "uniform"), (1023, "integers", 8, "uniform"),
     (1024, "white", 65, "uniform"), (1024, "lognormal", 2, "log"), (1024, "integers", 1025, "log"),
+    (1425, "white", 8, "log"), (1425, "lognormal", 1025, "uniform"),
     (4096, "white", 1025, "uniform"), (4096, "lognormal", 65, "log"), (4096, "integers", 1, "uniform"),
 ])
 def test_counts_of_large_maps_are_the_restatement(slicer, n, kind, T, spacing):

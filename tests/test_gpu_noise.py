@@ -17,7 +17,10 @@ pytestmark = pytest.mark.gpu
 L = lensing._L
 ERR_ARG, ERR_STATE, ERR_UNSUPPORTED = 2, 3, 6
 SEED = 0xFEDCBA9876543210
-# the tail block with n^2 mod 4 = 0 and 1, under a workgroup (n^2 / 4 < 256), and many workgroups
+# the tail block with n^2 mod 4 = 0 and 1, under a workgroup (n^2 / 4 < 256), and many workgroups.  A square map never
+# ends 2 or 3 pixels into a block: run_at does (test_a_run_that_ends_inside_a_block).  The threads stride only beyond
+# kMaxGroups = 2^20 workgroups of 256 blocks of 4 pixels, a run of more than 2^30 pixels (n > 32768, 4 GiB of output):
+# no test here reaches that loop's second round
 SIZES = [1, 2, 3, 4, 5, 7, 8, 9, 15, 16, 17, 63, 64, 65, 100, 257, 1000, 1024]
 SIGMAS = (0.3, 1.0, 1e-3)
 
@@ -175,6 +178,32 @@ def test_a_smaller_map_is_the_start_of_a_larger_one(slicer):
                 nz.run(d, 0.3, npix=m)
                 got = nz.read()
                 assert got.shape == (m, m) and got.tobytes() == want[:m * m].tobytes(), m
+    finally:
+        slicer.free(d)
+
+
+def test_a_run_that_ends_inside_a_block(slicer):
+    """count mod 4 = 1, 2, 3: the last block is loaded and stored pixel by pixel, on both load paths and without a map,
+    and what it stores is the start of the whole block's values."""
+    n = 9
+    x = make_map(n)
+    want = run(slicer, x, n, 0.3).ravel()
+    want_pure = run(slicer, None, n, 0.3).ravel()
+    d = slicer.to_device(np.concatenate([np.zeros(1, np.float32), x]))
+    try:
+        with slicer_amd.Noise(slicer, n, SEED) as nz:
+            for count in (1, 2, 3, 5, 6, 7, 78, 79):
+                for off in (1, 0):  # on the 16-byte grid and off it; x itself starts one float in
+                    src = slicer.to_device(x[:count]) if off == 0 else None
+                    try:
+                        nz.run_at(d + 4 if src is None else src, 0, count, 0.3, 0, 0)
+                        got = nz.read()
+                    finally:
+                        if src is not None:
+                            slicer.free(src)
+                    assert got.shape == (count,) and got.tobytes() == want[:count].tobytes(), (count, off)
+                nz.run_at(None, 0, count, 0.3, 0, 0)
+                assert nz.read().tobytes() == want_pure[:count].tobytes(), count
     finally:
         slicer.free(d)
 

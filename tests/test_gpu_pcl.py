@@ -157,6 +157,37 @@ def test_dc_bin_is_kept():
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("n", [270, 1029])
+def test_mask_kernels_past_one_pixel_a_thread(n):
+    """k_pcl_moments is 256 workgroups of 256 threads, k_pcl_mask at most 4096: a thread takes a second pixel from n^2 >
+    65536 and n^2 > 2^20 on, and CASES stop at 128 (where three quarters of the moments' workgroups have no pixel).  270
+    and 1029 are the smallest sizes the transform takes past 256 and 1024; both leave the last round ragged."""
+    assert 256 * 256 < 270 * 270 < 2 * 256 * 256 and 4096 * 256 < 1029 * 1029 < 2 * 4096 * 256
+    N = float(n * n)
+    edges = np.array([0.0, 8.0, float(n // 2)])
+    with Session(False) as ss, slicer_amd.Pcl(ss.s, n, ANGLE, 1, edges=edges) as p:
+        user, width = MASKS["taper_holes"](n)
+        w_ref = pcl_np.mask(n, width, user)
+        set_mask(ss, p, user, width)
+        assert np.array_equal(p.mask().view(np.uint32), w_ref.view(np.uint32))
+        cp, w64 = p.coupling(), w_ref.astype(np.float64)
+        # the moments: the bound of test_coupling_matrix
+        assert abs(cp["mean_w"] - w64.mean()) <= 2 * N * 2.0 ** -53 * w64.mean()
+        assert abs(cp["mean_w2"] - (w64 ** 2).mean()) <= 2 * N * 2.0 ** -53 * (w64 ** 2).mean()
+        # zeros and ones: every partial sum is an integer, so a pixel dropped or taken twice changes the means exactly
+        user = binary(n)
+        set_mask(ss, p, user, 0.0)
+        assert np.array_equal(p.mask().view(np.uint32), user.view(np.uint32))
+        cp = p.coupling()
+        assert cp["mean_w"] == cp["mean_w2"] == float(user.sum(dtype=np.int64)) / N
+        # values that are not finite are counted in every round: a thread's second pixel, and the map's last one
+        bad = user.copy().ravel()
+        bad[[256 * 256 + 5, n * n - 1]] = np.nan, np.inf
+        code, text = _code(lambda: set_mask(ss, p, bad.reshape(n, n), 0.0))
+        assert code == 2 and "2 values that are not finite" in text
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("kind", sorted(MASKS))
 @pytest.mark.parametrize("n,split", CASES)
 def test_coupling_matrix(n, split, kind):

@@ -17,7 +17,10 @@ L = lensing._L
 ERR_ARG, ERR_STATE = 2, 3
 KEYS = ("pdf", "peaks", "minima", "below", "above", "nan")
 # no interior (1, 2), one interior pixel (3), tile seams at rows 16 / 32 and columns 64 / 128, both load paths
-# (4 | n or not), more tiles than workgroups (4096: 16384 tiles)
+# (4 | n or not), more tiles than workgroups (4096: 16384 tiles).  The grid is at most 8 workgroups a CU (6 at
+# B = 1024, whose LDS is 25700 B), 2048 and 1536 on 256 CUs, so the tile loop takes a second round from 2049 (1537) tiles
+# on: 4096 runs it eight to eleven times, on the float4 path with every tile full; 1425 (90 x 23 = 2070 tiles, the
+# smallest n past 2048) runs it twice on the scalar path with a short last tile row and column
 SMALL = [1, 2, 3, 4, 5, 15, 16, 17, 18, 33, 63, 64, 65, 66, 67, 68, 100, 129]
 KINDS = ("white", "lognormal", "integers")
 BINS = (1, 7, 64, 1024)
@@ -103,6 +106,7 @@ def test_counts_are_the_restatement(slicer, n):
     (1000, "white", 7, "log"), (1000, "lognormal", 1024, "uniform"), (1000, "integers", 64, "uniform"),
     (1023, "white", 1024, "log"), (1023, "lognormal", 1, "uniform"), (1023, "integers", 7, "uniform"),
     (1024, "white", 64, "uniform"), (1024, "lognormal", 7, "log"), (1024, "integers", 1024, "log"),
+    (1425, "white", 7, "log"), (1425, "lognormal", 1024, "uniform"),
     (4096, "white", 1024, "uniform"), (4096, "lognormal", 64, "log"), (4096, "integers", 1, "uniform"),
 ])
 def test_counts_of_large_maps_are_the_restatement(slicer, n, kind, B, spacing):

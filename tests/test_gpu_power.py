@@ -106,6 +106,11 @@ def check(s, maps, angle, edges, split):
     return cross
 
 
+# A bin is cut into slices of about kSliceModes = 8192 modes, whole rows |j0| = a, and a workgroup walks the rows of its
+# slice in chunks of 128.  Up to n = 100 a bin is one slice of one chunk.  1000 and 4096 have, with the default unit bins,
+# one slice of up to 501 and 2049 rows (4 and 17 chunks) and, with log_edges, up to 26 and 444 slices a bin; the unit
+# bins of 8505 and 16384 below have up to 2 and 4 slices of many chunks each.  The cap of a bin's slices at its rows
+# needs more than 8192 modes a row, n > 8192 with one bin over most of the plane: no test here reaches it.
 CASES = [(n, False) for n in (16, 30, 45, 49, 100, 1000, 4096)] + [(30, True), (45, True), (1024, True)]
 
 

@@ -19,9 +19,35 @@ ERR_ARG, ERR_STATE = 2, 3
 # n below the reach of every level; both sides of the tile seams of level_cfg: a tile is 128 columns (one span up to
 # d = 16, eight runs of 16 at stride d above) by two segments of at most 8 rows at stride d, so at step d the seams are
 # at columns 128 k (d <= 16) and 8 d k (d = 32: 256), and at rows 16 d k: 16, 32, 64, 96, 128, 256 for d = 1 ... 16; maps
-# with fewer than 16 rows per residue (n < 16 d) take shorter segments, n < d leaves residues empty
+# with fewer than 16 rows per residue (n < 16 d) take shorter segments, n < d leaves residues empty.
+# The dilated regime (d >= 32): a residue has ceil(n / d) rows and columns, a tile takes 16 and 8 of them, so a second row
+# block needs n > 16 d = 512 and the sizes here stay at one row block at d = 32.  (1024, 8) of the large maps has two, all
+# of them full.  DILATED has the ragged ones: 530 at d = 32 (17 a residue: a second row block of one row in residues
+# 0 ... 17 and of none in 18 ... 31, three column blocks, the last of one column), 1031 at d = 32 (33: three row blocks,
+# five column blocks) and at d = 64 (17, the extra row and column in residues 0 ... 6)
 SIZES = [1, 2, 3, 4, 5, 7, 8, 9, 15, 16, 17, 31, 32, 33, 63, 64, 65, 95, 96, 97, 100, 127, 128, 129, 130, 255, 256, 257, 260]
 SCALES = (1, 3, 6)
+DILATED = [(530, 6), (1031, 7)]
+
+
+def level_counts(n, j):
+    """level_cfg of slicer_amd/csrc/slicer_starlet.hip at level j (d = 2^j) of an n x n map: the rows of a residue at
+    most, the rows of a segment, and the tiles as row blocks x column residue runs x column blocks a row residue."""
+    d, run_log2 = 1 << j, min(j, 4)
+    tc, run = 128 >> run_log2, 1 << run_log2
+    per_residue = (n + d - 1) // d
+    seg = max(1, min(8, (per_residue + 1) // 2))
+    return {"per_residue": per_residue, "seg": seg, "kblocks_r": (per_residue + 2 * seg - 1) // (2 * seg),
+            "resblocks_c": (min(d, n) + run - 1) // run, "kblocks_c": (per_residue + tc - 1) // tc}
+
+
+# what the comment above claims (no device needed)
+assert all(level_counts(n, 5)["kblocks_r"] == 1 for n in SIZES) and level_counts(512, 5)["kblocks_r"] == 1
+assert level_counts(1024, 5) == {"per_residue": 32, "seg": 8, "kblocks_r": 2, "resblocks_c": 2, "kblocks_c": 4}
+assert level_counts(530, 5) == {"per_residue": 17, "seg": 8, "kblocks_r": 2, "resblocks_c": 2, "kblocks_c": 3}
+assert level_counts(1031, 5) == {"per_residue": 33, "seg": 8, "kblocks_r": 3, "resblocks_c": 2, "kblocks_c": 5}
+assert level_counts(1031, 6) == {"per_residue": 17, "seg": 8, "kblocks_r": 2, "resblocks_c": 4, "kblocks_c": 3}
+assert 530 % 32 == 18 and 1031 % 32 == 7 and 1031 % 64 == 7  # the residues below these hold the extra row and column
 
 
 @pytest.fixture(scope="module")
@@ -99,6 +125,22 @@ def test_large_maps_are_the_restatement(slicer, n, scales):
     assert (np.abs(total - x.astype(np.float64)) <= bound).all()
 
 
+@pytest.mark.parametrize("n,scales", DILATED)
+def test_dilated_tiles_past_one_block_on_ragged_maps(slicer, n, scales):
+    """At d >= 32 blockIdx.x decodes into (column block, column residue run, row block, row residue) with more than one
+    row block and more than one column block, and n mod d != 0 leaves the last of each ragged: one row (column) in the
+    low residues, none in the others, where `row >= n` and `col >= n` cut the tile short."""
+    for j in range(5, scales):
+        c = level_counts(n, j)
+        assert c["kblocks_r"] >= 2 and c["kblocks_c"] >= 2 and c["resblocks_c"] >= 2 and n % (1 << j) != 0, (j, c)
+        assert (c["per_residue"] - 1) % (2 * c["seg"]) == 0  # the last row block holds one row
+    for kind in ("white", "lognormal"):
+        x = make_map(n, kind)
+        ref = W.starlet(x, scales)
+        for off_grid in (False, True):
+            check(slicer, x, scales, off_grid, ref)
+
+
 @pytest.mark.parametrize("n", [5, 130])
 def test_a_constant_map_is_its_own_coarse_map(slicer, n):
     for value in (3.25, 0.1, -1e30):
@@ -162,12 +204,10 @@ def test_runs_repeat_and_carry_nothing_over(slicer):
         slicer.free(dy)
 
 
-@pytest.mark.parametrize("value", [np.nan, np.inf])
-def test_a_non_finite_pixel_reaches_exactly_its_support(slicer, value):
-    n, scales = 150, 5
+def reach_of_one_pixel(slicer, n, scales, pixels, value):
     clean = make_map(n)
     before = run(slicer, clean, scales)
-    for at in ((0, 0), (31, 128), (32, 127), (149, 64), (75, 75)):  # corners, both sides of a tile seam, the middle
+    for at in pixels:
         x = clean.copy()
         x[at] = value
         got = check(slicer, x, scales)
@@ -177,6 +217,19 @@ def test_a_non_finite_pixel_reaches_exactly_its_support(slicer, value):
             assert got[j][~reach[j]].tobytes() == before[j][~reach[j]].tobytes()  # every other output keeps its bits
             if value != value:
                 assert np.isnan(got[j][reach[j]]).all()
+
+
+@pytest.mark.parametrize("value", [np.nan, np.inf])
+def test_a_non_finite_pixel_reaches_exactly_its_support(slicer, value):
+    # corners, both sides of a tile seam, the middle
+    reach_of_one_pixel(slicer, 150, 5, ((0, 0), (31, 128), (32, 127), (149, 64), (75, 75)), value)
+
+
+@pytest.mark.parametrize("value", [np.nan, np.inf])
+def test_a_non_finite_pixel_reaches_exactly_its_support_in_ragged_dilated_tiles(slicer, value):
+    # n = 530 at d = 32 (DILATED): row 528 = 16 + 16 d is the one row of residue 16's second row block, column 529 =
+    # 17 + 16 d the one column of residue 17's third column block, (529, 529) both at once, in the corner
+    reach_of_one_pixel(slicer, 530, 6, ((528, 300), (17, 529), (529, 529)), value)
 
 
 def test_run_kappa_and_a_second_handle_on_a_scale(slicer):
