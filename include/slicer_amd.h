@@ -928,6 +928,81 @@ int slicer_pcl_spectrum(slicer_pcl_handle ph, int32_t map, double *host);
 int slicer_pcl_read(slicer_pcl_handle ph, double *cl, double *coupled, double *ell_mean, int64_t *counts);
 int slicer_pcl_destroy(slicer_pcl_handle ph);
 
+/* ---- Real-space two-point correlation functions xi_kk(theta), xi+(theta), xi-(theta) ----
+ * Fields and weights.  A spin-0 field is one f32 map a; a spin-2 field is two, (a1, a2) = (gamma1, gamma2).  Every map is
+ * n^2 = npix^2 pixels, row-major, axis 0 slow and component 1 (row N6's convention), 2 <= npix <= 16383, and is only read.
+ * A field value that is not finite is the caller's, as in row N7.  One optional f32 weight map w is shared by all fields
+ * (NULL: w = 1); it must be finite and >= 0.  The working fields are a~ = a * w, the product of the two f32 values taken
+ * in f64, which is exact (row N17 takes an f32 product instead).
+ * Pairs.  For a lag r = (dx, dy) != 0 along (axis 0, axis 1), |dx|, |dy| <= n - 1: C_ab(r) = sum over x of a~(x) b~(x + r),
+ * over the x for which both pixels lie inside the map.  Nothing wraps.  W(r) = sum over x of w(x) w(x + r), and
+ * N(r) = (n - |dx|) (n - |dy|): ordered pairs, a bin sums both signs of r.
+ * Bins.  Edges in pixels, f64, finite, 0 <= r_0 < ... < r_B <= sqrt(2) (n - 1) (the f64 product of sqrt(2.0) and n - 1),
+ * 1 <= B <= SLICER_XI_MAX_BINS.  A lag is in bin b iff RN64(r_b^2) <= m2 < RN64(r_{b+1}^2) on the exact integer
+ * m2 = dx^2 + dy^2; the last bin is closed on the right (row N7's rule); m2 = 0 is in no bin.  L = min(ceil(r_B), n - 1) is
+ * the largest |dx| or |dy| that can occur.
+ * Per bin, with M_b the number of its lags:  counts = N_b = sum N(r), int64, exact, independent of w;  W_b = sum W(r) in
+ * f64;  r_mean = sum W(r) sqrt(m2) / W_b.  With w = NULL, W(r) = N(r): W_b = (double)N_b and the radius sum come from the
+ * integers on the host (long double), no transform.
+ *   spin 0, fields a <= b   xi_ab = sum C_ab(r) / W_b  (auto: a = b only; cross: every pair, in row N7's pair order)
+ *   spin 2                  xi+ = sum (C_11 + C_22) / W_b,  xi- = sum [(C_11 - C_22) c4 + (C_12 + C_21) s4] / W_b,
+ *                           c4 = (dx^4 - 6 dx^2 dy^2 + dy^4) / m2^2, s4 = 4 dx dy (dx^2 - dy^2) / m2^2, from the integer lags
+ *                           in f64: xi+- = <gt gt> +- <gx gx> with gt + i gx = -gamma e^(-2 i phi), phi = atan2(dy, dx),
+ *                           the sign under which gt > 0 around a point mass with row N6's gamma.  For a cross pair the
+ *                           first index of each C is field a's component, the second field b's.
+ * A bin is empty when M_b = 0 or W_b <= 2^-30 sum w^2: its xi, xi- and r_mean are NaN, W_b and counts are still reported.
+ * (Under a 0/1 mask any bin with one real pair has W_b >= 1 > 2^-30 sum w^2 for n <= 8192; one without has pure round-off.)
+ * Route.  P = the smallest size >= n + L with prime factors 2, 3, 5, 7 only (slicer_shear_supported); none up to 16384:
+ * SLICER_ERR_UNSUPPORTED.  n itself need not be such a size.  (1) each map is zero-padded to P^2 in f64 and transformed as
+ * the f64 product with the padded weights (the r2c transform of row N6, under the shear_split option of h at create);
+ * (2) one pointwise kernel forms the real spectrum: Re(conj fa fb) (spin 0, and |what|^2 for the weights),
+ * Re(conj f1a f1b + conj f2a f2b) (xi+), the same with a minus sign and Re(conj f1a f2b + conj f2a f1b) (xi-);
+ * (3) each spectrum is inverted in f64, every mode kept; a lag (dx, dy) sits at (dx mod P, dy mod P), and since
+ * P >= n + L no lag <= L aliases; (4) the binning kernel walks the FULL window |dx|, |dy| <= L, both signs of both lags
+ * (nothing is doubled), applies c4 and s4, and reduces per bin without floating-point atomics: per-workgroup partials in a
+ * fixed tree, summed in a fixed order.  The same inputs give the same bits.  Every spectrum is real, so each inverse is the
+ * part of its correlation that is even in r: for a cross pair slicer_xi_correlation returns (C_ab(r) + C_ab(-r)) / 2
+ * where C_ab itself is not even; the bins, which hold both signs, do not see the difference.
+ * Out of scope: kappa-gamma_t (galaxy-galaxy lensing) and the parity-odd xi_x, per-field weights, shear shape noise, COSEBIs
+ * and band powers from xi, the curved sky, lags beyond P = 16384.
+ *   slicer_xi_bins         host only: counts N_b and lags M_b [B] by enumeration, and P (any of them NULL).  Refusals as
+ *                          slicer_xi_create's of npix and the edges (message through slicer_last_error(NULL))
+ *   slicer_xi_create       on the device and stream of h.  spin: 0 or 2 (others: SLICER_ERR_ARG); 1 <= n_fields <= 32 (below:
+ *                          SLICER_ERR_ARG, above: SLICER_ERR_UNSUPPORTED); cross: 0 or 1 (SLICER_ERR_ARG).  npix < 2, edges that
+ *                          are NULL, fewer than 2, not finite, negative, not strictly ascending or beyond sqrt(2) (npix - 1):
+ *                          SLICER_ERR_ARG; npix > 16383, more than SLICER_XI_MAX_BINS bins, no P: SLICER_ERR_UNSUPPORTED.
+ *                          Device memory: the plan of P, 24 P^2 bytes, 16 P (P/2+1) bytes for one spectrum and as much per
+ *                          kept field component (all of them with cross, one field's without), two windows of 8 (2L+1)^2
+ *                          (SLICER_ERR_NOMEM).  The handle starts with w = NULL
+ *   slicer_xi_set_weights  a device f32 npix^2 map, or NULL.  Checks the values on the device, computes W(r), W_b and the
+ *                          radius sums once, and waits for the stream.  A value that is negative or not finite:
+ *                          SLICER_ERR_ARG, and the handle then refuses to run (SLICER_ERR_STATE) until weights are accepted.
+ *                          New weights invalidate the last run
+ *   slicer_xi_run          n_fields (spin 0) or 2 n_fields (spin 2: gamma1, gamma2 of field 0, then of field 1, ...) device
+ *                          f32 maps; enqueued, no synchronisation.  A NULL map: SLICER_ERR_ARG
+ *   slicer_xi_read         xi (spin 2: xi+) and xim (xi-; NULL for spin 0, else SLICER_ERR_ARG) [pairs][B] in the pair order
+ *                          of slicer_power_create, r_mean, weights (W_b) and counts [B] (any of them NULL); waits for the
+ *                          stream.  Before a run: SLICER_ERR_STATE
+ *   slicer_xi_correlation  the (2L+1)^2 f64 lag window of one inverse of pair `pair` of the last run, [dx + L][dy + L]:
+ *                          which = SLICER_XI_PLUS (C_ab of spin 0; C_11 + C_22), SLICER_XI_MINUS (C_11 - C_22) or
+ *                          SLICER_XI_CROSS (C_12 + C_21), the latter two for spin 2 only; recomputed from the kept
+ *                          transforms (auto mode keeps only the last field's: SLICER_ERR_STATE for the others).
+ *                          SLICER_XI_WEIGHTS: W(r) of the weights in use, whatever `pair`, also before a run */
+typedef struct slicer_xi_s *slicer_xi_handle;
+#define SLICER_XI_MAX_BINS 512
+#define SLICER_XI_PLUS 0
+#define SLICER_XI_MINUS 1
+#define SLICER_XI_CROSS 2
+#define SLICER_XI_WEIGHTS 3
+int slicer_xi_bins(int32_t npix, int32_t n_edges, const double *edges, int64_t *counts, int64_t *lags, int32_t *padded);
+int slicer_xi_create(slicer_handle h, int32_t npix, int32_t spin, int32_t n_fields, int32_t cross, int32_t n_edges,
+                     const double *edges, slicer_xi_handle *out);
+int slicer_xi_set_weights(slicer_xi_handle xh, const float *d_w);
+int slicer_xi_run(slicer_xi_handle xh, const float *const *d_maps);
+int slicer_xi_read(slicer_xi_handle xh, double *xi, double *xim, double *r_mean, double *weights, int64_t *counts);
+int slicer_xi_correlation(slicer_xi_handle xh, int32_t pair, int32_t which, double *host);
+int slicer_xi_destroy(slicer_xi_handle xh);
+
 /* per-kernel HIP-event timing (off by default; adds two event records per launch) */
 int slicer_profile_enable(slicer_handle h, int on);
 int slicer_profile_reset(slicer_handle h);

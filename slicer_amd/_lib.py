@@ -172,6 +172,14 @@ SYMBOLS = {
     "slicer_pcl_spectrum": (C.c_int, [_H, C.c_int32, C.c_void_p]),
     "slicer_pcl_read": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "slicer_pcl_destroy": (C.c_int, [_H]),
+    "slicer_xi_bins": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
+    "slicer_xi_create": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                   C.POINTER(C.c_void_p)]),
+    "slicer_xi_set_weights": (C.c_int, [_H, C.c_void_p]),
+    "slicer_xi_run": (C.c_int, [_H, C.POINTER(C.c_void_p)]),
+    "slicer_xi_read": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "slicer_xi_correlation": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p]),
+    "slicer_xi_destroy": (C.c_int, [_H]),
     "slicer_rays_create": (C.c_int, [_H, C.c_int32, C.c_double, C.POINTER(C.c_void_p)]),
     "slicer_rays_reset": (C.c_int, [_H]),
     "slicer_rays_step": (C.c_int, [_H, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

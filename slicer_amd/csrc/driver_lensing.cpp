@@ -22,6 +22,14 @@
 //     masked pseudo-C_l of the kappa maps, the layout of the .cl_ file with '#' lines for the mask (mean_w, mean_w2,
 //     taper_arcmin, taper_pix, mask) and per pair the decoupled bandpower C_s_t followed by the coupled one Ct_s_t; and
 //     .pclm_<npix>_<suffix>.txt, the mode-coupling matrix M, one row per line.
+//   * --xi auto|cross with --xi-edges a0,a1,... (required; at most 513 edges in arcminutes, one arcminute being
+//     npix / (60 ANGLE) pixels) and optionally --xi-mask FILE.fits (an image of the maps' size, BITPIX -32 or -64, finite
+//     and >= 0: the weight map shared by all maps): <directory><simulation>.xi_<npix>_<suffix>.txt, the real-space
+//     two-point functions xi_kk of the kappa maps (auto, or every pair with cross): '#' lines (npix, angle, the source
+//     redshifts, mask, the padded size P, the column names), then per bin r_lo r_hi r_mean (arcminutes), xi of every
+//     pair, the pair weight W_b and the pair count N_b; nan marks an empty bin.  With --shear also .xipm_<npix>_<suffix>
+//     .txt, xi+ and xi- of every source's (gamma1, gamma2) as they are written, auto only.  The maps do not wrap, and
+//     the mask is divided out exactly.  Refused for physical runs.
 //   * --moments: <directory><simulation>.moments_<npix>_<suffix>.txt, the raw central power sums S_2 ... S_8 and the
 //     mean of every kappa map and of --moments-levels L (default 0) successive 2x2 block means of it, about each level's
 //     own mean (Lens/moment.py and Lens/halve.py).
@@ -184,6 +192,14 @@ int LensingOptions::parse(int argc, char **argv, int &i)
             return bad("bad --pcl-taper (the width of the border taper in arcminutes, positive)");
         pcl_taper_given = true;
     } else if (a == "--pcl-mask" && has_value) pcl_mask = argv[++i];
+    else if (a == "--xi" && has_value) xi = argv[++i];
+    else if (a == "--xi-edges" && has_value) {
+        if (!parse_doubles(argv[++i], xi_edges))
+            return bad("bad --xi-edges (a comma-separated list of radii in arcminutes)");
+        if (xi_edges.size() > SLICER_XI_MAX_BINS + 1)
+            return bad("bad --xi-edges (" + std::to_string(xi_edges.size()) + " edges, at most " +
+                       std::to_string(SLICER_XI_MAX_BINS + 1) + ")");
+    } else if (a == "--xi-mask" && has_value) xi_mask = argv[++i];
     else if (a == "--bispectrum" && has_value) bispectrum = argv[++i];
     else if (a == "--bispectrum-edges" && has_value) {
         if (!parse_doubles(argv[++i], bispectrum_edges))
@@ -265,7 +281,7 @@ int LensingOptions::parse(int argc, char **argv, int &i)
 int LensingOptions::check() const
 {
     const bool no_kappa = kappa.empty(), derivative = !shear_derivative.empty(), pw = !power.empty();
-    const bool bs = !bispectrum.empty(), pc = !pcl.empty();
+    const bool bs = !bispectrum.empty(), pc = !pcl.empty(), x = !xi.empty();
     const std::pair<bool, const char *> rules[] = {
         {shear && no_kappa, "--shear needs --kappa (the shear maps are computed from the kappa maps)"},
         {raytrace && no_kappa, "--raytrace needs --kappa (the rays are observed at the source redshifts of the kappa maps)"},
@@ -282,6 +298,11 @@ int LensingOptions::check() const
         {!pcl_mask.empty() && !pc, "--pcl-mask needs --pcl"},
         {pc && pcl_edges.empty(), "--pcl needs --pcl-edges (the bin edges in units of l_f)"},
         {pc && !pcl_taper_given && pcl_mask.empty(), "--pcl needs --pcl-taper or --pcl-mask (or both)"},
+        {x && xi != "auto" && xi != "cross", "bad --xi (auto or cross)"},
+        {x && no_kappa, "--xi needs --kappa (the correlation functions are those of the kappa maps)"},
+        {!xi_edges.empty() && !x, "--xi-edges needs --xi"},
+        {!xi_mask.empty() && !x, "--xi-mask needs --xi"},
+        {x && xi_edges.empty(), "--xi needs --xi-edges (the bin edges in arcminutes)"},
         {bs && bispectrum != "all" && bispectrum != "equilateral", "bad --bispectrum (all or equilateral)"},
         {bs && no_kappa, "--bispectrum needs --kappa (the bispectra are those of the kappa maps)"},
         {!bispectrum_edges.empty() && !bs, "--bispectrum-edges needs --bispectrum"},
@@ -336,6 +357,17 @@ int LensingOptions::check_npix(const InputParams &p) const
         const string why = pcl_mask.empty() ? "" : fits_read_mask(pcl_mask, p.npix, w.data());
         if (!why.empty())
             return bad("--pcl-mask: " + why);
+    }
+    if (!xi.empty()) {  // the edges, the mask file
+        if (p.physical)
+            return bad("--xi-edges: the edges are angles, and the maps of a physical run have none");
+        const vector<double> e = xi_edges_pix(p.npix, p.fov);
+        if (slicer_xi_bins(p.npix, (int)e.size(), e.data(), nullptr, nullptr, nullptr) != SLICER_OK)
+            return bad(string("--xi-edges: ") + slicer_last_error(nullptr));
+        vector<float> w((size_t)p.npix * (size_t)p.npix);
+        const string why = xi_mask.empty() ? "" : fits_read_mask(xi_mask, p.npix, w.data());
+        if (!why.empty())
+            return bad("--xi-mask: " + why);
     }
     if (!bispectrum.empty() && !slicer_shear_supported(p.npix))
         return bad("--bispectrum: " + npix + fft_sizes);
@@ -431,6 +463,27 @@ int LensingOutputs::create()
     if (!o.pcl.empty() && slicer_pcl_create(h, p.npix, p.fov, (int)zs.size(), o.pcl == "cross", (int)o.pcl_edges.size(),
                                             o.pcl_edges.data(), pclh.out()) != SLICER_OK)
         return fail(h, "slicer_amd: --pcl");
+    if (!o.xi.empty()) {
+        const char *who = "slicer_amd: --xi";
+        const vector<double> e = o.xi_edges_pix(p.npix, p.fov);
+        if (slicer_xi_create(h, p.npix, 0, (int)zs.size(), o.xi == "cross", (int)e.size(), e.data(), xih.out()) != SLICER_OK ||
+            (o.shear && slicer_xi_create(h, p.npix, 2, 1, 0, (int)e.size(), e.data(), xipmh.out()) != SLICER_OK))
+            return fail(h, who);
+        if (!o.xi_mask.empty()) {
+            vector<float> w(map.size());
+            DeviceMaps mask(h);
+            const string why = fits_read_mask(o.xi_mask, p.npix, w.data());
+            if (!why.empty()) {
+                cerr << who << "-mask: " << why << endl;
+                return 1;
+            }
+            // (slicer_xi_set_weights waits for the stream: neither copy of the mask is read after it returns)
+            if (!mask.add(p.npix) || slicer_copy_to_device(h, mask.maps[0], w.data(), w.size() * sizeof(float)) != SLICER_OK ||
+                slicer_xi_set_weights(xih, mask.maps[0]) != SLICER_OK ||
+                (xipmh && slicer_xi_set_weights(xipmh, mask.maps[0]) != SLICER_OK))
+                return fail(h, who);
+        }
+    }
     if (o.moments && slicer_moments_create(h, p.npix, o.moments_levels, SLICER_HALVE_MEAN, mh.out()) != SLICER_OK)
         return fail(h, "slicer_amd: --moments");
     if (!o.peaks_edges.empty() &&
@@ -631,6 +684,8 @@ int LensingOutputs::write()
     if (const int rc = ph ? power_spectra() : 0)
         return rc;
     if (const int rc = pclh ? pseudo_spectra() : 0)
+        return rc;
+    if (const int rc = xih ? correlations() : 0)
         return rc;
     if (const int rc = bsh ? bispectra() : 0)
         return rc;
@@ -959,6 +1014,17 @@ int LensingOutputs::source_shear(size_t s, const float *d_kappa)
         if (slicer_shear_read(shh, g ? fd[k] : spectral[k], map.data()) != SLICER_OK ||
             !save(k < 4 ? "shear" : "deflection", token[k], s))
             return fail(h, "slicer_amd: --kappa");
+    if (xipmh) {  // xi+ and xi- of the gammas just written
+        const int B = (int)o.xi_edges.size() - 1;
+        float *g12[2] = {nullptr, nullptr};
+        xipm_rows.resize((s + 1) * 2 * (size_t)B);
+        double *row = &xipm_rows[s * 2 * (size_t)B];
+        if (slicer_shear_device_map(shh, g ? fd[0] : spectral[0], &g12[0]) != SLICER_OK ||
+            slicer_shear_device_map(shh, g ? fd[1] : spectral[1], &g12[1]) != SLICER_OK ||
+            slicer_xi_run(xipmh, g12) != SLICER_OK ||
+            slicer_xi_read(xipmh, row, row + B, nullptr, nullptr, nullptr) != SLICER_OK)
+            return fail(h, "slicer_amd: --xi");
+    }
     return 0;
 }
 
@@ -1065,6 +1131,63 @@ int LensingOutputs::pseudo_spectra()
         for (int k = 0; k < B; k++)
             add(m, k + 1 < B ? "%.17g " : "%.17g\n", M[(size_t)b * B + k]);
     return write_table("mode-coupling matrix", ".pclm_", m);
+}
+
+// --xi.  Both tables: '#' lines (npix, angle, source redshifts, mask: the file as given or "none", padded: P, the column
+// names), then per bin r_lo r_hi r_mean in arcminutes, the xi columns, W_b and N_b (%.17g; nan for an empty bin).  The
+// .xi_ table has xi_s_t of every pair of kappa maps, the .xipm_ table (with --shear) xip_s xim_s of every source.
+int LensingOutputs::correlations()
+{
+    const char *who = "slicer_amd: --xi";
+    const int S = (int)plan.zs.size(), B = (int)o.xi_edges.size() - 1;
+    const bool cross = o.xi == "cross";
+    const size_t n_pairs = cross ? (size_t)S * (S + 1) / 2 : S;
+    const vector<double> e = o.xi_edges_pix(p.npix, p.fov);
+    int32_t P = 0;
+    vector<float *> maps(S);
+    for (int s = 0; s < S; s++)
+        if (slicer_kappa_device_map(kh, s, &maps[s]) != SLICER_OK)
+            return fail(h, who);
+    vector<double> c(n_pairs * B), r(B), W(B);
+    vector<int64_t> counts(B);
+    if (slicer_xi_bins(p.npix, B + 1, e.data(), nullptr, nullptr, &P) != SLICER_OK)
+        return fail(nullptr, who);
+    if (slicer_xi_run(xih, maps.data()) != SLICER_OK ||
+        slicer_xi_read(xih, c.data(), nullptr, r.data(), W.data(), counts.data()) != SLICER_OK)
+        return fail(h, who);
+    const double arcmin = 60.0 * p.fov / p.npix;  // of one pixel
+    string head;
+    add(head, "# npix %d\n# angle_deg %.17g\n# zs", p.npix, p.fov);
+    for (double z : plan.zs)
+        add(head, " %.17g", z);
+    head += "\n# mask " + (o.xi_mask.empty() ? string("none") : o.xi_mask);
+    add(head, "\n# padded %d\n# r_lo r_hi r_mean", (int)P);
+    for (const bool pm : {false, true}) {
+        if (pm && !xipmh)
+            break;
+        string t = head;
+        for (int s = 0; s < S; s++)
+            if (pm)
+                add(t, " xip_%d xim_%d", s, s);
+            else
+                for (int u = s; u < (cross ? S : s + 1); u++)
+                    add(t, " xi_%d_%d", s, u);
+        t += " weight n_pairs\n";
+        for (int b = 0; b < B; b++) {
+            add(t, "%.17g %.17g %.17g", o.xi_edges[b], o.xi_edges[b + 1], r[b] * arcmin);
+            if (pm)
+                for (int s = 0; s < S; s++)
+                    add(t, " %.17g %.17g", xipm_rows[((size_t)s * 2) * B + b], xipm_rows[((size_t)s * 2 + 1) * B + b]);
+            else
+                for (size_t q = 0; q < n_pairs; q++)
+                    add(t, " %.17g", c[q * B + b]);
+            add(t, " %.17g %lld\n", W[b], (long long)counts[b]);
+        }
+        if (const int rc = pm ? write_table("shear correlation functions", ".xipm_", t)
+                              : write_table("correlation functions", ".xi_", t))
+            return rc;
+    }
+    return 0;
 }
 
 // The bispectra table: '#' lines (npix, angle, source redshifts, the bin edges in multipoles, column names), then per

@@ -1,5 +1,5 @@
 // driver_lensing.hpp -- the lensing outputs of the SLICER_amd driver (slicer_main.cpp): their options, their host
-// planning and the device-0 work behind --kappa, --shear, --deflection, --raytrace, --power, --pcl, --moments, --peaks,
+// planning and the device-0 work behind --kappa, --shear, --deflection, --raytrace, --power, --pcl, --xi, --moments, --peaks,
 // --minkowski, --bispectrum, --smooth, --shape-noise and --starlet (driver_lensing.cpp describes the options), with the small helpers the rest of the driver shares with them.
 #pragma once
 #include <deque>
@@ -25,6 +25,9 @@ struct LensingOptions {
     bool pcl_taper_given = false;
     double pcl_taper_arcmin = 0.0;    // --pcl-taper: the width of the border taper, 0 without it
     std::string pcl_mask;             // --pcl-mask: a FITS image of the map's size, "" without it
+    std::string xi;                   // "" (no --xi), "auto" or "cross"
+    std::vector<double> xi_edges;     // --xi-edges in arcminutes, required with it: at most 513
+    std::string xi_mask;              // --xi-mask: a FITS image of the map's size, "" without it
     bool moments = false, moments_levels_given = false;
     int moments_levels = 0;
     std::vector<double> peaks_edges;  // empty: no --peaks
@@ -44,6 +47,14 @@ struct LensingOptions {
     int n_power_edges(int npix) const { return power_edges.empty() ? npix : (int)power_edges.size(); }
     const double *power_edges_or_null() const { return power_edges.empty() ? nullptr : power_edges.data(); }
     double pcl_taper_pix(int npix, double angle_deg) const { return pcl_taper_arcmin * npix / (60.0 * angle_deg); }
+    // --xi-edges in pixels of a map of npix pixels and angle_deg degrees a side
+    std::vector<double> xi_edges_pix(int npix, double angle_deg) const
+    {
+        std::vector<double> e(xi_edges);
+        for (double &v : e)
+            v = v * npix / (60.0 * angle_deg);
+        return e;
+    }
     // scale k of --smooth in pixels of a map of npix pixels and angle_deg degrees a side
     double smooth_sigma_pix(size_t k, int npix, double angle_deg) const { return smooth_arcmin[k] * npix / (60.0 * angle_deg); }
 
@@ -109,6 +120,10 @@ struct LensingOutputs {
     Owned<slicer_shear_handle, slicer_shear_destroy> shh{};  // --shear and --raytrace
     Owned<slicer_power_handle, slicer_power_destroy> ph{};
     Owned<slicer_pcl_handle, slicer_pcl_destroy> pclh{};  // --pcl
+    // --xi: the kappa maps' handle (spin 0, every source a field) and with --shear a spin-2 one of one field, run as
+    // each source's shear is made; the rows of the .xipm_ table, [source][bin] of (xi+, xi-)
+    Owned<slicer_xi_handle, slicer_xi_destroy> xih{}, xipmh{};
+    std::vector<double> xipm_rows{};
     Owned<slicer_moments_handle, slicer_moments_destroy> mh{};
     Owned<slicer_peaks_handle, slicer_peaks_destroy> pkh{};
     Owned<slicer_minkowski_handle, slicer_minkowski_destroy> mkh{};
@@ -190,6 +205,7 @@ private:
     int source_shear(size_t s, const float *d_kappa);
     int power_spectra();
     int pseudo_spectra();
+    int correlations();
     int bispectra();
     int write_table(const char *what, const char *token, const std::string &text) const;
 };

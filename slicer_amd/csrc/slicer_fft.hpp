@@ -1,11 +1,13 @@
 // slicer_fft.hpp -- internal (not exported): the forward f64 r2c transform of slicer_shear.hip, shared by the shear
-// handle, the power-spectrum handle (row N7), the bispectrum handle (row N15) and the pseudo-C_l
-// handle (row N17).  One plan per map size and shear_split value:
+// handle, the power-spectrum handle (row N7), the bispectrum handle (row N15), the pseudo-C_l
+// handle (row N17) and the correlation-function handle (row N18).  One plan per map size and shear_split value:
 // the twiddles, the row and column pass chains, and the buffers the forward passes go through.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cmath>
 #include <vector>
 
 #include "../../include/slicer_amd.h"
@@ -49,3 +51,25 @@ SLICER_FFT_INTERNAL int slicer_power_bin_real(slicer_power_handle ph, hipStream_
 // The bin edges of slicer_power_bins into `out`, or 0 .. npix-1 for NULL (then n_edges must be npix); "" if they are
 // usable, else why not (slicer_power.hip).
 SLICER_FFT_INTERNAL const char *check_edges(int npix, int n_edges, const double *edges, std::vector<double> &out);
+// Smallest j in [0, cap] with a2 + j^2 >= e2 (strict: > e2), cap if none.  a2 + j^2 is an integer below 2^53, so the
+// comparisons are exact; the square root only gives the starting point.
+__host__ __device__ inline int first_at_least(double a2, double e2, bool strict, int cap)
+{
+    const double t = e2 - a2;
+    int j;
+    if (!(t > 0.0))
+        j = 0;
+    else if (t >= (double)cap * (double)cap)
+        j = cap;
+    else
+        j = std::min(cap, (int)ceil(sqrt(t)));
+    auto ok = [&](int x) {
+        const double m = a2 + (double)x * (double)x;
+        return strict ? m > e2 : m >= e2;
+    };
+    while (j > 0 && ok(j - 1))
+        j--;
+    while (j < cap && !ok(j))
+        j++;
+    return j;
+}

@@ -36,29 +36,6 @@ constexpr int kRowsPerChunk = kBinThreads / 2;  // two runs (+a, -a) per row val
 constexpr int kBlock = 8;                       // sources per block in cross mode
 constexpr int64_t kSliceModes = 8192;          // target modes per workgroup slice of a bin
 
-// Smallest j in [0, cap] with a2 + j^2 >= e2 (strict: > e2), cap if none.  a2 + j^2 is an integer below 2^53, so the
-// comparisons are exact; the square root only gives the starting point.
-__host__ __device__ inline int first_at_least(double a2, double e2, bool strict, int cap)
-{
-    const double t = e2 - a2;
-    int j;
-    if (!(t > 0.0))
-        j = 0;
-    else if (t >= (double)cap * (double)cap)
-        j = cap;
-    else
-        j = std::min(cap, (int)ceil(sqrt(t)));
-    auto ok = [&](int x) {
-        const double m = a2 + (double)x * (double)x;
-        return strict ? m > e2 : m >= e2;
-    };
-    while (j > 0 && ok(j - 1))
-        j--;
-    while (j < cap && !ok(j))
-        j++;
-    return j;
-}
-
 // Rows of |j0| = a: +a (i0 = a) exists for a <= (n-1)/2, -a (i0 = n - a) for 1 <= a <= n/2.
 __host__ __device__ inline bool row_exists(int n, int a, int neg) { return neg ? a >= 1 && a <= n / 2 : a <= (n - 1) / 2; }
 

@@ -6,7 +6,8 @@ multi-plane ray tracing through the lens planes (row N11), and Gaussian and aper
 and shape noise for such maps from a counter-based generator (row N13), and the Minkowski functionals of such maps'
 excursion sets as exact counts (row N14), and the binned bispectra of such maps (row N15), and the starlet transform of
 such maps with the binned absolute sums of its scales, the starlet l1-norm (row N16), and the masked pseudo-C_l of such
-maps: coupled bandpowers, the mask's mode-coupling matrix and the decoupled bandpowers (row N17).
+maps: coupled bandpowers, the mask's mode-coupling matrix and the decoupled bandpowers (row N17), and the real-space
+two-point correlation functions xi_kk, xi+ and xi- of such maps and of shear maps (row N18).
 
 plane_weights wraps the host weights of include/slicer_amd.h (slicer_lensing_weights); Kappa is the device accumulator
 (slicer_kappa_*) bound to a Slicer handle: it reads the finalized plane maps where they are, in HBM.  Shear (slicer_shear_*)
@@ -22,7 +23,8 @@ Minkowski (slicer_minkowski_*) counts the faces, edges and vertices of the pixel
 Bispectrum (slicer_bispectrum_*) contracts the band-filtered f64 maps of a map over a list of bin triples; Starlet
 (slicer_starlet_*) splits a map into wavelet scales that sum back to it, and L1Norm (slicer_l1norm_*) sums |x| of a map's
 pixels bin by bin over Peaks' edges; Pcl (slicer_pcl_*) is Power under a mask (a border taper, a user mask or both),
-with the coupling matrix of the mask and the bandpowers decoupled by it.
+with the coupling matrix of the mask and the bandpowers decoupled by it; Xi (slicer_xi_*) sums the pair products of
+zero-padded maps over annuli of the lag, divided by the pair weights of one shared weight map.
 """
 import ctypes as C
 import math
@@ -996,6 +998,95 @@ class Pcl(_SubHandle):
             return out
         return {"ell_lo": self.edges[:-1] * self.ell_f, "ell_hi": self.edges[1:] * self.ell_f, "ell": ell,
                 "counts": counts, "cl": square(flat), "coupled": square(cflat)}
+
+
+XI_MAX_BINS = 512
+XI_PLUS, XI_MINUS, XI_CROSS, XI_WEIGHTS = range(4)
+
+
+def xi_bins(npix, edges):
+    """Host only (no device): {"counts": N_b, "lags": M_b (int64 each), "padded": P} for edges in pixels, as
+    slicer_xi_bins enumerates them."""
+    e = np.ascontiguousarray(edges, np.float64).ravel()
+    B = max(e.size - 1, 0)
+    counts, lags = np.zeros(B, np.int64), np.zeros(B, np.int64)
+    P = C.c_int32()
+    _host_chk(_L.slicer_xi_bins(int(npix), e.size, _dptr(e), counts.ctypes.data, lags.ctypes.data, C.byref(P)))
+    return {"counts": counts, "lags": lags, "padded": P.value}
+
+
+class Xi(_SubHandle):
+    """Real-space two-point correlation functions of n_fields npix^2 fields under one shared weight map, on the device
+    of `slicer`, on its stream.  spin=0: xi_ab(theta) of maps; spin=2: xi+ and xi- of (gamma1,
+    gamma2) pairs.  cross=False: every field with itself; cross=True: every pair.  edges in pixels (required; at most
+    512 bins).  The maps are not periodic: nothing wraps, and any weight map is divided out exactly."""
+    _handle, _destroy = "_xh", "slicer_xi_destroy"
+
+    def __init__(self, slicer: Slicer, npix, spin, n_fields, edges, cross=False):
+        self._s = slicer
+        self.npix, self.spin, self.n_fields, self.cross = int(npix), int(spin), int(n_fields), bool(cross)
+        self.edges = np.ascontiguousarray(edges, np.float64).ravel().copy()
+        self.n_bins = self.edges.size - 1
+        self.n_pairs = self.n_fields * (self.n_fields + 1) // 2 if self.cross else self.n_fields
+        xh = C.c_void_p()
+        slicer._chk(_L.slicer_xi_create(slicer._h, self.npix, self.spin, self.n_fields, int(self.cross), self.edges.size,
+                                        _dptr(self.edges), C.byref(xh)))
+        self._xh = xh
+        self.max_lag = min(int(math.ceil(self.edges[-1])), self.npix - 1)
+
+    def set_weights(self, d_w=None):
+        """d_w: device address of an f32 npix^2 weight map (finite, >= 0), or None for w = 1.  Waits for the stream."""
+        self._s._chk(_L.slicer_xi_set_weights(self._xh, None if d_w is None else int(d_w)))
+
+    def run(self, ptrs):
+        """ptrs: device addresses of the f32 npix^2 maps: n_fields of them (spin 0), or gamma1, gamma2 of field 0, then
+        of field 1, ... (spin 2)."""
+        ptrs = [int(p) for p in ptrs]
+        want = self.n_fields * (2 if self.spin else 1)
+        if len(ptrs) != want:
+            raise ValueError(f"expected {want} maps, got {len(ptrs)}")
+        arr = (C.c_void_p * len(ptrs))(*ptrs)
+        self._s._chk(_L.slicer_xi_run(self._xh, arr))
+
+    def run_kappa(self, kappa: Kappa):
+        """Spin 0: the maps of every source of a Kappa accumulator, where they are."""
+        self.run([kappa.device_map(s) for s in range(kappa.n_sources)])
+
+    def read(self):
+        """dict: r_lo, r_hi (bin edges in pixels), r (the weighted mean lag), weights (W_b), counts (N_b), and xi (spin
+        2: xip and xim), each [F][F][B], symmetric (cross) or [F][B] (auto); NaN in empty bins."""
+        F, B = self.n_fields, self.n_bins
+        flat = np.empty((self.n_pairs, B), np.float64)
+        mflat = np.empty((self.n_pairs, B), np.float64) if self.spin else None
+        r, W = np.empty(B, np.float64), np.empty(B, np.float64)
+        counts = np.empty(B, np.int64)
+        self._s._chk(_L.slicer_xi_read(self._xh, flat.ctypes.data, _dptr(mflat), r.ctypes.data, W.ctypes.data,
+                                       counts.ctypes.data))
+
+        def square(x):
+            if not self.cross:
+                return x
+            out = np.empty((F, F, B), np.float64)
+            p = 0
+            for s in range(F):
+                for t in range(s, F):
+                    out[s, t] = out[t, s] = x[p]
+                    p += 1
+            return out
+        out = {"r_lo": self.edges[:-1].copy(), "r_hi": self.edges[1:].copy(), "r": r, "weights": W, "counts": counts}
+        if self.spin:
+            out["xip"], out["xim"] = square(flat), square(mflat)
+        else:
+            out["xi"] = square(flat)
+        return out
+
+    def correlation(self, pair=0, which=XI_PLUS):
+        """The lag window of one inverse of pair `pair` (pair-major, as read's flat order) of the last run, f64
+        [2L+1, 2L+1] indexed [dx + L, dy + L]: XI_PLUS, XI_MINUS, XI_CROSS, or XI_WEIGHTS for W(r)."""
+        W = 2 * self.max_lag + 1
+        out = np.empty((W, W), np.float64)
+        self._s._chk(_L.slicer_xi_correlation(self._xh, int(pair), int(which), out.ctypes.data))
+        return out
 
 
 RAYS_KAPPA, RAYS_GAMMA1, RAYS_GAMMA2, RAYS_OMEGA, RAYS_DEFLECTION1, RAYS_DEFLECTION2 = range(6)
