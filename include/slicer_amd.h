@@ -1003,6 +1003,47 @@ int slicer_xi_read(slicer_xi_handle xh, double *xi, double *xim, double *r_mean,
 int slicer_xi_correlation(slicer_xi_handle xh, int32_t pair, int32_t which, double *host);
 int slicer_xi_destroy(slicer_xi_handle xh);
 
+/* ---- Betti numbers of a map's excursion sets, as exact counts ----
+ * Input, thresholds, rank and excursion sets are those of the Minkowski functionals above (row N14): any device f32 map of
+ * npix^2 pixels (row-major), only read; f64 thresholds t_0 < ... < t_{T-1}, finite and strictly ascending,
+ * 1 <= T <= SLICER_BETTI_MAX_THRESHOLDS; k(x) = the number of t_j <= (double)x, compared in f64, k(NaN) = k(-inf) = 0,
+ * k(+inf) = T; pixel x is in Q_j iff k(x) > j; positions outside the map are in no set and the field does not wrap.
+ * Per threshold j = 0 ... T-1, all int64:
+ *   components[j]  beta_0: the 8-connected components of Q_j; two pixels of Q_j are joined iff they share a side or a
+ *                  corner
+ *   holes[j]       beta_1: the 4-connected components (sides only) of the complement {pixels of the map with k <= j, NaN
+ *                  pixels included} that contain no pixel of the map's first or last row or column; a complement
+ *                  component that touches the rim reaches outside and is not a hole
+ *   faces[j]       the pixels with k > j: the number slicer_minkowski_read gives, for cross-checks without a second handle
+ *   n_nan          the NaN pixels of the last run
+ * These connectivities are the ones the closed pixel complex of row N14 implies: components[j] - holes[j] equals its
+ * vertices[j] - edges[j] + faces[j] exactly, on every map.  The counts are exact and the same on every run, although the
+ * order in which the device unites pixels is not.
+ *   slicer_betti_create    on the device and stream of h (create it after any slicer_set_stream, destroy it before h).
+ *                          The numbers are checked before the handle, so that they can be checked without a device:
+ *                          npix < 1, fewer than 1 or more than 1025 thresholds, a threshold that is not finite,
+ *                          thresholds not strictly ascending: SLICER_ERR_ARG; npix > SLICER_BETTI_MAX_NPIX (node ids and
+ *                          npix^2 + 1 stay well inside 32 bits): SLICER_ERR_UNSUPPORTED.  Device memory: a u16 rank map
+ *                          (2 npix^2 bytes), a u32 parent array of npix^2 + 1 nodes, the thresholds, at most max(64, 8 per
+ *                          compute unit) rows of 4 (T + 2) bytes of counters, 8 (T + 1) bytes of link counters and
+ *                          8 (T + 2) + 8 (3 T + 1) bytes of sums and results: about 6 GB at npix = 32768
+ *                          (SLICER_ERR_NOMEM)
+ *   slicer_betti_run       any device f32 map of the handle's npix^2 pixels (e.g. slicer_kappa_device_map); enqueued, no
+ *                          synchronisation.  A NULL map: SLICER_ERR_ARG
+ *   slicer_betti_run_npix  the same of a smaller map of npix^2 pixels, 1 <= npix <= the handle's (others:
+ *                          SLICER_ERR_ARG), so that one handle serves every level of a moments pyramid
+ *   slicer_betti_read      components, holes, faces [T] each and the NaN count of the last run (any of them NULL); waits
+ *                          for the stream.  Before any run: SLICER_ERR_STATE */
+typedef struct slicer_betti *slicer_betti_handle;
+#define SLICER_BETTI_MAX_THRESHOLDS 1025
+#define SLICER_BETTI_MAX_NPIX 32768
+int slicer_betti_create(slicer_handle h, int32_t npix, int32_t n_thresholds, const double *thresholds,
+                        slicer_betti_handle *out);
+int slicer_betti_run(slicer_betti_handle bh, const float *d_map);
+int slicer_betti_run_npix(slicer_betti_handle bh, const float *d_map, int32_t npix);
+int slicer_betti_read(slicer_betti_handle bh, int64_t *components, int64_t *holes, int64_t *faces, int64_t *n_nan);
+int slicer_betti_destroy(slicer_betti_handle bh);
+
 /* per-kernel HIP-event timing (off by default; adds two event records per launch) */
 int slicer_profile_enable(slicer_handle h, int on);
 int slicer_profile_reset(slicer_handle h);

@@ -124,6 +124,11 @@ SYMBOLS = {
     "slicer_minkowski_run_npix": (C.c_int, [_H, C.c_void_p, C.c_int32]),
     "slicer_minkowski_read": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "slicer_minkowski_destroy": (C.c_int, [_H]),
+    "slicer_betti_create": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "slicer_betti_run": (C.c_int, [_H, C.c_void_p]),
+    "slicer_betti_run_npix": (C.c_int, [_H, C.c_void_p, C.c_int32]),
+    "slicer_betti_read": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "slicer_betti_destroy": (C.c_int, [_H]),
     "slicer_bispectrum_triangles": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "slicer_bispectrum_create": (C.c_int, [_H, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
                                           C.POINTER(C.c_void_p)]),

@@ -43,6 +43,11 @@
 //     the edges of `bins` (1 ... 1024) uniform bins from lo to hi; with --moments also of every level of its pyramid of
 //     block means; with --smooth and / or --shape-noise also .smooth_minkowski_, .noisy_minkowski_ and
 //     .noisy_smooth_minkowski_, where --peaks writes its tables of those maps.
+//   * --betti lo,hi,bins: <directory><simulation>.betti_<npix>_<suffix>.txt, the Betti numbers of the same excursion
+//     sets over the same kind of thresholds as exact counts: per threshold the 8-connected components of the set and its
+//     holes (the 4-connected components of the complement that do not touch the map's rim), whose difference is
+//     --minkowski's euler; the levels and the tables .smooth_betti_, .noisy_betti_ and .noisy_smooth_betti_ as for
+//     --minkowski.  The Betti tables are the last files of a run.
 //   * --bispectrum all|equilateral with --bispectrum-edges r0,r1,... (required; 2 ... 33 edges in the units of
 //     --power-edges): <directory><simulation>.bl_<npix>_<suffix>.txt, the binned bispectrum B_ijk of every kappa map over
 //     all triples i <= j <= k of the bins or over the equilateral ones, with the number of closed triangles of every
@@ -224,6 +229,9 @@ int LensingOptions::parse(int argc, char **argv, int &i)
         if (const int rc = uniform_edges(a, has_value ? argv[++i] : nullptr, "the first and the last threshold",
                                          minkowski_thresholds))
             return rc;
+    } else if (a == "--betti") {
+        if (const int rc = uniform_edges(a, has_value ? argv[++i] : nullptr, "the first and the last threshold", betti_thresholds))
+            return rc;
     } else if (a == "--smooth") {
         const string v = has_value ? argv[++i] : "";
         const size_t colon = v.find(':');
@@ -312,6 +320,7 @@ int LensingOptions::check() const
         {!peaks_edges.empty() && no_kappa, "--peaks needs --kappa (the histograms and peak counts are those of the kappa maps)"},
         {!minkowski_thresholds.empty() && no_kappa,
          "--minkowski needs --kappa (the Minkowski functionals are those of the kappa maps)"},
+        {!betti_thresholds.empty() && no_kappa, "--betti needs --kappa (the Betti numbers are those of the kappa maps)"},
         {!smooth_kind.empty() && no_kappa, "--smooth needs --kappa (the smoothed maps are those of the kappa maps)"},
         {shape_noise && no_kappa, "--shape-noise needs --kappa (the noise is added to the kappa maps)"},
         {starlet_scales > 0 && no_kappa, "--starlet needs --kappa (the transform is that of the kappa maps)"},
@@ -493,6 +502,9 @@ int LensingOutputs::create()
         slicer_minkowski_create(h, p.npix, (int)o.minkowski_thresholds.size(), o.minkowski_thresholds.data(), mkh.out()) !=
             SLICER_OK)
         return fail(h, "slicer_amd: --minkowski");
+    if (!o.betti_thresholds.empty() &&
+        slicer_betti_create(h, p.npix, (int)o.betti_thresholds.size(), o.betti_thresholds.data(), bth.out()) != SLICER_OK)
+        return fail(h, "slicer_amd: --betti");
     if (!o.bispectrum.empty()) {
         const int B = (int)o.bispectrum_edges.size() - 1;
         for (int i = 0; i < B; i++)
@@ -659,7 +671,7 @@ bool LensingOutputs::save(const char *what, const string &token, size_t s, const
 
 // Per source the kappa file, then its moments, then the histograms and the Minkowski functionals of its pyramid (which
 // the moments of the same source left behind), then the shear files, then the smoothed maps with their moments,
-// histograms and functionals, then the noisy maps with theirs; after the sources the tables.
+// histograms and functionals, then the noisy maps with theirs; after the sources the tables, the Betti tables last.
 int LensingOutputs::write()
 {
     if (slicer_kappa_finalize(kh) != SLICER_OK)
@@ -691,20 +703,23 @@ int LensingOutputs::write()
         return rc;
     // what stdout calls a statistic and its file token; the same of a kind of map, and whether the run has that kind
     static const char *const statistic[N_STATISTICS][2] = {
-        {"moments", "moments_"}, {"histograms and peak counts", "peaks_"}, {"Minkowski functionals", "minkowski_"}};
+        {"moments", "moments_"}, {"histograms and peak counts", "peaks_"}, {"Minkowski functionals", "minkowski_"},
+        {"Betti numbers", "betti_"}};
     static const char *const kind[N_KINDS][2] = {{"", "."},
                                                  {" of the smoothed maps", ".smooth_"},
                                                  {" of the noisy maps", ".noisy_"},
                                                  {" of the smoothed noisy maps", ".noisy_smooth_"}};
-    const bool has_statistic[N_STATISTICS] = {mh != nullptr, pkh != nullptr, mkh != nullptr};
+    const bool has_statistic[N_STATISTICS] = {mh != nullptr, pkh != nullptr, mkh != nullptr, bth != nullptr};
+    const auto write_statistic = [&](int t, int k) {
+        return write_table((string(statistic[t][0]) + kind[k][0]).c_str(), (string(kind[k][1]) + statistic[t][1]).c_str(),
+                           tables[t][k]);
+    };
     const bool has_kind[N_KINDS] = {true, !smh.empty(), nh != nullptr, nh != nullptr && !smh.empty()};
     // the moments and the histograms kind by kind, then the Minkowski tables: the order these files have always had
     for (const bool last : {false, true})
         for (int k = 0; k < N_KINDS; k++)
             for (int t = 0; t < N_STATISTICS; t++)
-                if ((t == MINKOWSKI) == last && has_statistic[t] && has_kind[k] &&
-                    write_table((string(statistic[t][0]) + kind[k][0]).c_str(), (string(kind[k][1]) + statistic[t][1]).c_str(),
-                                tables[t][k]))
+                if (t != BETTI && (t == MINKOWSKI) == last && has_statistic[t] && has_kind[k] && write_statistic(t, k))
                     return 1;
     static const char *const starlet_table[2][2] = {{"starlet histograms and peak counts", "starlet_peaks_"},
                                                     {"starlet l1-norms", "starlet_l1_"}};
@@ -713,6 +728,10 @@ int LensingOutputs::write()
             if (write_table((string(starlet_table[t][0]) + kind[noisy ? NOISY : KAPPA][0]).c_str(),
                             (string(kind[noisy ? NOISY : KAPPA][1]) + starlet_table[t][1]).c_str(), starlet_tables[t][noisy]))
                 return 1;
+    // the Betti tables after every file that a run without --betti writes
+    for (int k = 0; k < N_KINDS; k++)
+        if (has_statistic[BETTI] && has_kind[k] && write_statistic(BETTI, k))
+            return 1;
     return 0;
 }
 
@@ -886,7 +905,9 @@ int LensingOutputs::map_statistics(size_t s, float *d_map, MapKind kind, const s
         return rc;
     if (const int rc = pkh ? source_peaks(s, d_map, tables[PEAKS][kind], head, lead_names, lead) : 0)
         return rc;
-    return mkh ? source_minkowski(s, d_map, tables[MINKOWSKI][kind], head, lead_names, lead) : 0;
+    if (const int rc = mkh ? source_minkowski(s, d_map, tables[MINKOWSKI][kind], head, lead_names, lead) : 0)
+        return rc;
+    return bth ? source_betti(s, d_map, tables[BETTI][kind], head, lead_names, lead) : 0;
 }
 
 void LensingOutputs::counts_head(string &text, const char *name, const vector<double> &values, const string &head,
@@ -992,6 +1013,30 @@ int LensingOutputs::source_minkowski(size_t s, float *d_map, string &text, const
             add(text, "%.17g %d %d %d %.17g %lld %lld %lld %lld %lld %lld %lld\n", plan.zs[s], l, p.npix >> l, j, t[j],
                 (long long)c[j], (long long)c[T + j], (long long)c[2 * T + j], (long long)c[3 * T + j],
                 (long long)c[4 * T + j], (long long)(c[2 * T + j] - c[T + j] + c[j]), (long long)n_nan);
+        }
+        return 0;
+    });
+}
+
+// The Betti table: '#' lines (npix, angle, levels, the thresholds, column names), then per (source, level) one row per
+// threshold j: the exact counts of slicer_betti_read; n_nan is the level's, repeated in every row.  The levels are those
+// of source_peaks.
+int LensingOutputs::source_betti(size_t s, float *d_map, string &text, const string &head, const string &lead_names,
+                                 const string &lead)
+{
+    const vector<double> &t = o.betti_thresholds;
+    const int T = (int)t.size();
+    vector<int64_t> c(3 * T);  // components, holes, faces [T]
+    int64_t n_nan = 0;
+    counts_head(text, "thresholds", t, head, lead_names + "z level npix j threshold n_components n_holes n_faces n_nan\n");
+    return pyramid_levels("slicer_amd: --betti", d_map, [&](int l, float *d_level) {
+        if (slicer_betti_run_npix(bth, d_level, p.npix >> l) != SLICER_OK ||
+            slicer_betti_read(bth, &c[0], &c[T], &c[2 * T], &n_nan) != SLICER_OK)
+            return fail(h, "slicer_amd: --betti");
+        for (int j = 0; j < T; j++) {
+            text += lead;
+            add(text, "%.17g %d %d %d %.17g %lld %lld %lld %lld\n", plan.zs[s], l, p.npix >> l, j, t[j], (long long)c[j],
+                (long long)c[T + j], (long long)c[2 * T + j], (long long)n_nan);
         }
         return 0;
     });

@@ -1,6 +1,6 @@
 // driver_lensing.hpp -- the lensing outputs of the SLICER_amd driver (slicer_main.cpp): their options, their host
 // planning and the device-0 work behind --kappa, --shear, --deflection, --raytrace, --power, --pcl, --xi, --moments, --peaks,
-// --minkowski, --bispectrum, --smooth, --shape-noise and --starlet (driver_lensing.cpp describes the options), with the small helpers the rest of the driver shares with them.
+// --minkowski, --betti, --bispectrum, --smooth, --shape-noise and --starlet (driver_lensing.cpp describes the options), with the small helpers the rest of the driver shares with them.
 #pragma once
 #include <deque>
 #include <string>
@@ -32,6 +32,7 @@ struct LensingOptions {
     int moments_levels = 0;
     std::vector<double> peaks_edges;  // empty: no --peaks
     std::vector<double> minkowski_thresholds;  // empty: no --minkowski
+    std::vector<double> betti_thresholds;      // empty: no --betti
     std::string bispectrum;                 // "" (no --bispectrum), "all" or "equilateral"
     std::vector<double> bispectrum_edges;   // --bispectrum-edges, required with it: at most 33
     std::string smooth_kind;             // "" (no --smooth), "gauss" or "map"
@@ -127,6 +128,7 @@ struct LensingOutputs {
     Owned<slicer_moments_handle, slicer_moments_destroy> mh{};
     Owned<slicer_peaks_handle, slicer_peaks_destroy> pkh{};
     Owned<slicer_minkowski_handle, slicer_minkowski_destroy> mkh{};
+    Owned<slicer_betti_handle, slicer_betti_destroy> bth{};
     Owned<slicer_bispectrum_handle, slicer_bispectrum_destroy> bsh{};  // --bispectrum: one handle, source after source
     std::vector<int32_t> bispectrum_triples{};                         // its list, rows (i, j, k)
     std::deque<Owned<slicer_smooth_handle, slicer_smooth_destroy>> smh{};  // --smooth: one per scale
@@ -156,10 +158,10 @@ struct LensingOutputs {
     size_t rt_next = 0;
     DeviceMaps upload{h};        // planes read back from their files
     std::vector<float> map{};    // the host copy of the map that save() writes
-    // The tables of --moments, --peaks and --minkowski, which write() gathers source by source: one per statistic and
+    // The tables of --moments, --peaks, --minkowski and --betti, which write() gathers source by source: one per statistic and
     // kind of map -- the kappa maps, the smoothed ones scale by scale, the noisy ones realisation by realisation, and
     // the smoothed noisy ones
-    enum Statistic { MOMENTS, PEAKS, MINKOWSKI, N_STATISTICS };
+    enum Statistic { MOMENTS, PEAKS, MINKOWSKI, BETTI, N_STATISTICS };
     enum MapKind { KAPPA, SMOOTH, NOISY, NOISY_SMOOTH, N_KINDS };
     std::string tables[N_STATISTICS][N_KINDS]{};
 
@@ -184,11 +186,13 @@ private:
                      const std::string &lead);
     int source_minkowski(size_t s, float *d_map, std::string &text, const std::string &head, const std::string &lead_names,
                          const std::string &lead);
-    // ... of every statistic that is on, into its table of this kind of map: moments, then peaks, then Minkowski (the
-    // last two read the pyramid that the moments of the same map left behind)
+    int source_betti(size_t s, float *d_map, std::string &text, const std::string &head, const std::string &lead_names,
+                     const std::string &lead);
+    // ... of every statistic that is on, into its table of this kind of map: moments, then peaks, Minkowski, Betti (the
+    // last three read the pyramid that the moments of the same map left behind)
     int map_statistics(size_t s, float *d_map, MapKind kind, const std::string &head = "", const std::string &lead_names = "",
                        const std::string &lead = "");
-    // The '#' lines of a --peaks / --minkowski table while `text` is empty: npix, angle, levels, `name` and the values,
+    // The '#' lines of a --peaks / --minkowski / --betti table while `text` is empty: npix, angle, levels, `name` and the values,
     // `head`, the column names.  The levels of the pyramid under d_map, 0 (the map itself) ... levels: rows(l, d_level).
     void counts_head(std::string &text, const char *name, const std::vector<double> &values, const std::string &head,
                      const std::string &columns) const;

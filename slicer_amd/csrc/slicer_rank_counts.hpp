@@ -1,6 +1,6 @@
 // slicer_rank_counts.hpp -- internal: what slicer_peaks.hip and slicer_minkowski.hip (row N14) share,
 // device and host; slicer_starlet.hip (row N16) takes the search, the column sums and the host helpers for its binned
-// sums.  Only those three include it; everything is in an unnamed namespace, so each has its own copy (the column-sum
+// sums, and slicer_betti.hip (row N19) the same.  Only those four include it; everything is in an unnamed namespace, so each has its own copy (the column-sum
 // kernel too: kernels of one name, one per code object).
 // Both count integers over tiles of kT0 x kT1 = 16 x 64 positions (the tile of slicer_fd.hip), four adjacent ones of a
 // row a thread, from a window in LDS whose rows have pitch 72 with the tile's first column at window column 4, so that

@@ -7,7 +7,8 @@ and shape noise for such maps from a counter-based generator (row N13), and the 
 excursion sets as exact counts (row N14), and the binned bispectra of such maps (row N15), and the starlet transform of
 such maps with the binned absolute sums of its scales, the starlet l1-norm (row N16), and the masked pseudo-C_l of such
 maps: coupled bandpowers, the mask's mode-coupling matrix and the decoupled bandpowers (row N17), and the real-space
-two-point correlation functions xi_kk, xi+ and xi- of such maps and of shear maps (row N18).
+two-point correlation functions xi_kk, xi+ and xi- of such maps and of shear maps (row N18), and the Betti numbers of
+such maps' excursion sets as exact counts (row N19).
 
 plane_weights wraps the host weights of include/slicer_amd.h (slicer_lensing_weights); Kappa is the device accumulator
 (slicer_kappa_*) bound to a Slicer handle: it reads the finalized plane maps where they are, in HBM.  Shear (slicer_shear_*)
@@ -24,7 +25,8 @@ Bispectrum (slicer_bispectrum_*) contracts the band-filtered f64 maps of a map o
 (slicer_starlet_*) splits a map into wavelet scales that sum back to it, and L1Norm (slicer_l1norm_*) sums |x| of a map's
 pixels bin by bin over Peaks' edges; Pcl (slicer_pcl_*) is Power under a mask (a border taper, a user mask or both),
 with the coupling matrix of the mask and the bandpowers decoupled by it; Xi (slicer_xi_*) sums the pair products of
-zero-padded maps over annuli of the lag, divided by the pair weights of one shared weight map.
+zero-padded maps over annuli of the lag, divided by the pair weights of one shared weight map; Betti (slicer_betti_*)
+counts the 8-connected components of the sets x >= t_j and the holes in them by a union-find on the device.
 """
 import ctypes as C
 import math
@@ -551,6 +553,57 @@ def minkowski_functionals(read, angle_deg):
             "v1": f64("boundary") * d / (4.0 * theta * theta),
             "v1_with_border": (f64("boundary") + f64("border")) * d / (4.0 * theta * theta),
             "v2": f64("euler") / (theta * theta)}
+
+
+BETTI_MAX_THRESHOLDS = 1025
+BETTI_MAX_NPIX = 32768
+
+
+class Betti(_SubHandle):
+    """The Betti numbers of the excursion sets x >= t_j of an npix^2 map over the f64 `thresholds`, as exact int64
+    counts: the 8-connected components of every set and its holes (the 4-connected components of the complement that
+    do not touch the map's rim), on the device of `slicer`, on its stream.  components - holes
+    is Minkowski's euler of the same map and thresholds.  peaks_edges(lo, hi, bins) gives bins + 1 uniform thresholds."""
+    _handle, _destroy = "_bh", "slicer_betti_destroy"
+
+    def __init__(self, slicer: Slicer, npix, thresholds):
+        self._s = slicer
+        self.npix = int(npix)
+        self.thresholds = np.array(thresholds, np.float64).ravel()
+        self.n_thresholds = self.thresholds.size
+        bh = C.c_void_p()
+        slicer._chk(_L.slicer_betti_create(slicer._h, self.npix, self.n_thresholds, _dptr(self.thresholds),
+                                           C.byref(bh)))
+        self._bh = bh
+        self.last_npix = None  # of the last run
+
+    def run(self, d_map, npix=None):
+        """d_map: device address of an f32 map of npix^2 pixels (None: the handle's npix; otherwise at most that)."""
+        d = None if d_map is None else int(d_map)
+        if npix is None:
+            self._s._chk(_L.slicer_betti_run(self._bh, d))
+        else:
+            self._s._chk(_L.slicer_betti_run_npix(self._bh, d, int(npix)))
+        self.last_npix = self.npix if npix is None else int(npix)
+
+    def run_kappa(self, kappa: Kappa, s):
+        """The map of source s of a Kappa accumulator, where it is."""
+        self.run(kappa.device_map(s), kappa.npix)
+
+    def run_level(self, moments: Moments, level):
+        """Level `level` >= 1 of the last run of a Moments pyramid, where it is (level 0 is the caller's own map)."""
+        self.run(moments.device_map(level), moments.npix >> int(level))
+
+    def read(self):
+        """dict: thresholds [T], components, holes, faces (int64 [T], one value per threshold), nan, and npix: the map
+        size of the last run."""
+        T = self.n_thresholds
+        components, holes, faces = (np.empty(T, np.int64) for _ in range(3))
+        nan = np.empty(1, np.int64)
+        self._s._chk(_L.slicer_betti_read(self._bh, components.ctypes.data, holes.ctypes.data, faces.ctypes.data,
+                                          nan.ctypes.data))
+        return {"thresholds": self.thresholds.copy(), "components": components, "holes": holes, "faces": faces,
+                "nan": int(nan[0]), "npix": self.last_npix}
 
 
 BISPECTRUM_MAX_BINS = 32
