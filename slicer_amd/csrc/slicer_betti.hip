@@ -70,13 +70,7 @@ static_assert((int64_t)kBettiMaxNpix * kBettiMaxNpix + 1 < ((int64_t)1 << 31), "
 static_assert(kMaxT + 1 <= 65536, "a rank fits u16");
 
 // log2 of the copies of the T + 1 rank counters that kCopyBytes hold, 32 at most
-int lg_copies_of(int T)
-{
-    int lg = 0;
-    while (lg < 5 && ((size_t)(T + 1) * sizeof(unsigned) << (lg + 1)) <= kCopyBytes)
-        lg++;
-    return lg;
-}
+int lg_copies_of(int T) { return lg_copies((size_t)(T + 1) * sizeof(unsigned), kCopyBytes, 5); }
 
 size_t rank_dyn_lds(int T) { return (size_t)T * sizeof(double) + ((((size_t)T + 1) << lg_copies_of(T)) + 1) * sizeof(unsigned); }
 
@@ -91,8 +85,8 @@ struct RankArgs {
     int T, lg_copies;
 };
 
-// Thread q of the grid-stride loop takes the four pixels 4 q ... 4 q + 3 of the flat map: a float4 when the map is on the
-// 16-byte grid (VEC) and the quad is whole, scalar loads otherwise.
+// Thread q of the grid-stride loop takes the four pixels 4 q ... 4 q + 3 of the flat map (load_quad; VEC: the map is on
+// the 16-byte grid).
 template <bool VEC>
 __global__ __launch_bounds__(kThreads) void k_betti_rank(RankArgs a)
 {
@@ -101,8 +95,7 @@ __global__ __launch_bounds__(kThreads) void k_betti_rank(RankArgs a)
     const unsigned copy = tid & ((1 << lg) - 1), n2 = a.n2;
     double *thr = dyn;
     unsigned *cnt = reinterpret_cast<unsigned *>(dyn + T);  // rank k, copy c: cnt[(k << lg) + c]; then the NaNs
-    for (int k = tid; k < T; k += kThreads)
-        thr[k] = a.thr[k];
+    stage_table<kThreads>(thr, a.thr, T);
     for (int k = tid; k <= nan_at; k += kThreads)
         cnt[k] = 0u;
     if (blockIdx.x == 0) {
@@ -115,19 +108,8 @@ __global__ __launch_bounds__(kThreads) void k_betti_rank(RankArgs a)
     const unsigned nquads = (n2 + kPer - 1) / kPer;
     for (unsigned q = blockIdx.x * kThreads + tid; q < nquads; q += gridDim.x * kThreads) {
         const unsigned p0 = q * kPer, have = min((unsigned)kPer, n2 - p0);
-        float v[kPer];
-#pragma unroll
-        for (int e = 0; e < kPer; e++)
-            v[e] = -INFINITY;
-        if (VEC && have == kPer) {
-            const float4 m = *reinterpret_cast<const float4 *>(a.x + p0);
-            v[0] = m.x, v[1] = m.y, v[2] = m.z, v[3] = m.w;
-        } else {
-#pragma unroll
-            for (int e = 0; e < kPer; e++)
-                if ((unsigned)e < have)
-                    v[e] = a.x[p0 + e];
-        }
+        const float4 m = load_quad<VEC>(a.x, p0, (int)have, -INFINITY);
+        const float v[kPer] = {m.x, m.y, m.z, m.w};
         unsigned n_nan = 0;
         double xd[kPer];
         int pos[kPer];
@@ -164,12 +146,8 @@ __global__ __launch_bounds__(kThreads) void k_betti_rank(RankArgs a)
     }
     __syncthreads();
     unsigned *out = a.partial + (size_t)blockIdx.x * (nb + 1);
-    for (int k = tid; k < nb; k += kThreads) {
-        unsigned sum = 0;
-        for (int c = 0; c < 1 << lg; c++)
-            sum += cnt[(k << lg) + c];
-        out[k] = sum;
-    }
+    for (int k = tid; k < nb; k += kThreads)
+        out[k] = fold_copies(cnt, k, lg);
     if (tid == 0)
         out[nb] = cnt[nan_at];
 }
@@ -332,54 +310,34 @@ __global__ __launch_bounds__(kThreads) void k_betti_finish(const int64_t *sums, 
         res[3 * T] = sums[nb];
 }
 
+const RankModule kBetti = {"slicer_betti", "slicer_betti_create", "thresholds", "fewer than 1 threshold", 1, kMaxT, kBettiMaxNpix};
+
 }  // namespace
 
-struct slicer_betti : SubHandle {
-    int n = 0, T = 0;
-    int gmax = 0;  // rows of `partial`
-    std::vector<double> thr;
-    double *d_thr = nullptr;
+struct slicer_betti : RankHandle {  // table: the T thresholds
+    int T = 0;
     unsigned short *rank = nullptr;
     unsigned *parent = nullptr;
     unsigned *partial = nullptr;
     int64_t *sums = nullptr;  // the column sums of `partial`
     unsigned *links = nullptr;
     int64_t *res = nullptr;
-    bool ran = false;
 };
 
 extern "C" {
 
 int slicer_betti_create(slicer_handle h, int32_t npix, int32_t n_thresholds, const double *thresholds, slicer_betti_handle *out)
 {
-    // the numbers first: they need no handle, so a caller can have them checked before any device exists
-    const char *who = "slicer_betti_create";
-    if (out)
-        *out = nullptr;
-    if (int rc = npix_in_range(h, who, npix, kBettiMaxNpix))
-        return rc;
-    if (n_thresholds < 1)
-        return fail(h, SLICER_ERR_ARG, "slicer_betti_create: fewer than 1 threshold");
-    if (n_thresholds > kMaxT)
-        return fail(h, SLICER_ERR_ARG, "slicer_betti_create: %d thresholds, at most %d", n_thresholds, kMaxT);
-    if (!thresholds)
-        return fail(h, SLICER_ERR_ARG, "slicer_betti_create: null argument");
-    if (const char *what = ascending_fault(n_thresholds, thresholds))
-        return fail(h, SLICER_ERR_ARG, "slicer_betti_create: thresholds must be %s", what);
-    if (!h || !out)
-        return fail(h, SLICER_ERR_ARG, "slicer_betti_create: null argument");
     hipStream_t st = nullptr;
     slicer_betti_handle bh = nullptr;
-    if (int rc = sub_new(h, who, &st, &bh))
+    int rc = rank_create(h, kBetti, npix, n_thresholds, thresholds, out, &st, &bh);
+    if (!bh)
         return rc;
-    bh->n = npix;
+    const char *who = kBetti.create;
     bh->T = n_thresholds;
     const size_t n2 = (size_t)npix * npix, nC = (size_t)bh->T + 2;
     const int64_t quad_groups = (int64_t)((n2 + kPer - 1) / kPer + kThreads - 1) / kThreads;
     bh->gmax = resident_groups(rank_dyn_lds(bh->T), quad_groups, h->num_cus);
-    bh->thr.assign(thresholds, thresholds + n_thresholds);
-    int rc = SLICER_OK;
-    rc = bh->mem.alloc(rc, h, who, (void **)&bh->d_thr, (size_t)n_thresholds * sizeof(double));
     // (the rank map up to the next multiple of kGroup pixels: k_betti_link loads whole groups)
     rc = bh->mem.alloc(rc, h, who, (void **)&bh->rank, (n2 + kGroup - 1) / kGroup * kGroup * sizeof(unsigned short));
     rc = bh->mem.alloc(rc, h, who, (void **)&bh->parent, (n2 + 1) * sizeof(unsigned));
@@ -387,25 +345,14 @@ int slicer_betti_create(slicer_handle h, int32_t npix, int32_t n_thresholds, con
     rc = bh->mem.alloc(rc, h, who, (void **)&bh->sums, nC * sizeof(int64_t));
     rc = bh->mem.alloc(rc, h, who, (void **)&bh->links, 2 * ((size_t)bh->T + 1) * sizeof(unsigned));
     rc = bh->mem.alloc(rc, h, who, (void **)&bh->res, (3 * (size_t)bh->T + 1) * sizeof(int64_t));
-    if (rc == SLICER_OK) {
-        // (bh->thr outlives the copy)
-        hipError_t e = hipMemcpyAsync(bh->d_thr, bh->thr.data(), (size_t)n_thresholds * sizeof(double), hipMemcpyHostToDevice, st);
-        if (e != hipSuccess)
-            rc = fail(h, SLICER_ERR_HIP, "%s: copying the thresholds: %s", who, hipGetErrorString(e));
-    }
-    return sub_done(rc, bh, out);
+    return sub_done(rank_upload(rc, *bh, kBetti, st), bh, out);
 }
 
 int slicer_betti_run_npix(slicer_betti_handle bh, const float *d_map, int32_t npix)
 {
-    if (!bh || !d_map)
-        return fail(bh ? bh->h : nullptr, SLICER_ERR_ARG, "slicer_betti_run_npix: null argument");
-    if (npix < 1 || npix > bh->n)
-        return fail(bh->h, SLICER_ERR_ARG, "slicer_betti_run_npix: npix = %d outside 1..%d", npix, bh->n);
     hipStream_t st;
-    if (int rc = sub_stream(bh->h, bh->device, &st))
+    if (int rc = rank_run_begin(bh, d_map, npix, kBetti, &st))
         return rc;
-    bh->ran = false;
     const int T = bh->T;
     const unsigned n2 = (unsigned)npix * (unsigned)npix;
     // grid-stride kernels: as many workgroups as the work fills, kPerCu a CU at most
@@ -417,7 +364,7 @@ int slicer_betti_run_npix(slicer_betti_handle bh, const float *d_map, int32_t np
         ProfScope ps(bh->h, KN_BETTI_RANK);
         RankArgs a{};
         a.x = d_map;
-        a.thr = bh->d_thr;
+        a.thr = bh->d_table;
         a.rank = bh->rank;
         a.parent = bh->parent;
         a.partial = bh->partial;
@@ -469,17 +416,15 @@ int slicer_betti_run_npix(slicer_betti_handle bh, const float *d_map, int32_t np
 
 int slicer_betti_run(slicer_betti_handle bh, const float *d_map)
 {
-    if (!bh || !d_map)
-        return fail(bh ? bh->h : nullptr, SLICER_ERR_ARG, "slicer_betti_run: null argument");
+    if (int rc = rank_not_null(bh, d_map, kBetti, ""))
+        return rc;
     return slicer_betti_run_npix(bh, d_map, bh->n);
 }
 
 int slicer_betti_read(slicer_betti_handle bh, int64_t *components, int64_t *holes, int64_t *faces, int64_t *n_nan)
 {
-    if (!bh)
-        return fail(nullptr, SLICER_ERR_ARG, "slicer_betti_read: null handle");
-    if (!bh->ran)
-        return fail(bh->h, SLICER_ERR_STATE, "slicer_betti_read before any slicer_betti_run");
+    if (int rc = rank_read_begin(bh, kBetti))
+        return rc;
     const size_t T = (size_t)bh->T;
     return read_slices(*bh, bh->res, {{components, T}, {holes, T}, {faces, T}, {n_nan, 1}});
 }

@@ -1,6 +1,7 @@
 // slicer_host.hpp -- internal (not installed, not exported): the host layer under the C ABI of include/slicer_amd.h.
-// The handle, its error and profiling plumbing, what the sub-handles (kappa, shear, FFT plan, power, moments, peaks, rays, smooth, noise, minkowski, bispectrum, starlet, l1norm, betti)
-// share, and the functions that cross the files of the core pass:
+// The handle, its error and profiling plumbing, what the sub-handles (kappa, shear, FFT plan, power, moments, peaks,
+// rays, smooth, noise, minkowski, bispectrum, starlet, l1norm, pcl, xi, betti) share, and the functions that cross the
+// files of the core pass:
 //   slicer_host.cpp    errors, grow-only buffers, profiling, the sub-handle helpers: SubHandle (the base of every
 //                      sub-handle struct) with sub_new / sub_done for its *_create, sub_stream for its launches, sub_read
 //                      for its read-backs and sub_destroy; npix_in_range and ranges_overlap for the argument checks

@@ -16,8 +16,8 @@
 // (i, j)): every face, edge and vertex has exactly one owner, and an owned edge is on the rim iff i is 0 or n (top
 // edge) or j is 0 or n (left edge).  What does not exist (a face or a left edge of row n, a top edge of column n,
 // anything past them) has only faces of rank 0 and is never counted, so existence needs no test.
-// The tile, the search, the grid size and the column sums are those of slicer_rank_counts.hpp, shared with
-// slicer_peaks.hip.
+// The tile, the search, the four-pixel load, the counters' copies, the grid size, the column sums and the host side of
+// the entry points are those of slicer_rank_counts.hpp.
 // A workgroup of 256 threads takes tiles of kT0 x kT1 = 16 x 64 cells and every thread
 // four adjacent cells of one row.  A tile needs the RANKS of 17 x 65 pixels: its own faces, one row above and one
 // column to the left.  Every pixel of the window is searched once, while it is staged, and the window holds the ranks
@@ -74,13 +74,7 @@ struct MinkArgs {
 };
 
 // log2 of the copies of the 5 (T + 1) counters that kCopyBytes hold, 32 at most
-int lg_copies_of(int T)
-{
-    int lg = 0;
-    while (lg < 5 && ((size_t)kHists * (T + 1) * sizeof(unsigned) << (lg + 1)) <= kCopyBytes)
-        lg++;
-    return lg;
-}
+int lg_copies_of(int T) { return lg_copies((size_t)kHists * (T + 1) * sizeof(unsigned), kCopyBytes, 5); }
 
 template <bool VEC>
 __global__ __launch_bounds__(kThreads) void k_minkowski(MinkArgs a)
@@ -92,8 +86,7 @@ __global__ __launch_bounds__(kThreads) void k_minkowski(MinkArgs a)
     const unsigned copy = tid & ((1 << lg) - 1);
     double *thr = dyn;
     unsigned *cnt = reinterpret_cast<unsigned *>(dyn + T);
-    for (int k = tid; k < T; k += kThreads)
-        thr[k] = a.thr[k];
+    stage_table<kThreads>(thr, a.thr, T);
     for (int k = tid; k <= nan_at; k += kThreads)
         cnt[k] = 0u;
     // w more elements of rank k in histogram h; rank 0 is in no set
@@ -108,24 +101,11 @@ __global__ __launch_bounds__(kThreads) void k_minkowski(MinkArgs a)
         // the five pixels of this thread: v[0..3] the quad of window row lr (map row r0 - 1 + lr), v[4] the extra one.
         // A position outside the map stays -inf: rank 0, like the NaNs, which are counted here.
         float v[kPer + 1];
-#pragma unroll
-        for (int q = 0; q <= kPer; q++)
-            v[q] = -INFINITY;
         {
-            const int r = r0 - 1 + lr, c = c0 + lc;
-            if (r >= 0 && r < n) {
-                if (VEC) {  // 4 | n and c % 4 == 0: a float4 lies in the map whole or not at all
-                    if (c < n) {
-                        const float4 m = *reinterpret_cast<const float4 *>(a.x + (size_t)r * n + c);
-                        v[0] = m.x, v[1] = m.y, v[2] = m.z, v[3] = m.w;
-                    }
-                } else {
-#pragma unroll
-                    for (int q = 0; q < kPer; q++)
-                        if (c + q < n)
-                            v[q] = a.x[(size_t)r * n + c + q];
-                }
-            }
+            // (VEC: 4 | n and c % 4 == 0, so a quad lies in the map whole or not at all)
+            const int r = r0 - 1 + lr, c = c0 + lc, have = r >= 0 && r < n && c < n ? (VEC ? kPer : min(n - c, kPer)) : 0;
+            const float4 m = load_quad<VEC>(a.x, (size_t)r * n + c, have, -INFINITY);
+            v[0] = m.x, v[1] = m.y, v[2] = m.z, v[3] = m.w, v[kPer] = -INFINITY;
         }
         int er = -1, ec = -1;  // the extra pixel's map position
         if (tid < kT1)
@@ -203,12 +183,8 @@ __global__ __launch_bounds__(kThreads) void k_minkowski(MinkArgs a)
     }
     __syncthreads();
     unsigned *out = a.partial + (size_t)blockIdx.x * nC;
-    for (int k = tid; k < nC - 1; k += kThreads) {
-        unsigned sum = 0;
-        for (int c = 0; c < 1 << lg; c++)
-            sum += cnt[(k << lg) + c];
-        out[k] = sum;
-    }
+    for (int k = tid; k < nC - 1; k += kThreads)
+        out[k] = fold_copies(cnt, k, lg);
     if (tid == 0)
         out[nC - 1] = cnt[nan_at];
 }
@@ -268,17 +244,16 @@ size_t mink_dyn_lds(int T)
     return (size_t)T * sizeof(double) + (((mink_columns(T) - 1) << lg_copies_of(T)) + 1) * sizeof(unsigned);
 }
 
+const RankModule kMinkowski = {"slicer_minkowski", "slicer_minkowski_create", "thresholds", "fewer than 1 threshold", 1, kMaxT,
+                               kMaxNpix};
+
 }  // namespace
 
-struct slicer_minkowski : SubHandle {
-    int n = 0, T = 0;
-    int gmax = 0;  // rows of `partial`
-    std::vector<double> thr;
-    double *d_thr = nullptr;
+struct slicer_minkowski : RankHandle {  // table: the T thresholds
+    int T = 0;
     unsigned *partial = nullptr;
     int64_t *hist = nullptr;  // the column sums of `partial`
     int64_t *res = nullptr;
-    bool ran = false;
 };
 
 extern "C" {
@@ -286,60 +261,30 @@ extern "C" {
 int slicer_minkowski_create(slicer_handle h, int32_t npix, int32_t n_thresholds, const double *thresholds,
                             slicer_minkowski_handle *out)
 {
-    // the numbers first: they need no handle, so a caller can have them checked before any device exists
-    const char *who = "slicer_minkowski_create";
-    if (out)
-        *out = nullptr;
-    if (int rc = npix_in_range(h, who, npix, kMaxNpix))
-        return rc;
-    if (n_thresholds < 1)
-        return fail(h, SLICER_ERR_ARG, "slicer_minkowski_create: fewer than 1 threshold");
-    if (n_thresholds > kMaxT)
-        return fail(h, SLICER_ERR_ARG, "slicer_minkowski_create: %d thresholds, at most %d", n_thresholds, kMaxT);
-    if (!thresholds)
-        return fail(h, SLICER_ERR_ARG, "slicer_minkowski_create: null argument");
-    if (const char *what = ascending_fault(n_thresholds, thresholds))
-        return fail(h, SLICER_ERR_ARG, "slicer_minkowski_create: thresholds must be %s", what);
-    if (!h || !out)
-        return fail(h, SLICER_ERR_ARG, "slicer_minkowski_create: null argument");
     hipStream_t st = nullptr;
     slicer_minkowski_handle mh = nullptr;
-    if (int rc = sub_new(h, who, &st, &mh))
+    int rc = rank_create(h, kMinkowski, npix, n_thresholds, thresholds, out, &st, &mh);
+    if (!mh)
         return rc;
-    mh->n = npix;
     mh->T = n_thresholds;
     // the LDS of a workgroup: the window, the thresholds, the counters; the tiles cover the n + 1 cells of a side
     mh->gmax = resident_groups(kRows * kPitch * sizeof(unsigned short) + mink_dyn_lds(mh->T), tiles_of(npix + 1), h->num_cus);
-    mh->thr.assign(thresholds, thresholds + n_thresholds);
     const size_t nC = mink_columns(mh->T);
-    int rc = SLICER_OK;
-    rc = mh->mem.alloc(rc, h, who, (void **)&mh->d_thr, (size_t)n_thresholds * sizeof(double));
-    rc = mh->mem.alloc(rc, h, who, (void **)&mh->partial, (size_t)mh->gmax * nC * sizeof(unsigned));
-    rc = mh->mem.alloc(rc, h, who, (void **)&mh->hist, nC * sizeof(int64_t));
-    rc = mh->mem.alloc(rc, h, who, (void **)&mh->res, (5 * (size_t)mh->T + 1) * sizeof(int64_t));
-    if (rc == SLICER_OK) {
-        // (mh->thr outlives the copy)
-        hipError_t e = hipMemcpyAsync(mh->d_thr, mh->thr.data(), (size_t)n_thresholds * sizeof(double), hipMemcpyHostToDevice, st);
-        if (e != hipSuccess)
-            rc = fail(h, SLICER_ERR_HIP, "%s: copying the thresholds: %s", who, hipGetErrorString(e));
-    }
-    return sub_done(rc, mh, out);
+    rc = mh->mem.alloc(rc, h, kMinkowski.create, (void **)&mh->partial, (size_t)mh->gmax * nC * sizeof(unsigned));
+    rc = mh->mem.alloc(rc, h, kMinkowski.create, (void **)&mh->hist, nC * sizeof(int64_t));
+    rc = mh->mem.alloc(rc, h, kMinkowski.create, (void **)&mh->res, (5 * (size_t)mh->T + 1) * sizeof(int64_t));
+    return sub_done(rank_upload(rc, *mh, kMinkowski, st), mh, out);
 }
 
 int slicer_minkowski_run_npix(slicer_minkowski_handle mh, const float *d_map, int32_t npix)
 {
-    if (!mh || !d_map)
-        return fail(mh ? mh->h : nullptr, SLICER_ERR_ARG, "slicer_minkowski_run_npix: null argument");
-    if (npix < 1 || npix > mh->n)
-        return fail(mh->h, SLICER_ERR_ARG, "slicer_minkowski_run_npix: npix = %d outside 1..%d", npix, mh->n);
     hipStream_t st;
-    if (int rc = sub_stream(mh->h, mh->device, &st))
+    if (int rc = rank_run_begin(mh, d_map, npix, kMinkowski, &st))
         return rc;
-    mh->ran = false;
     const int nC = (int)mink_columns(mh->T);
     MinkArgs a{};
     a.x = d_map;
-    a.thr = mh->d_thr;
+    a.thr = mh->d_table;
     a.partial = mh->partial;
     a.n = npix;
     a.T = mh->T;
@@ -369,18 +314,16 @@ int slicer_minkowski_run_npix(slicer_minkowski_handle mh, const float *d_map, in
 
 int slicer_minkowski_run(slicer_minkowski_handle mh, const float *d_map)
 {
-    if (!mh || !d_map)
-        return fail(mh ? mh->h : nullptr, SLICER_ERR_ARG, "slicer_minkowski_run: null argument");
+    if (int rc = rank_not_null(mh, d_map, kMinkowski, ""))
+        return rc;
     return slicer_minkowski_run_npix(mh, d_map, mh->n);
 }
 
 int slicer_minkowski_read(slicer_minkowski_handle mh, int64_t *faces, int64_t *edges, int64_t *vertices, int64_t *boundary,
                           int64_t *border, int64_t *n_nan)
 {
-    if (!mh)
-        return fail(nullptr, SLICER_ERR_ARG, "slicer_minkowski_read: null handle");
-    if (!mh->ran)
-        return fail(mh->h, SLICER_ERR_STATE, "slicer_minkowski_read before any slicer_minkowski_run");
+    if (int rc = rank_read_begin(mh, kMinkowski))
+        return rc;
     const size_t T = (size_t)mh->T;
     return read_slices(*mh, mh->res, {{faces, T}, {edges, T}, {vertices, T}, {boundary, T}, {border, T}, {n_nan, 1}});
 }

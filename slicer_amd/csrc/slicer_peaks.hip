@@ -8,8 +8,8 @@
 //              A comparison with a NaN is false, so a NaN and its neighbours are neither; ties give neither.
 // Every count is an integer: nothing here is a floating-point sum, so the results are exact and the same on every run.
 //
-// The tile, the search, the grid size and the column sums are those of slicer_rank_counts.hpp, shared with
-// slicer_minkowski.hip.
+// The tile, the search, the PDF rule, the grid size, the column sums and the host side of the entry points are those of
+// slicer_rank_counts.hpp.
 // k_peaks: a workgroup of 256 threads takes tiles of kT0 x kT1 = 16 x 64 pixels, stages a
 // tile with a halo of one pixel in LDS as f32 and every thread takes four adjacent pixels of one row.  The window is
 // 18 rows of pitch 72 with the tile's first column at window column 4 (not 18 x 66): the sixteen float4s of a window row
@@ -56,8 +56,7 @@ __global__ __launch_bounds__(kThreads) void k_peaks(PeakArgs a)
     const int n = a.n, B = a.B, nE = B + 1, nC = 3 * B + kOutside, tid = threadIdx.x;
     double *edge = dyn;
     unsigned *cnt = reinterpret_cast<unsigned *>(dyn + nE);
-    for (int k = tid; k < nE; k += kThreads)
-        edge[k] = a.edges[k];
+    stage_table<kThreads>(edge, a.edges, nE);
     for (int k = tid; k < nC; k += kThreads)
         cnt[k] = 0u;
     const double eB = a.edges[B];
@@ -118,19 +117,10 @@ __global__ __launch_bounds__(kThreads) void k_peaks(PeakArgs a)
                 break;
             const float x = nb[1][q + 1];
             // the pdf's counter of this pixel, and the distance from it to the peaks' one (the minima's: twice that)
-            int slot, stride = 1;
-            if (x != x) {
-                atomicAdd(&cnt[3 * B + 6], 1u);
-                continue;  // every comparison with it is false: neither a peak nor a minimum
-            } else if (pos[q] == 0) {
-                slot = 3 * B;  // below e_0
-            } else if (xd[q] > eB) {
-                slot = 3 * B + 3;  // above e_B
-            } else {
-                slot = pos[q] - 1;  // e_{B-1} <= x <= e_B gives pos = B: the last bin is closed
-                stride = B;
-            }
+            const int slot = pdf_slot(xd[q], pos[q], eB, 3 * B, 3), stride = slot < B ? B : 1;  // below[3], above[3], nan
             atomicAdd(&cnt[slot], 1u);
+            if (slot == 3 * B + 6)
+                continue;  // a NaN: every comparison with it is false, neither a peak nor a minimum
             if (!row_inside || j < 1 || j > n - 2)
                 continue;
             const float c00 = nb[0][q], c01 = nb[0][q + 1], c02 = nb[0][q + 2], c10 = nb[1][q], c12 = nb[1][q + 2];
@@ -151,16 +141,14 @@ __global__ __launch_bounds__(kThreads) void k_peaks(PeakArgs a)
 
 size_t peaks_dyn_lds(int B) { return (size_t)(B + 1) * sizeof(double) + (3 * (size_t)B + kOutside) * sizeof(unsigned); }
 
+const RankModule kPeaks = {"slicer_peaks", "slicer_peaks_create", "edges", "fewer than 2 edges", 2, kMaxBins + 1, kMaxNpix};
+
 }  // namespace
 
-struct slicer_peaks : SubHandle {
-    int n = 0, B = 0;
-    int gmax = 0;  // rows of `partial`
-    std::vector<double> edges;
-    double *d_edges = nullptr;
+struct slicer_peaks : RankHandle {  // table: the B + 1 edges
+    int B = 0;
     unsigned *partial = nullptr;
     int64_t *res = nullptr;
-    bool ran = false;
 };
 
 extern "C" {
@@ -187,59 +175,29 @@ int slicer_peaks_edges(double lo, double hi, int32_t bins, double *edges)
 
 int slicer_peaks_create(slicer_handle h, int32_t npix, int32_t n_edges, const double *edges, slicer_peaks_handle *out)
 {
-    // the numbers first: they need no handle, so a caller can have them checked before any device exists
-    const char *who = "slicer_peaks_create";
-    if (out)
-        *out = nullptr;
-    if (int rc = npix_in_range(h, who, npix, kMaxNpix))
-        return rc;
-    if (n_edges < 2)
-        return fail(h, SLICER_ERR_ARG, "slicer_peaks_create: fewer than 2 edges");
-    if (n_edges > kMaxBins + 1)
-        return fail(h, SLICER_ERR_ARG, "slicer_peaks_create: %d edges, at most %d", n_edges, kMaxBins + 1);
-    if (!edges)
-        return fail(h, SLICER_ERR_ARG, "slicer_peaks_create: null argument");
-    if (const char *what = ascending_fault(n_edges, edges))
-        return fail(h, SLICER_ERR_ARG, "slicer_peaks_create: edges must be %s", what);
-    if (!h || !out)
-        return fail(h, SLICER_ERR_ARG, "slicer_peaks_create: null argument");
     hipStream_t st = nullptr;
     slicer_peaks_handle ph = nullptr;
-    if (int rc = sub_new(h, who, &st, &ph))
+    int rc = rank_create(h, kPeaks, npix, n_edges, edges, out, &st, &ph);
+    if (!ph)
         return rc;
-    ph->n = npix;
     ph->B = n_edges - 1;
     // the LDS of a workgroup: the window, the edges, the counters
     ph->gmax = resident_groups(kRows * kPitch * sizeof(float) + peaks_dyn_lds(ph->B), tiles_of(npix), h->num_cus);
-    ph->edges.assign(edges, edges + n_edges);
     const size_t nC = 3 * (size_t)ph->B + kOutside;
-    int rc = SLICER_OK;
-    rc = ph->mem.alloc(rc, h, who, (void **)&ph->d_edges, (size_t)n_edges * sizeof(double));
-    rc = ph->mem.alloc(rc, h, who, (void **)&ph->partial, (size_t)ph->gmax * nC * sizeof(unsigned));
-    rc = ph->mem.alloc(rc, h, who, (void **)&ph->res, nC * sizeof(int64_t));
-    if (rc == SLICER_OK) {
-        // (ph->edges outlives the copy)
-        hipError_t e = hipMemcpyAsync(ph->d_edges, ph->edges.data(), (size_t)n_edges * sizeof(double), hipMemcpyHostToDevice, st);
-        if (e != hipSuccess)
-            rc = fail(h, SLICER_ERR_HIP, "%s: copying the edges: %s", who, hipGetErrorString(e));
-    }
-    return sub_done(rc, ph, out);
+    rc = ph->mem.alloc(rc, h, kPeaks.create, (void **)&ph->partial, (size_t)ph->gmax * nC * sizeof(unsigned));
+    rc = ph->mem.alloc(rc, h, kPeaks.create, (void **)&ph->res, nC * sizeof(int64_t));
+    return sub_done(rank_upload(rc, *ph, kPeaks, st), ph, out);
 }
 
 int slicer_peaks_run_npix(slicer_peaks_handle ph, const float *d_map, int32_t npix)
 {
-    if (!ph || !d_map)
-        return fail(ph ? ph->h : nullptr, SLICER_ERR_ARG, "slicer_peaks_run_npix: null argument");
-    if (npix < 1 || npix > ph->n)
-        return fail(ph->h, SLICER_ERR_ARG, "slicer_peaks_run_npix: npix = %d outside 1..%d", npix, ph->n);
     hipStream_t st;
-    if (int rc = sub_stream(ph->h, ph->device, &st))
+    if (int rc = rank_run_begin(ph, d_map, npix, kPeaks, &st))
         return rc;
-    ph->ran = false;
     const int nC = 3 * ph->B + kOutside;
     PeakArgs a{};
     a.x = d_map;
-    a.edges = ph->d_edges;
+    a.edges = ph->d_table;
     a.partial = ph->partial;
     a.n = npix;
     a.B = ph->B;
@@ -266,18 +224,16 @@ int slicer_peaks_run_npix(slicer_peaks_handle ph, const float *d_map, int32_t np
 
 int slicer_peaks_run(slicer_peaks_handle ph, const float *d_map)
 {
-    if (!ph || !d_map)
-        return fail(ph ? ph->h : nullptr, SLICER_ERR_ARG, "slicer_peaks_run: null argument");
+    if (int rc = rank_not_null(ph, d_map, kPeaks, ""))
+        return rc;
     return slicer_peaks_run_npix(ph, d_map, ph->n);
 }
 
 int slicer_peaks_read(slicer_peaks_handle ph, int64_t *pdf, int64_t *peaks, int64_t *minima, int64_t *below,
                       int64_t *above, int64_t *n_nan)
 {
-    if (!ph)
-        return fail(nullptr, SLICER_ERR_ARG, "slicer_peaks_read: null handle");
-    if (!ph->ran)
-        return fail(ph->h, SLICER_ERR_STATE, "slicer_peaks_read before any slicer_peaks_run");
+    if (int rc = rank_read_begin(ph, kPeaks))
+        return rc;
     const size_t B = (size_t)ph->B;
     return read_slices(*ph, ph->res, {{pdf, B}, {peaks, B}, {minima, B}, {below, 3}, {above, 3}, {n_nan, 1}});
 }

@@ -30,15 +30,17 @@
 // k_l1norm: a workgroup is one wave.  The map is a flat array cut into chunks of 512 pixels, workgroup g of G takes
 // chunks g, g + G, ... (G fixed by the handle: resident_groups), a lane pixels lane, lane + 64, ... of a chunk; the
 // loads of its next chunk are in flight while it bins the current one.  The
-// edges sit in LDS (rank_search of slicer_rank_counts.hpp, N10's); counts are u32 in LDS (integer atomics).  The sums
-// are C = 2^c copies of B + 2 f64 cells in LDS, lane l adds into copy l mod C, and the lanes of a wave take turns: in
+// edges sit in LDS (rank_search and pdf_slot of slicer_rank_counts.hpp, N10's); counts are u32 in LDS (integer
+// atomics).  The sums are C = 2^c copies of B + 2 f64 cells in LDS, lane l adds into copy l mod C, and the lanes of a
+// wave take turns: in
 // round r = 0 ... 64 / C - 1 the lanes with l / C = r add, plain read-add-write, no two of them into one cell.  So the
 // order of every cell's additions is fixed by the pixel indices alone.  C is the largest power of two <= 64 whose
 // copies fit in 32 KiB (64 bins: 32 copies, 2 rounds; 1024 bins: 2 copies, 32 rounds).  Flush: the copies of a cell
 // are added in index order into row g of partial sums [G][B + 2], the counts stored as row g of [G][B + 3];
-// k_l1norm_sums adds the rows of a column in a fixed order (sixteen threads take rows t, t + 16, ..., then thread 0
-// adds the sixteen in order), k_column_sums the counts in int64.  No floating-point atomics; every row and result is
-// stored by every launch.  All terms are non-negative, so whatever the order |sum - S| <= (count - 1) 2^-53 S (1 + ...).
+// k_column_sums<double, double> adds the rows of a column in a fixed order (sixteen threads take rows t, t + 16, ...,
+// then thread 0 adds the sixteen in order), k_column_sums<unsigned, int64_t> the counts.  No floating-point atomics;
+// every row and result is stored by every launch.  All terms are non-negative, so whatever the order
+// |sum - S| <= (count - 1) 2^-53 S (1 + ...).
 #include <hip/hip_runtime.h>
 
 #include "slicer_rank_counts.hpp"
@@ -210,8 +212,7 @@ __global__ __launch_bounds__(kL1Threads) void k_l1norm(L1Args a)
     double *edge = dyn;                // [B + 1]
     double *acc = dyn + (B + 1);       // [B + 2][1 << cl]: slot B is below, B + 1 above
     unsigned *cnt = reinterpret_cast<unsigned *>(acc + ((size_t)nS << cl));  // [B + 3]: ... and B + 2 the NaNs
-    for (int k = lane; k <= B; k += kL1Threads)
-        edge[k] = a.edges[k];
+    stage_table<kL1Threads>(edge, a.edges, B + 1);
     for (int k = lane; k < nS << cl; k += kL1Threads)
         acc[k] = 0.0;
     for (int k = lane; k < nC; k += kL1Threads)
@@ -246,15 +247,7 @@ __global__ __launch_bounds__(kL1Threads) void k_l1norm(L1Args a)
 #pragma unroll
         for (int q = 0; q < kL1Per; q++) {
             const double x = xd[q];
-            int slot;
-            if (x != x)
-                slot = B + 2;
-            else if (pos[q] == 0)
-                slot = B;  // below e_0
-            else if (x > eB)
-                slot = B + 1;  // above e_B
-            else
-                slot = pos[q] - 1;  // e_{B-1} <= x <= e_B gives pos = B: the last bin is closed
+            const int slot = pdf_slot(x, pos[q], eB, B, 1);  // a bin, or B: below, B + 1: above, B + 2: NaN
             if (in[q])
                 atomicAdd(&cnt[slot], 1u);
             const bool adds = in[q] && slot < nS;
@@ -272,42 +265,13 @@ __global__ __launch_bounds__(kL1Threads) void k_l1norm(L1Args a)
             cur[q] = nxt[q];
     }
     __syncthreads();
-    for (int s = lane; s < nS; s += kL1Threads) {
-        double sum = acc[(size_t)s << cl];
-        for (int c = 1; c < 1 << cl; c++)
-            sum = sum + acc[((size_t)s << cl) + c];
-        a.psum[(size_t)blockIdx.x * nS + s] = sum;
-    }
+    for (int s = lane; s < nS; s += kL1Threads)
+        a.psum[(size_t)blockIdx.x * nS + s] = fold_copies(acc, s, cl);
     for (int k = lane; k < nC; k += kL1Threads)
         a.pcnt[(size_t)blockIdx.x * nC + k] = cnt[k];
 }
 
-// Workgroup v sums columns 16 v ... 16 v + 15 of psum[G][nS] into sums[nS]: thread rg of a column's sixteen the rows
-// rg, rg + 16, ... in that order, then thread 0 of them the sixteen in order.
-__global__ __launch_bounds__(kThreads) void k_l1norm_sums(const double *psum, int G, int nS, double *sums)
-{
-    __shared__ double red[kFinRows][kFinCols];
-    const int cl = threadIdx.x % kFinCols, rg = threadIdx.x / kFinCols, col = (int)blockIdx.x * kFinCols + cl;
-    double acc = 0.0;
-    if (col < nS)
-        for (int g = rg; g < G; g += kFinRows)
-            acc = acc + psum[(size_t)g * nS + col];
-    red[rg][cl] = acc;
-    __syncthreads();
-    if (rg != 0 || col >= nS)
-        return;
-    for (int k = 1; k < kFinRows; k++)
-        acc = acc + red[k][cl];
-    sums[col] = acc;
-}
-
-int l1_copies_log2(int B)
-{
-    int cl = 0;
-    while (cl < 6 && ((size_t)(B + 2) * sizeof(double) << (cl + 1)) <= kL1CopyBytes)
-        cl++;
-    return cl;
-}
+int l1_copies_log2(int B) { return lg_copies((size_t)(B + 2) * sizeof(double), kL1CopyBytes, 6); }
 
 size_t l1_lds(int B, int cl)
 {
@@ -330,6 +294,9 @@ std::vector<std::vector<uint64_t>> starlet_tables(int J)
     return H;
 }
 
+const RankModule kL1Norm = {"slicer_l1norm", "slicer_l1norm_create", "edges", "fewer than 2 edges", 2, SLICER_PEAKS_MAX_BINS + 1,
+                            kMaxNpix};
+
 }  // namespace
 
 struct slicer_starlet : SubHandle {
@@ -339,15 +306,11 @@ struct slicer_starlet : SubHandle {
     int ran_n = 0;                       // npix of the last run, 0 before any
 };
 
-struct slicer_l1norm : SubHandle {
-    int n = 0, B = 0;
-    int gmax = 0, copies_log2 = 0;
-    std::vector<double> edges;
-    double *d_edges = nullptr;
+struct slicer_l1norm : RankHandle {  // table: the B + 1 edges
+    int B = 0, copies_log2 = 0;
     double *psum = nullptr, *sums = nullptr;
     unsigned *pcnt = nullptr;
     int64_t *counts = nullptr;
-    bool ran = false;
 };
 
 extern "C" {
@@ -484,62 +447,33 @@ int slicer_starlet_destroy(slicer_starlet_handle sh) { return sub_destroy(sh); }
 
 int slicer_l1norm_create(slicer_handle h, int32_t npix, int32_t n_edges, const double *edges, slicer_l1norm_handle *out)
 {
-    // the numbers first, in the order of slicer_peaks_create
-    const char *who = "slicer_l1norm_create";
-    if (out)
-        *out = nullptr;
-    if (int rc = npix_in_range(h, who, npix, kMaxNpix))
-        return rc;
-    if (n_edges < 2)
-        return fail(h, SLICER_ERR_ARG, "%s: fewer than 2 edges", who);
-    if (n_edges > SLICER_PEAKS_MAX_BINS + 1)
-        return fail(h, SLICER_ERR_ARG, "%s: %d edges, at most %d", who, n_edges, SLICER_PEAKS_MAX_BINS + 1);
-    if (!edges)
-        return fail(h, SLICER_ERR_ARG, "%s: null argument", who);
-    if (const char *what = ascending_fault(n_edges, edges))
-        return fail(h, SLICER_ERR_ARG, "%s: edges must be %s", who, what);
-    if (!h || !out)
-        return fail(h, SLICER_ERR_ARG, "%s: null argument", who);
     hipStream_t st = nullptr;
     slicer_l1norm_handle lh = nullptr;
-    if (int rc = sub_new(h, who, &st, &lh))
+    int rc = rank_create(h, kL1Norm, npix, n_edges, edges, out, &st, &lh);
+    if (!lh)
         return rc;
-    lh->n = npix;
+    const char *who = kL1Norm.create;
     lh->B = n_edges - 1;
     lh->copies_log2 = l1_copies_log2(lh->B);
     const uint64_t np2 = (uint64_t)npix * (uint64_t)npix;
     lh->gmax = resident_groups(l1_lds(lh->B, lh->copies_log2), (int64_t)((np2 + kL1Chunk - 1) / kL1Chunk), h->num_cus);
-    lh->edges.assign(edges, edges + n_edges);
     const size_t nS = (size_t)lh->B + 2, nC = (size_t)lh->B + 3;
-    int rc = SLICER_OK;
-    rc = lh->mem.alloc(rc, h, who, (void **)&lh->d_edges, (size_t)n_edges * sizeof(double));
     rc = lh->mem.alloc(rc, h, who, (void **)&lh->psum, (size_t)lh->gmax * nS * sizeof(double));
     rc = lh->mem.alloc(rc, h, who, (void **)&lh->pcnt, (size_t)lh->gmax * nC * sizeof(unsigned));
     rc = lh->mem.alloc(rc, h, who, (void **)&lh->sums, nS * sizeof(double));
     rc = lh->mem.alloc(rc, h, who, (void **)&lh->counts, nC * sizeof(int64_t));
-    if (rc == SLICER_OK) {
-        // (lh->edges outlives the copy)
-        hipError_t e = hipMemcpyAsync(lh->d_edges, lh->edges.data(), (size_t)n_edges * sizeof(double), hipMemcpyHostToDevice, st);
-        if (e != hipSuccess)
-            rc = fail(h, SLICER_ERR_HIP, "%s: copying the edges: %s", who, hipGetErrorString(e));
-    }
-    return sub_done(rc, lh, out);
+    return sub_done(rank_upload(rc, *lh, kL1Norm, st), lh, out);
 }
 
 int slicer_l1norm_run_npix(slicer_l1norm_handle lh, const float *d_map, int32_t npix)
 {
-    if (!lh || !d_map)
-        return fail(lh ? lh->h : nullptr, SLICER_ERR_ARG, "slicer_l1norm_run_npix: null argument");
-    if (npix < 1 || npix > lh->n)
-        return fail(lh->h, SLICER_ERR_ARG, "slicer_l1norm_run_npix: npix = %d outside 1..%d", npix, lh->n);
     hipStream_t st;
-    if (int rc = sub_stream(lh->h, lh->device, &st))
+    if (int rc = rank_run_begin(lh, d_map, npix, kL1Norm, &st))
         return rc;
-    lh->ran = false;
     const int nS = lh->B + 2, nC = lh->B + 3;
     L1Args a{};
     a.x = d_map;
-    a.edges = lh->d_edges;
+    a.edges = lh->d_table;
     a.psum = lh->psum;
     a.pcnt = lh->pcnt;
     a.npixels = (uint64_t)npix * (uint64_t)npix;
@@ -554,8 +488,7 @@ int slicer_l1norm_run_npix(slicer_l1norm_handle lh, const float *d_map, int32_t 
     }
     {
         ProfScope ps(lh->h, KN_L1NORM_FINISH);
-        hipLaunchKernelGGL(k_l1norm_sums, dim3((unsigned)((nS + kFinCols - 1) / kFinCols)), dim3(kThreads), 0, st, lh->psum, G,
-                           nS, lh->sums);
+        launch_column_sums(st, lh->psum, G, nS, lh->sums);
         launch_column_sums(st, lh->pcnt, G, nC, lh->counts);
         HIPCHK(lh->h, hipGetLastError());
     }
@@ -565,18 +498,16 @@ int slicer_l1norm_run_npix(slicer_l1norm_handle lh, const float *d_map, int32_t 
 
 int slicer_l1norm_run(slicer_l1norm_handle lh, const float *d_map)
 {
-    if (!lh || !d_map)
-        return fail(lh ? lh->h : nullptr, SLICER_ERR_ARG, "slicer_l1norm_run: null argument");
+    if (int rc = rank_not_null(lh, d_map, kL1Norm, ""))
+        return rc;
     return slicer_l1norm_run_npix(lh, d_map, lh->n);
 }
 
 int slicer_l1norm_read(slicer_l1norm_handle lh, int64_t *counts, double *sums, int64_t *below, int64_t *above,
                        int64_t *n_nan, double *below_sum, double *above_sum)
 {
-    if (!lh)
-        return fail(nullptr, SLICER_ERR_ARG, "slicer_l1norm_read: null handle");
-    if (!lh->ran)
-        return fail(lh->h, SLICER_ERR_STATE, "slicer_l1norm_read before any slicer_l1norm_run");
+    if (int rc = rank_read_begin(lh, kL1Norm))
+        return rc;
     const size_t B = (size_t)lh->B;
     if (int rc = read_slices(*lh, lh->counts, {{counts, B}, {below, 1}, {above, 1}, {n_nan, 1}}))
         return rc;

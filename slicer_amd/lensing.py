@@ -71,6 +71,31 @@ class _SubHandle:
         self.close()
 
 
+class _MapRuns:
+    """run, run_kappa and run_level of a sub-handle whose runs take one f32 device map of at most its own npix: _run and
+    _run_npix name the two C calls.  A class that keeps last_npix (the map size of the last run) has it recorded."""
+    _run = _run_npix = None
+
+    def run(self, d_map, npix=None):
+        """d_map: device address of an f32 map of npix^2 pixels (None: the handle's npix; otherwise at most that)."""
+        d = None if d_map is None else int(d_map)
+        handle = getattr(self, self._handle)
+        if npix is None:
+            self._s._chk(getattr(_L, self._run)(handle, d))
+        else:
+            self._s._chk(getattr(_L, self._run_npix)(handle, d, int(npix)))
+        if hasattr(self, "last_npix"):
+            self.last_npix = self.npix if npix is None else int(npix)
+
+    def run_kappa(self, kappa: "Kappa", s):
+        """The map of source s of a Kappa accumulator, where it is."""
+        self.run(kappa.device_map(s), kappa.npix)
+
+    def run_level(self, moments: "Moments", level):
+        """Level `level` >= 1 of the last run of a Moments pyramid, where it is (level 0 is the caller's own map)."""
+        self.run(moments.device_map(level), moments.npix >> int(level))
+
+
 def _plane_args(ld, ld2, zsnap, sources):
     """(ld, ld2, zsnap, zs, P, S) as slicer_lensing_* take them; zs is None for sources "all", and then S = P."""
     ld, ld2, zsnap = (np.ascontiguousarray(a, np.float64) for a in (ld, ld2, zsnap))
@@ -444,10 +469,11 @@ def peaks_edges(lo, hi, bins):
     return e
 
 
-class Peaks(_SubHandle):
+class Peaks(_MapRuns, _SubHandle):
     """One-point PDF histogram and the counts of peaks and minima by height of an npix^2 map over the f64 `edges`, on
     the device of `slicer`, on its stream.  Every count is an exact int64."""
     _handle, _destroy = "_ph", "slicer_peaks_destroy"
+    _run, _run_npix = "slicer_peaks_run", "slicer_peaks_run_npix"
 
     def __init__(self, slicer: Slicer, npix, edges):
         self._s = slicer
@@ -457,22 +483,6 @@ class Peaks(_SubHandle):
         ph = C.c_void_p()
         slicer._chk(_L.slicer_peaks_create(slicer._h, self.npix, self.edges.size, _dptr(self.edges), C.byref(ph)))
         self._ph = ph
-
-    def run(self, d_map, npix=None):
-        """d_map: device address of an f32 map of npix^2 pixels (None: the handle's npix; otherwise at most that)."""
-        d = None if d_map is None else int(d_map)
-        if npix is None:
-            self._s._chk(_L.slicer_peaks_run(self._ph, d))
-        else:
-            self._s._chk(_L.slicer_peaks_run_npix(self._ph, d, int(npix)))
-
-    def run_kappa(self, kappa: Kappa, s):
-        """The map of source s of a Kappa accumulator, where it is."""
-        self.run(kappa.device_map(s), kappa.npix)
-
-    def run_level(self, moments: Moments, level):
-        """Level `level` >= 1 of the last run of a Moments pyramid, where it is (level 0 is the caller's own map)."""
-        self.run(moments.device_map(level), moments.npix >> int(level))
 
     def read(self):
         """dict: edges [B+1], pdf, peaks, minima (int64 [B]), below, above (int64 [3]: pdf, peaks, minima), nan."""
@@ -488,11 +498,12 @@ class Peaks(_SubHandle):
 MINKOWSKI_MAX_THRESHOLDS = 1025
 
 
-class Minkowski(_SubHandle):
+class Minkowski(_MapRuns, _SubHandle):
     """The Minkowski functionals of the excursion sets x >= t_j of an npix^2 map over the f64 `thresholds`, as exact
     int64 counts of the faces, edges and vertices of the pixel complex, on the device of `slicer`, on its stream
     (DESIGN.md S8 row N14).  peaks_edges(lo, hi, bins) gives bins + 1 uniform thresholds."""
     _handle, _destroy = "_mh", "slicer_minkowski_destroy"
+    _run, _run_npix = "slicer_minkowski_run", "slicer_minkowski_run_npix"
 
     def __init__(self, slicer: Slicer, npix, thresholds):
         self._s = slicer
@@ -504,23 +515,6 @@ class Minkowski(_SubHandle):
                                                C.byref(mh)))
         self._mh = mh
         self.last_npix = None  # of the last run
-
-    def run(self, d_map, npix=None):
-        """d_map: device address of an f32 map of npix^2 pixels (None: the handle's npix; otherwise at most that)."""
-        d = None if d_map is None else int(d_map)
-        if npix is None:
-            self._s._chk(_L.slicer_minkowski_run(self._mh, d))
-        else:
-            self._s._chk(_L.slicer_minkowski_run_npix(self._mh, d, int(npix)))
-        self.last_npix = self.npix if npix is None else int(npix)
-
-    def run_kappa(self, kappa: Kappa, s):
-        """The map of source s of a Kappa accumulator, where it is."""
-        self.run(kappa.device_map(s), kappa.npix)
-
-    def run_level(self, moments: Moments, level):
-        """Level `level` >= 1 of the last run of a Moments pyramid, where it is (level 0 is the caller's own map)."""
-        self.run(moments.device_map(level), moments.npix >> int(level))
 
     def read(self):
         """dict: thresholds [T], faces, edges, vertices, boundary, border and euler = vertices - edges + faces (int64
@@ -559,12 +553,13 @@ BETTI_MAX_THRESHOLDS = 1025
 BETTI_MAX_NPIX = 32768
 
 
-class Betti(_SubHandle):
+class Betti(_MapRuns, _SubHandle):
     """The Betti numbers of the excursion sets x >= t_j of an npix^2 map over the f64 `thresholds`, as exact int64
     counts: the 8-connected components of every set and its holes (the 4-connected components of the complement that
     do not touch the map's rim), on the device of `slicer`, on its stream.  components - holes
     is Minkowski's euler of the same map and thresholds.  peaks_edges(lo, hi, bins) gives bins + 1 uniform thresholds."""
     _handle, _destroy = "_bh", "slicer_betti_destroy"
+    _run, _run_npix = "slicer_betti_run", "slicer_betti_run_npix"
 
     def __init__(self, slicer: Slicer, npix, thresholds):
         self._s = slicer
@@ -576,23 +571,6 @@ class Betti(_SubHandle):
                                            C.byref(bh)))
         self._bh = bh
         self.last_npix = None  # of the last run
-
-    def run(self, d_map, npix=None):
-        """d_map: device address of an f32 map of npix^2 pixels (None: the handle's npix; otherwise at most that)."""
-        d = None if d_map is None else int(d_map)
-        if npix is None:
-            self._s._chk(_L.slicer_betti_run(self._bh, d))
-        else:
-            self._s._chk(_L.slicer_betti_run_npix(self._bh, d, int(npix)))
-        self.last_npix = self.npix if npix is None else int(npix)
-
-    def run_kappa(self, kappa: Kappa, s):
-        """The map of source s of a Kappa accumulator, where it is."""
-        self.run(kappa.device_map(s), kappa.npix)
-
-    def run_level(self, moments: Moments, level):
-        """Level `level` >= 1 of the last run of a Moments pyramid, where it is (level 0 is the caller's own map)."""
-        self.run(moments.device_map(level), moments.npix >> int(level))
 
     def read(self):
         """dict: thresholds [T], components, holes, faces (int64 [T], one value per threshold), nan, and npix: the map
@@ -716,12 +694,13 @@ def smooth_weights(sigma_pix, truncate=4.0):
     return R.value, g, h
 
 
-class Smooth(_SubHandle):
+class Smooth(_MapRuns, _SubHandle):
     """An npix^2 map filtered with a Gaussian of sigma_pix pixels truncated at `truncate` sigma and renormalised at the
     map's edges (kind "gauss"), or with the aperture-mass filter (1 - r^2 / 2 s^2) exp(-r^2 / 2 s^2) / (2 pi s^2) built
     from it (kind "map"), on the device of `slicer`, on its stream (DESIGN.md S8 row N12).  The map does not wrap;
     radius is the filter's reach in pixels."""
     _handle, _destroy = "_sh", "slicer_smooth_destroy"
+    _run, _run_npix = "slicer_smooth_run", "slicer_smooth_run_npix"
 
     def __init__(self, slicer: Slicer, npix, kind="gauss", sigma_pix=1.0, truncate=4.0):
         if kind not in _SMOOTH_KINDS:
@@ -734,23 +713,6 @@ class Smooth(_SubHandle):
                                             C.byref(sh)))
         self._sh = sh
         self.radius = smooth_weights(self.sigma_pix, self.truncate)[0]
-
-    def run(self, d_map, npix=None):
-        """d_map: device address of an f32 map of npix^2 pixels (None: the handle's npix; otherwise at most that)."""
-        d = None if d_map is None else int(d_map)
-        if npix is None:
-            self._s._chk(_L.slicer_smooth_run(self._sh, d))
-        else:
-            self._s._chk(_L.slicer_smooth_run_npix(self._sh, d, int(npix)))
-        self.last_npix = self.npix if npix is None else int(npix)
-
-    def run_kappa(self, kappa: Kappa, s):
-        """The map of source s of a Kappa accumulator, where it is."""
-        self.run(kappa.device_map(s), kappa.npix)
-
-    def run_level(self, moments: Moments, level):
-        """Level `level` >= 1 of the last run of a Moments pyramid, where it is (level 0 is the caller's own map)."""
-        self.run(moments.device_map(level), moments.npix >> int(level))
 
     def device_map(self):
         """Device address of the last run's output, f32 [n, n] for the n of that run."""
@@ -869,11 +831,12 @@ def starlet_gains(scales):
     return g, coarse.value
 
 
-class Starlet(_SubHandle):
+class Starlet(_MapRuns, _SubHandle):
     """The starlet transform (isotropic undecimated wavelet transform, B3-spline a trous, mirrored edges) of an npix^2
     map into `scales` wavelet maps w_1 ... w_J and one coarse map that sum back to it, on the device of `slicer`, on its
     stream.  Scale j reaches 2 * 2^j pixels; scale 0 names the coarse map."""
     _handle, _destroy = "_sh", "slicer_starlet_destroy"
+    _run, _run_npix = "slicer_starlet_run", "slicer_starlet_run_npix"
 
     def __init__(self, slicer: Slicer, npix, scales):
         self._s = slicer
@@ -882,23 +845,6 @@ class Starlet(_SubHandle):
         sh = C.c_void_p()
         slicer._chk(_L.slicer_starlet_create(slicer._h, self.npix, self.scales, C.byref(sh)))
         self._sh = sh
-
-    def run(self, d_map, npix=None):
-        """d_map: device address of an f32 map of npix^2 pixels (None: the handle's npix; otherwise at most that)."""
-        d = None if d_map is None else int(d_map)
-        if npix is None:
-            self._s._chk(_L.slicer_starlet_run(self._sh, d))
-        else:
-            self._s._chk(_L.slicer_starlet_run_npix(self._sh, d, int(npix)))
-        self.last_npix = self.npix if npix is None else int(npix)
-
-    def run_kappa(self, kappa: Kappa, s):
-        """The map of source s of a Kappa accumulator, where it is."""
-        self.run(kappa.device_map(s), kappa.npix)
-
-    def run_level(self, moments: Moments, level):
-        """Level `level` >= 1 of the last run of a Moments pyramid, where it is (level 0 is the caller's own map)."""
-        self.run(moments.device_map(level), moments.npix >> int(level))
 
     def device_map(self, scale):
         """Device address of w_scale (1 ... scales) or of the coarse map (0) of the last run, f32 [n, n] for its n."""
@@ -918,11 +864,12 @@ class Starlet(_SubHandle):
         return [self.read(j) for j in range(self.scales + 1)]
 
 
-class L1Norm(_SubHandle):
+class L1Norm(_MapRuns, _SubHandle):
     """Per bin of the f64 `edges` (Peaks' rule: the last bin closed) the exact int64 count of an npix^2 map's pixels
     and the f64 sum of their |x|, on the device of `slicer`, on its stream: on the scales of a
     Starlet, the starlet l1-norm."""
     _handle, _destroy = "_lh", "slicer_l1norm_destroy"
+    _run, _run_npix = "slicer_l1norm_run", "slicer_l1norm_run_npix"
 
     def __init__(self, slicer: Slicer, npix, edges):
         self._s = slicer
@@ -932,14 +879,6 @@ class L1Norm(_SubHandle):
         lh = C.c_void_p()
         slicer._chk(_L.slicer_l1norm_create(slicer._h, self.npix, self.edges.size, _dptr(self.edges), C.byref(lh)))
         self._lh = lh
-
-    def run(self, d_map, npix=None):
-        """d_map: device address of an f32 map of npix^2 pixels (None: the handle's npix; otherwise at most that)."""
-        d = None if d_map is None else int(d_map)
-        if npix is None:
-            self._s._chk(_L.slicer_l1norm_run(self._lh, d))
-        else:
-            self._s._chk(_L.slicer_l1norm_run_npix(self._lh, d, int(npix)))
 
     def run_scale(self, starlet: Starlet, scale):
         """Scale `scale` of the last run of a Starlet, where it is."""

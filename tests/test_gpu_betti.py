@@ -297,6 +297,31 @@ def test_nan_and_infinite_pixels(slicer):
         assert k >= 1 and np.all(got["components"][:k] == 1) and not got["components"][k:].any() and not got["holes"].any()
 
 
+@functools.lru_cache(maxsize=1)
+def speckled_map():
+    """White noise of 67^2 = 4489 pixels -- the last quad of k_betti_rank holds one pixel, which the float4 kernel loads
+    on its scalar path -- with a few NaN, +inf and -inf pixels, that last pixel among them."""
+    x = make_map(67, "white").copy()
+    x[3, 5] = x[40, 66] = x[66, 66] = np.nan
+    x[0, 0] = x[30, 31] = np.inf
+    x[66, 0] = x[12, 60] = -np.inf
+    x.setflags(write=False)
+    return x
+
+
+# k_betti_rank keeps its T + 1 u32 rank counters in 2^c copies, c the largest <= 5 with 4 (T + 1) 2^c <= 16384 B (lg_copies
+# of slicer_rank_counts.hpp): 32 copies up to T = 127, 16 up to 255, 8 up to 511, 4 up to 1023, 2 above.  The last and the
+# first T of every count; the fold of the copies at the flush has to give the counts of one copy.
+@pytest.mark.parametrize("T", [127, 128, 255, 256, 511, 512, 1023, 1024, 1025])
+def test_counts_at_every_number_of_counter_copies(slicer, T):
+    x = speckled_map()
+    t = make_thresholds("white", T, "uniform")
+    got, ref = run(slicer, x, t), BT.counts(x, t)
+    for k in BT.KEYS:
+        assert np.array_equal(got[k], ref[k]), (T, k, got[k], ref[k])
+    assert got["nan"] == 3 and got["faces"][0] > got["faces"][-1] >= 2
+
+
 @pytest.mark.parametrize("n", [64, 129])
 def test_an_input_off_the_16_byte_grid_gives_the_same_counts(slicer, n):
     x = make_map(n, "lognormal")

@@ -1,6 +1,6 @@
-"""Return codes and exact slicer_last_error texts of the ten add-on sub-handles (kappa, shear, power, moments, peaks,
-rays, smooth, noise, minkowski, bispectrum): what their entry points answer without a handle, and -- on the GPU -- before
-any run and for a map size outside the handle's.  The texts are not uniform (kappa, shear, power and bispectrum look at
+"""Return codes and exact slicer_last_error texts of twelve add-on sub-handles (kappa, shear, power, moments, peaks,
+rays, smooth, noise, minkowski, bispectrum, l1norm, betti): what their entry points answer without a handle, and -- on the
+GPU -- before any run and for a map size outside the handle's.  The texts are not uniform (kappa, shear, power and bispectrum look at
 the handle first, the others at the numbers) and are pinned as they are.  Messages of failed HIP calls carry a source
 position and are not pinned here."""
 import ctypes as C
@@ -13,7 +13,8 @@ from slicer_amd import lensing
 
 L = lensing._L
 OK, ERR_ARG, ERR_STATE, ERR_UNSUPPORTED = 0, 2, 3, 6
-MAX = 131072  # the largest npix of the modules that have one
+MAX = 131072  # the largest npix of the modules that have one, but Betti's
+BETTI_MAX = 32768  # SLICER_BETTI_MAX_NPIX
 EDGES = np.array([1.0, 3.0, 5.0])
 E = EDGES.ctypes.data
 BUF = np.zeros(64)
@@ -25,7 +26,7 @@ def _err(h=None):
 
 
 # ---- *_create without a handle -------------------------------------------------------------------
-# name: (the arguments after npix of a well-formed call, numbers checked before the handle)
+# name: (the arguments after npix of a well-formed call, numbers checked before the handle[, the largest npix])
 CREATE = {
     "kappa": ((1,), False),
     "shear": ((5.0,), False),
@@ -37,25 +38,58 @@ CREATE = {
     "noise": ((7,), True),
     "minkowski": ((3, E), True),
     "bispectrum": ((5.0, 3, E, 4, None), False),
+    "l1norm": ((3, E), True),
+    "betti": ((3, E), True, BETTI_MAX),
 }
 
 
 @pytest.mark.parametrize("null_out", [False, True])
 @pytest.mark.parametrize("name", list(CREATE))
 def test_create_without_a_handle(name, null_out):
-    args, numbers_first = CREATE[name]
+    args, numbers_first, largest = (CREATE[name] + (MAX,))[:3]
     create = getattr(L, f"slicer_{name}_create")
     who = f"slicer_{name}_create: "
     expected = {0: (ERR_ARG, who + "npix must be positive"),
-                MAX + 1: (ERR_UNSUPPORTED, who + f"npix = {MAX + 1} above {MAX}"),
+                largest + 1: (ERR_UNSUPPORTED, who + f"npix = {largest + 1} above {largest}"),
                 16: (ERR_ARG, who + "null argument")}
-    for npix in (0, MAX + 1, 16):
+    for npix in (0, largest + 1, 16):
         out = C.c_void_p(1)
         code, text = expected[npix if numbers_first else 16]
         assert create(None, npix, *args, None if null_out else C.byref(out)) == code, npix
         assert _err() == text
         # the numbers-first modules clear *out before anything else; the others return before they touch it
         assert out.value == (1 if null_out or not numbers_first else None)
+
+
+# the four that take an ascending f64 table: (what its values are called, the refusal of too few, the most of them)
+TABLES = {
+    "peaks": ("edges", "fewer than 2 edges", 1025),
+    "l1norm": ("edges", "fewer than 2 edges", 1025),
+    "minkowski": ("thresholds", "fewer than 1 threshold", 1025),
+    "betti": ("thresholds", "fewer than 1 threshold", 1025),
+}
+
+
+@pytest.mark.parametrize("name", list(TABLES))
+def test_create_looks_at_the_table_before_the_handle(name):
+    nouns, too_few, most = TABLES[name]
+    create = getattr(L, f"slicer_{name}_create")
+    who = f"slicer_{name}_create: "
+    long, inf, nan, tie = (np.array(v, np.float64) for v in (np.arange(most + 1), [1, np.inf, 5], [1, np.nan, 5], [1, 3, 3]))
+    cases = [((0, E), who + too_few), ((-1, E), who + too_few),
+             ((most + 1, long.ctypes.data), who + f"{most + 1} {nouns}, at most {most}"),
+             ((3, None), who + "null argument"),
+             ((3, inf.ctypes.data), who + f"{nouns} must be finite"),
+             ((3, nan.ctypes.data), who + f"{nouns} must be finite"),
+             ((3, tie.ctypes.data), who + f"{nouns} must be strictly ascending"),
+             ((most, long.ctypes.data), who + "null argument")]  # a table that is taken: now the handle is missed
+    if too_few.startswith("fewer than 2"):
+        cases.append(((1, E), who + too_few))
+    for args, text in cases:
+        out = C.c_void_p(1)
+        assert create(None, 16, *args, C.byref(out)) == ERR_ARG, args
+        assert _err() == text
+        assert out.value is None
 
 
 @pytest.mark.parametrize("name", list(CREATE))
@@ -120,6 +154,12 @@ NULL_HANDLE = [
     ("slicer_bispectrum_read", (P, None, None), "slicer_bispectrum_read: null handle"),
     ("slicer_bispectrum_spectrum", (P,), "slicer_bispectrum_spectrum: null argument"),
     ("slicer_bispectrum_read_map", (0, P), "slicer_bispectrum_read_map: null argument"),
+    ("slicer_l1norm_run", (P,), "slicer_l1norm_run: null argument"),
+    ("slicer_l1norm_run_npix", (P, 16), "slicer_l1norm_run_npix: null argument"),
+    ("slicer_l1norm_read", (P, None, None, None, None, None, None), "slicer_l1norm_read: null handle"),
+    ("slicer_betti_run", (P,), "slicer_betti_run: null argument"),
+    ("slicer_betti_run_npix", (P, 16), "slicer_betti_run_npix: null argument"),
+    ("slicer_betti_read", (P, None, None, None), "slicer_betti_read: null handle"),
 ]
 
 
@@ -177,12 +217,16 @@ def test_moments_before_any_run(slicer):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", ["peaks", "minkowski"])
+@pytest.mark.parametrize("name", ["peaks", "minkowski", "l1norm", "betti"])
 def test_counts_before_any_run_and_npix_outside(slicer, d_zeros, name):
+    outputs = {"peaks": 6, "minkowski": 6, "l1norm": 7, "betti": 4}[name]  # arrays a *_read takes
     handle = _made(slicer, name, 3, E)
     try:
-        _state(slicer, getattr(L, f"slicer_{name}_read")(handle, P, None, None, None, None, None),
+        _state(slicer, getattr(L, f"slicer_{name}_read")(handle, P, *[None] * (outputs - 1)),
                f"slicer_{name}_read before any slicer_{name}_run")
+        for run, more in (("run", ()), ("run_npix", (N,))):  # a handle, but no map
+            assert getattr(L, f"slicer_{name}_{run}")(handle, None, *more) == ERR_ARG
+            assert _err(slicer._h) == f"slicer_{name}_{run}: null argument"
         _run_npix_refusals(slicer, name, handle, d_zeros)
     finally:
         assert getattr(L, f"slicer_{name}_destroy")(handle) == OK
