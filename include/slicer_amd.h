@@ -180,7 +180,23 @@ int slicer_libc_rand_state_set(const uint32_t *v31);
 int slicer_rand_stream_set(slicer_handle h, const uint32_t *v31);
 int slicer_rand_stream_get(slicer_handle h, uint32_t *v31);
 
-/* Use an existing hipStream_t (e.g. the caller framework's current stream); NULL = handle-owned. */
+/* The stream that this handle and every sub-handle made from it (slicer_kappa_*, slicer_smooth_*, ...) enqueue on.
+ *   hip_stream   an existing hipStream_t of the handle's device, e.g. the caller framework's current stream.  NULL is
+ *                the stream the handle created for itself (a blocking stream, what a new handle works on), NOT HIP's
+ *                default stream: a handle never works on the default stream.  Its own stream is a blocking one, so it
+ *                is ordered with the legacy default stream by HIP's rule for blocking streams.
+ *   refused      null handle: SLICER_ERR_ARG.  Between slicer_plane_begin and slicer_plane_finalize (file open or
+ *                not): SLICER_ERR_STATE -- a pass runs on one stream.  Accepted on a new handle and from
+ *                slicer_plane_finalize on (slicer_plane_read finalizes, also where it ends in
+ *                SLICER_ERR_NEGATIVE_COORD), while the maps of that pass stay readable.
+ *   ordering     a call that changes the stream orders the new stream behind everything the handle and its sub-handles
+ *                queued on the old one so far (one event recorded there, one hipStreamWaitEvent here; no host wait):
+ *                maps finalized, tables uploaded by a *_create, results of a *_run on the old stream are complete
+ *                for whatever is enqueued or read through the handle afterwards.  The old stream must still exist.
+ *                A sub-handle has no stream of its own: "the stream of h" in the comments below is the one h has
+ *                when the call is made, at its *_create and at every later call, so a sub-handle may be created
+ *                before or after a switch.  Setting the stream it already has does nothing.  Work the CALLER queued on either stream is ordered
+ *                by the streams themselves as usual. */
 int slicer_set_stream(slicer_handle h, void *hip_stream);
 
 int slicer_plane_begin(slicer_handle h, const slicer_plane_desc *desc);
@@ -311,7 +327,7 @@ int slicer_lensing_weights(double omega_m, double omega_lambda, double w0, doubl
                            const double *zsnap, int32_t n_sources, const double *zs, double *coeff, double *zlo,
                            double *zup, double *zl, double *chil);
 
-/* Device accumulator of n_sources kappa maps of npix^2 pixels, on the device and stream of h (create it after any
+/* Device accumulator of n_sources kappa maps of npix^2 pixels, on the device and stream of h (h's current one:
  * slicer_set_stream; destroy it before h).  Every call is enqueued on that stream with no host synchronisation, except
  * _plane_means and _read, which wait for it.
  *   slicer_kappa_add       n_maps (1..SLICER_MAX_PLANES) device f32 maps, e.g. slicer_plane_device_maps of a finalized
@@ -337,7 +353,7 @@ int slicer_kappa_destroy(slicer_kappa_handle kh);
  * K0 = 2 pi fftfreq(npix, d) along i0, K1 = 2 pi rfftfreq(npix, d) along i1, k^2 = K0^2 + K1^2 (every quotient 0 at 0),
  *   khat = rfft2(kappa);  phi = irfft2(-2 khat / k^2);  gamma1 = irfft2(khat (K0^2 - K1^2) / k^2);
  *   gamma2 = irfft2(khat 2 K0 K1 / k^2);  |gamma| = sqrt(gamma1^2 + gamma2^2),  irfft2 with s = (npix, npix),
- * computed in f64 and rounded once to f32, on the device and stream of h (create it after any slicer_set_stream;
+ * computed in f64 and rounded once to f32, on the device and stream of h (h's current one: slicer_set_stream;
  * destroy it before h).  Supported: 2 <= npix <= 16384 with prime factors 2, 3, 5, 7 only (slicer_shear_supported, host
  * only); others return SLICER_ERR_UNSUPPORTED.  angle_deg <= 0 or not finite: SLICER_ERR_ARG.
  *   slicer_shear_run         any device f32 npix^2 map (e.g. slicer_kappa_device_map); enqueued, no synchronisation
@@ -421,7 +437,7 @@ int slicer_fd_derivatives(slicer_handle h, int32_t npix, double spacing, const f
  *   counts[b] = N_b,  mean_radius[b] = mean of sqrt(m2) over the bin (NaN if N_b = 0),
  *   C_st,b = theta^2 / npix^4 * (1 / N_b) * sum over the bin of Re(khat_s conj khat_t)   (NaN if N_b = 0).
  *   slicer_power_bins      N_b and the mean radii, host only (no device); messages through slicer_last_error(NULL)
- *   slicer_power_create    on the device and stream of h (create it after any slicer_set_stream, destroy it before h);
+ *   slicer_power_create    on the device and stream of h (h's current one: slicer_set_stream, destroy it before h);
  *                          reads the shear_split option.  cross = 0: the n_maps auto-spectra; cross = 1: all
  *                          n_maps (n_maps + 1) / 2 pairs (0,0), (0,1), ..., (0,S-1), (1,1), ...  Refused before any
  *                          allocation: npix that slicer_shear_supported rejects or n_maps outside 1..128
@@ -469,7 +485,7 @@ int slicer_power_destroy(slicer_power_handle ph);
  * Bounds, u = 2^-53, A_k = sum_i |x_i - c|^k:  |S_k - exact| <= (2k - 1 + D) u (1 + 2^-20) A_k  (the rounding of d
  * k-fold, k - 1 products, D additions);  |mu - exact| <= (D + 2) u mean|x_i|.
  *   slicer_moments_depth     D(npix), host only; -1 for npix outside 1..131072 (message through slicer_last_error(NULL))
- *   slicer_moments_create    on the device and stream of h (create it after any slicer_set_stream, destroy it before
+ *   slicer_moments_create    on the device and stream of h (h's current one: slicer_set_stream, destroy it before
  *                            h); allocates the level maps.  The numbers are checked before the handle, so that they
  *                            can be checked without a device: npix < 1, levels outside 0..floor(log2 npix), a mode that
  *                            is neither SLICER_HALVE_*: SLICER_ERR_ARG; npix > 131072: SLICER_ERR_UNSUPPORTED
@@ -510,7 +526,7 @@ int slicer_moments_destroy(slicer_moments_handle mh);
  *                           rounded once to f64, no FMA.  SLICER_ERR_ARG (message through slicer_last_error(NULL)):
  *                           bins outside 1..1024, lo or hi not finite, a NULL array, edges that are not finite and
  *                           strictly ascending after rounding
- *   slicer_peaks_create     on the device and stream of h (create it after any slicer_set_stream, destroy it before h).
+ *   slicer_peaks_create     on the device and stream of h (h's current one: slicer_set_stream, destroy it before h).
  *                           The numbers are checked before the handle, so that they can be checked without a device:
  *                           npix < 1, fewer than 2 or more than 1025 edges, an edge that is not finite, edges not
  *                           strictly ascending: SLICER_ERR_ARG; npix > 131072: SLICER_ERR_UNSUPPORTED.  Device memory:
@@ -555,7 +571,7 @@ int slicer_peaks_destroy(slicer_peaks_handle ph);
  * its holes (the 4-connected components of the complement that do not reach outside the map); it is not stored here.
  * All counts are int64 and exact; the same input gives the same numbers on every run; there is no floating-point
  * accumulation anywhere.
- *   slicer_minkowski_create    on the device and stream of h (create it after any slicer_set_stream, destroy it before
+ *   slicer_minkowski_create    on the device and stream of h (h's current one: slicer_set_stream, destroy it before
  *                              h).  The numbers are checked before the handle, so that they can be checked without a
  *                              device: npix < 1, fewer than 1 or more than 1025 thresholds, a threshold that is not
  *                              finite, thresholds not strictly ascending: SLICER_ERR_ARG; npix > 131072:
@@ -600,7 +616,7 @@ int slicer_minkowski_destroy(slicer_minkowski_handle mh);
  *                                lookup of -l1 - l2.  Bad edges are refused as by slicer_power_bins, npix outside
  *                                1..16384 and a bad triple with SLICER_ERR_ARG; more than 2^31 mode pairs (the sum of
  *                                N_i N_j over the triples, N the full-plane modes of a bin): SLICER_ERR_UNSUPPORTED
- *   slicer_bispectrum_create     on the device and stream of h (create it after any slicer_set_stream, destroy it before
+ *   slicer_bispectrum_create     on the device and stream of h (h's current one: slicer_set_stream, destroy it before
  *                                h); reads the shear_split option.  Refused before any allocation: an npix that
  *                                slicer_shear_supported rejects, more than 32 bins or more than 2^20 triples
  *                                (SLICER_ERR_UNSUPPORTED); bad edges, a bad triple, an angle that is not positive and
@@ -638,7 +654,7 @@ int slicer_bispectrum_destroy(slicer_bispectrum_handle bh);
 
 /* ---- Multi-plane ray tracing through the lens planes ----
  * One ray per pixel of an npix^2 grid (axis 0 slow = component 1, axis 1 contiguous = component 2, as for N6 and N8), on the
- * device and stream of h (create it after any slicer_set_stream, destroy it before h).  State per ray, 12 f64: position
+ * device and stream of h (h's current one: slicer_set_stream, destroy it before h).  State per ray, 12 f64: position
  * b = (b1, b2) and direction t = (t1, t2) in pixel units, centred (b = beta / d, d = the spacing in radians per pixel,
  * h = (npix - 1) / 2), and the 2 x 2 matrices A = d beta / d theta and T = d t / d theta.  Start: the ray of pixel (i, j)
  * has b = t = (i - h, j - h), A = T = I; the last plane distance is chi = 0.  Every operation below is one IEEE f64
@@ -723,7 +739,7 @@ int slicer_lensing_plane_strengths(double omega_m, double omega_lambda, double w
  *   slicer_smooth_weights     host only: the radius and the tables g, h [radius + 1] (any of the three may be NULL).
  *                             SLICER_ERR_ARG (message through slicer_last_error(NULL)): s or t not finite or out of range,
  *                             R < 1; SLICER_ERR_UNSUPPORTED: R > 128 (run a wider filter on a level of the moments pyramid)
- *   slicer_smooth_create      on the device and stream of h (create it after any slicer_set_stream, destroy it before h).
+ *   slicer_smooth_create      on the device and stream of h (h's current one: slicer_set_stream, destroy it before h).
  *                             The numbers are checked before the handle, so that they can be checked without a device:
  *                             npix < 1, an unknown kind and the refusals of slicer_smooth_weights; npix > 131072:
  *                             SLICER_ERR_UNSUPPORTED.  Device memory: 4 bytes a pixel of output, 8 (GAUSS) or 16 (MAP) of
@@ -774,7 +790,7 @@ int slicer_smooth_destroy(slicer_smooth_handle sh);
  *                               least the radius away from every edge, in long double from slicer_smooth_weights' tables:
  *                               GAUSS sum g^2 / (sum g)^2, MAP c sqrt(sum_ij (g_i g_j - h_i g_j - g_i h_j)^2), sums over
  *                               -R ... R.  sigma_smoothed = sigma_pix gain.  Refusals: those of slicer_smooth_weights
- *   slicer_noise_create         on the device and stream of h (create it after any slicer_set_stream, destroy it before h);
+ *   slicer_noise_create         on the device and stream of h (h's current one: slicer_set_stream, destroy it before h);
  *                               one f32 npix^2 output owned by the handle.  The numbers are checked before the handle:
  *                               npix < 1 SLICER_ERR_ARG, npix > 131072 SLICER_ERR_UNSUPPORTED
  *   slicer_noise_run            d_map: any device f32 map of the handle's npix^2 pixels, or NULL; enqueued, no synchronisation.
@@ -829,7 +845,7 @@ int slicer_noise_destroy(slicer_noise_handle nh);
  *                              H_{j-1} * (1, 4, 6, 4, 1) / 16 dilated by 2^{j-1}: gain_j = sqrt(sum_ab (H_{j-1}[a] H_{j-1}[b] -
  *                              H_j[a] H_j[b])^2), gain_coarse = sum_a H_J[a]^2; 0.8907963, 0.2006639, 0.0855075, ...  scales
  *                              outside 1..12: SLICER_ERR_ARG (message through slicer_last_error(NULL))
- *   slicer_starlet_create      on the device and stream of h (create it after any slicer_set_stream, destroy it before h).
+ *   slicer_starlet_create      on the device and stream of h (h's current one: slicer_set_stream, destroy it before h).
  *                              The numbers are checked before the handle, so that they can be checked without a device:
  *                              npix < 1 or scales outside 1..12: SLICER_ERR_ARG; npix > 131072: SLICER_ERR_UNSUPPORTED.
  *                              Device memory: 4 (J + 1) bytes a pixel of outputs and 16 of f64 levels (SLICER_ERR_NOMEM)
@@ -1019,7 +1035,7 @@ int slicer_xi_destroy(slicer_xi_handle xh);
  * These connectivities are the ones the closed pixel complex of row N14 implies: components[j] - holes[j] equals its
  * vertices[j] - edges[j] + faces[j] exactly, on every map.  The counts are exact and the same on every run, although the
  * order in which the device unites pixels is not.
- *   slicer_betti_create    on the device and stream of h (create it after any slicer_set_stream, destroy it before h).
+ *   slicer_betti_create    on the device and stream of h (h's current one: slicer_set_stream, destroy it before h).
  *                          The numbers are checked before the handle, so that they can be checked without a device:
  *                          npix < 1, fewer than 1 or more than 1025 thresholds, a threshold that is not finite,
  *                          thresholds not strictly ascending: SLICER_ERR_ARG; npix > SLICER_BETTI_MAX_NPIX (node ids and

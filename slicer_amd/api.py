@@ -97,6 +97,7 @@ class Slicer:
         self._h = h
         self.npix = 0
         self.n_planes = 0
+        self._own = self.get_stream()  # a new handle works on its own stream
 
     def close(self):
         if getattr(self, "_h", None):
@@ -131,7 +132,17 @@ class Slicer:
         return v.value
 
     def set_stream(self, stream_ptr):
-        self._chk(_L.slicer_set_stream(self._h, C.c_void_p(stream_ptr)))
+        """Work on the hipStream_t at address stream_ptr from now on (include/slicer_amd.h: slicer_set_stream; refused
+        inside a pass, and a switch is ordered behind what was queued on the old stream).  None and 0 both mean the
+        handle's own stream.  0 is also what torch.cuda.current_stream().cuda_stream gives under torch's default
+        stream: a handle never works ON the default stream, but its own stream is a blocking one, which HIP orders
+        with the (legacy) default stream in both directions -- so work the caller queues there still comes before and
+        after the handle's in call order (on_own_stream tells; parallel.reduce_planes relies on it)."""
+        self._chk(_L.slicer_set_stream(self._h, C.c_void_p(stream_ptr or None)))
+
+    def on_own_stream(self):
+        """True while the handle works on the blocking stream it created for itself."""
+        return self.get_stream() == self._own
 
     def plane_begin(self, npix, fov_rad, ld, ld2, nrepperp=None, mas=MAS_TSC, accum=ACC_F32, algo=ALGO_AUTO,
                     hydro=False, snopt=0, want_type_maps=True, fixed_frac_bits=0, debug_flags=0):

@@ -220,9 +220,27 @@ int slicer_set_stream(slicer_handle h, void *hip_stream)
 {
     if (!h)
         return fail(h, SLICER_ERR_ARG, "null handle");
-    if (h->in_plane)
-        return fail(h, SLICER_ERR_STATE, "cannot change stream inside a plane pass");
-    h->stream = hip_stream ? (hipStream_t)hip_stream : h->own;
+    // (a pass stays "open" after slicer_plane_finalize so that its maps can be read: what must not see the stream change
+    // is a pass that still takes deposits)
+    if (h->in_plane && !h->finalized)
+        return fail(h, SLICER_ERR_STATE,
+                    "cannot change stream inside a plane pass (between slicer_plane_begin and slicer_plane_finalize)");
+    hipStream_t to = hip_stream ? (hipStream_t)hip_stream : h->own;
+    if (to == h->stream)
+        return SLICER_OK;
+    // Everything this handle and its sub-handles queued on the old stream (finalize kernels, table uploads of a
+    // *_create, runs) comes before whatever they queue on the new one: one event, recorded there and waited for here.
+    HIPCHK(h, hipSetDevice(h->device));
+    hipEvent_t e = get_event(h);
+    if (!e)
+        return fail(h, SLICER_ERR_HIP, "slicer_set_stream: no event to order the new stream behind the old one");
+    hipError_t rc = hipEventRecord(e, h->stream);
+    if (rc == hipSuccess)
+        rc = hipStreamWaitEvent(to, e, 0);
+    h->ev_pool.push_back(e);  // (the wait holds what the event stood for when it was queued: the event is free again)
+    if (rc != hipSuccess)
+        return fail(h, SLICER_ERR_HIP, "slicer_set_stream: ordering the streams failed: %s", hipGetErrorString(rc));
+    h->stream = to;
     return SLICER_OK;
 }
 

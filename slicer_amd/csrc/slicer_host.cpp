@@ -20,6 +20,8 @@ const char *kKernelNames[] = {"direct_deposit", "finalize_tsc", "fold_ngp",  "sy
                               "betti_rank",     "betti_link",   "betti_finish"};
 static_assert(sizeof kKernelNames / sizeof *kKernelNames == KN_COUNT, "one name per KN_* value");
 
+}  // namespace
+
 hipEvent_t get_event(slicer_handle h)
 {
     if (!h->ev_pool.empty()) {
@@ -29,11 +31,9 @@ hipEvent_t get_event(slicer_handle h)
     }
     hipEvent_t e = nullptr;
     if (hipEventCreate(&e) != hipSuccess)
-        return nullptr;  // the scope below then skips timing for this launch
+        return nullptr;  // ProfScope then skips timing for this launch
     return e;
 }
-
-}  // namespace
 
 int fail(slicer_handle h, int code, const char *fmt, ...)
 {

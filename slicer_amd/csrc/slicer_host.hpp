@@ -232,6 +232,9 @@ struct ProfScope {
     ~ProfScope();
 };
 void prof_collect(slicer_handle h);
+// An event of the handle's pool (a new one while the pool is empty; null if that fails).  Whoever is done with it pushes
+// it back onto h->ev_pool; slicer_destroy destroys the pool.
+hipEvent_t get_event(slicer_handle h);
 
 // What the sub-handles share.  sub_open (their *_create): the handle's stream and its device, made current; errors are
 // prefixed with `who`.  sub_stream (every later call): the handle's current stream, `device` made current.

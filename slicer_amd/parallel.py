@@ -132,6 +132,19 @@ def _sum_p2p(dist, torch, t, root, world, rank, tag0):
     return works, second_hop
 
 
+def works_with_stream(S, current):
+    """True if what the handle S enqueues is ordered with work on the stream at address `current` (torch's current
+    stream): S works on that very stream, or `current` is 0 and S works on its own blocking stream
+    (Slicer.on_own_stream, which S must offer; Slicer.set_stream(0) leaves the handle there).  The second case rests
+    on two facts.  Address 0 is HIP's LEGACY default stream: that holds for torch, whose default stream is the null
+    stream of a runtime built without the per-thread default stream -- a caller whose 0 means a per-thread default
+    stream must not rely on this and has to pass a stream of its own.  And HIP orders a blocking stream with the legacy
+    default stream in both directions.  A user stream, blocking or not, is not ordered with any other stream."""
+    if int(S.get_stream()) == int(current):
+        return True
+    return int(current) == 0 and S.on_own_stream()
+
+
 def reduce_planes(S, dist, torch, root=0, per_type=None, async_op=False, finalize=True, algo="rooted", sync_free=None):
     """Sum the current plane pass over the ranks onto `root`, in the accumulator's own type, then convert to f32 maps.
 
@@ -146,9 +159,10 @@ def reduce_planes(S, dist, torch, root=0, per_type=None, async_op=False, finaliz
     "p2p" (the same direct pattern written with sends / receives and local sums; any backend).
     STREAMS (device backends): the handle must work on torch's CURRENT stream (S.set_stream(torch.cuda.current_stream()
     .cuda_stream) and call this under that stream): the collectives are ordered behind the deposits -- and
-    plane_finalize behind the collectives -- through that stream; a handle on a stream of its own would race both.
-    This is checked.  async_op=True returns an object whose wait() completes the communication (call it under the same
-    stream), after which S.plane_finalize() may run.
+    plane_finalize behind the collectives -- through that stream; a handle on another stream would race both.
+    Under torch's default stream that call leaves the handle on its own blocking stream, which HIP orders with the
+    default stream (works_with_stream).  This is checked.  async_op=True returns an object whose wait() completes the
+    communication (call it under the same stream), after which S.plane_finalize() may run.
     sync_free (default: whenever S offers reduce_meta_get_async and the backend is a device one): no host
     synchronisation with the deposit stream -- the reduce meta is combined from host-known entries on a side stream and
     the negativity guard by a MAX all-reduce of the device flag next to the map sums."""
@@ -157,8 +171,7 @@ def reduce_planes(S, dist, torch, root=0, per_type=None, async_op=False, finaliz
     on_device = dist.get_backend() != "gloo"
     world, rank = dist.get_world_size(), dist.get_rank()
     if on_device and hasattr(S, "get_stream"):
-        cur = int(torch.cuda.current_stream().cuda_stream)
-        if int(S.get_stream()) != cur:
+        if not works_with_stream(S, torch.cuda.current_stream().cuda_stream):
             raise RuntimeError("reduce_planes: the slicer handle does not work on torch's current stream "
                                "(S.set_stream(torch.cuda.current_stream().cuda_stream)); its deposits and finalize "
                                "would not be ordered with the collectives")

@@ -55,6 +55,18 @@ def test_one_run_times_the_step_layout_and_the_per_plane_reduce_layout():
         assert rl[algo]["value"] > 0.2 * d["value"], (rl[algo], d["value"])
 
 
+@pytest.mark.parametrize("layout,port", [(["--shard", "files"], "29535"), (["--shard", "steps", "--gather", "on"], "29536")],
+                         ids=["files", "gather"])
+def test_no_overlap_layouts_run_under_torchs_default_stream(layout, port):
+    """--no-overlap keeps ONE handle, set to torch's current stream -- the default stream, pointer 0, which leaves the
+    handle on its own blocking stream (Slicer.set_stream).  reduce_planes accepts that pairing, since HIP orders a
+    blocking stream with the legacy default stream (parallel.works_with_stream), and StepGather's sends read the maps
+    behind plane_finalize for the same reason.  Before, `--shard files --no-overlap` ended in reduce_planes' "does not
+    work on torch's current stream"."""
+    d = _bench(SMALL + layout + ["--no-overlap"], env={"SLICER_BENCH_FORCE_DIST": "1", "MASTER_PORT": port})
+    assert d["value"] > 0 and d["config"]["shard"] == layout[1]
+
+
 def test_a_stuck_secondary_layout_cannot_take_the_main_number_down():
     """N > 1 runs time the reduce layouts after the main number; those collectives meet real multi-GPU hardware for the
     first time in the scaling run.  A watchdog prints the line with whatever finished and leaves if they do not finish in
