@@ -1060,6 +1060,66 @@ int slicer_betti_run_npix(slicer_betti_handle bh, const float *d_map, int32_t np
 int slicer_betti_read(slicer_betti_handle bh, int64_t *components, int64_t *holes, int64_t *faces, int64_t *n_nan);
 int slicer_betti_destroy(slicer_betti_handle bh);
 
+/* ---- Wavelet scattering coefficients of a kappa map, orders 0, 1 and 2 ----
+ * Input: one device f32 map of npix^2 pixels, axis 0 slow = component 1, axis 1 contiguous = component 2 (row N6's
+ * convention), only read, treated as periodic (as rows N7 and N15).  n = npix must be a size the f64 transform plans
+ * (slicer_shear_supported: prime factors 2, 3, 5, 7 only, <= 16384); 1 <= J <= SLICER_SCATTERING_MAX_J scales with
+ * 2^J <= n, 1 <= L <= SLICER_SCATTERING_MAX_L orientations.
+ * Filter bank: Morlet filters defined in Fourier space, where they are real.  For scale j = 0 ... J-1 and orientation
+ * l = 0 ... L-1: sigma = 0.8 2^j, xi = (3 pi / 4) 2^-j, s = 4 / L, theta = pi l / L (cos theta and sin theta computed on
+ * the host in f64).  For an angular frequency (w1, w2) along (axis 0, axis 1):
+ *   p = w1 cos theta + w2 sin theta,  q = -w1 sin theta + w2 cos theta,
+ *   A(w) = exp(-sigma^2 / 2 ((p - xi)^2 + q^2 / s^2)),  B(w) = exp(-sigma^2 / 2 (p^2 + q^2 / s^2)),
+ *   A^(w) = sum_m A(w + 2 pi m),  B^(w) = sum_m B(w + 2 pi m) over the nine m in {-1, 0, 1}^2, m1 outer, m2 inner, each
+ *   from -1 up;  beta = A^(0) / B^(0), on the host.
+ * For the mode index (a, b), 0 <= a, b < n: the signed index a_s = a for a < (n + 1) / 2 (integer division), else a - n
+ * (n / 2 maps to -n / 2), w = 2 pi (a_s, b_s) / n, and psi^_{jl}[a][b] = A^(w) - beta B^(w), psi^_{jl}[0][0] = 0 exactly.
+ * All of it in f64, no contraction into fused multiply-adds.
+ * Transform: for a real f64 field f with fhat = rfft2(f), W_{jl} f = |ifft2(fhat_full psi^_{jl})|, the modulus of a
+ * complex field.  Route (the library has no complex transform): with E[a][b] = (psi^[a][b] + psi^[(-a) mod n][(-b) mod n]) / 2
+ * and O the same with a minus sign (0 at the self-conjugate modes by construction), x = irfft2(fhat E),
+ * y = irfft2(-i fhat O), u = sqrt(x x + y y), rounded after each operation.
+ * Outputs, all f64:
+ *   s0[2]           the mean of kappa and the mean of kappa^2
+ *   s1[J][L]        the mean of u1 = W_{jl} kappa
+ *   p1[J][L]        the mean of u1^2: the wavelet power that s2 / s1 ratios and scattering covariances need
+ *   s2[J][L][J][L]  the mean of W_{j2 l2} u1 for j2 > j1, indexed [j1][l1][j2][l2]; NaN where j2 <= j1
+ * Nothing is subsampled: every field keeps n^2 pixels.  No floating-point atomics; every sum is blocked in a fixed order
+ * (64 values, the blocks of a chunk, a lane butterfly, the chunks in index order, as row N15): the same input gives the
+ * same bits run after run, and so does an input pointer one float off the 16-byte grid.  The coefficients are this
+ * definition's; they are not pinned against any other package's filter bank.
+ * Out of scope: subsampled or band-limited second-order transforms (psi^_{j2} occupies about 4^-j2 of the plane: the next
+ * step), a complex transform, orders above 2, j2 <= j1, scattering covariances and phase harmonics, non-periodic edges
+ * and masks, sizes that are not 2-3-5-7, plane maps.
+ *   slicer_scattering_filter   host only, no device: psi^_{jl} [npix][npix] by the definition above.  Refusals as
+ *                              slicer_scattering_create's of the numbers, (j, l) outside the bank and a NULL out:
+ *                              SLICER_ERR_ARG (messages through slicer_last_error(NULL))
+ *   slicer_scattering_create   on the device and stream of h, under the shear_split option of h at create.  The numbers are
+ *                              checked before the handle and before any allocation: an npix the transform does not plan,
+ *                              J > 12, L > 16: SLICER_ERR_UNSUPPORTED; J < 1, L < 1, 2^J > npix, null pointers:
+ *                              SLICER_ERR_ARG.  Device memory: two spectra (khat, u1hat) and two products (fhat E,
+ *                              -i fhat O) of 16 n (n/2+1) bytes each, two f64 maps x and y (16 n^2 bytes together), the
+ *                              transform's buffers (16 n (n/2+1) bytes per pass of its longer chain, at most three, and
+ *                              the twiddles), the partial sums (at most 64 KiB) and the results: about 48 n^2 bytes, 0.8 GB
+ *                              at 4096^2 and 13 GB at 16384^2 (computed, not measured) (SLICER_ERR_NOMEM)
+ *   slicer_scattering_run      any device f32 map of npix^2 pixels; enqueued, no synchronisation; every result word is
+ *                              rewritten.  A NULL map: SLICER_ERR_ARG.  J L (1 + (J - 1) L / 2) pairs of f64 inverses
+ *   slicer_scattering_read     s0, s1, p1, s2 of the last run (any of them NULL); waits for the stream.  Before any run:
+ *                              SLICER_ERR_STATE
+ *   slicer_scattering_modulus  the npix^2 f64 field u1 = W_{j1 l1} kappa (j2 = l2 = -1) or W_{j2 l2} u1 (j1 < j2 < J),
+ *                              recomputed from d_map into host memory; waits for the stream; the results of the last run
+ *                              stay readable.  Indices outside the bank: SLICER_ERR_ARG */
+typedef struct slicer_scattering_s *slicer_scattering_handle;
+#define SLICER_SCATTERING_MAX_J 12
+#define SLICER_SCATTERING_MAX_L 16
+int slicer_scattering_filter(int32_t npix, int32_t J, int32_t L, int32_t j, int32_t l, double *out);
+int slicer_scattering_create(slicer_handle h, int32_t npix, int32_t J, int32_t L, slicer_scattering_handle *out);
+int slicer_scattering_run(slicer_scattering_handle sh, const float *d_map);
+int slicer_scattering_read(slicer_scattering_handle sh, double *s0, double *s1, double *p1, double *s2);
+int slicer_scattering_modulus(slicer_scattering_handle sh, const float *d_map, int32_t j1, int32_t l1, int32_t j2,
+                              int32_t l2, double *host);
+int slicer_scattering_destroy(slicer_scattering_handle sh);
+
 /* per-kernel HIP-event timing (off by default; adds two event records per launch) */
 int slicer_profile_enable(slicer_handle h, int on);
 int slicer_profile_reset(slicer_handle h);

@@ -129,6 +129,12 @@ SYMBOLS = {
     "slicer_betti_run_npix": (C.c_int, [_H, C.c_void_p, C.c_int32]),
     "slicer_betti_read": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "slicer_betti_destroy": (C.c_int, [_H]),
+    "slicer_scattering_filter": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "slicer_scattering_create": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "slicer_scattering_run": (C.c_int, [_H, C.c_void_p]),
+    "slicer_scattering_read": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "slicer_scattering_modulus": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "slicer_scattering_destroy": (C.c_int, [_H]),
     "slicer_bispectrum_triangles": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "slicer_bispectrum_create": (C.c_int, [_H, C.c_int32, C.c_double, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
                                           C.POINTER(C.c_void_p)]),

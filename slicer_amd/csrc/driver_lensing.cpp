@@ -80,6 +80,16 @@
 //     '# sigma_scale' line), and per realisation r the same maps of the noisy map, .noisy<r>_starlet<j>_kappa_z...
 //     with the keys of the noisy file first, and the tables .noisy_starlet_peaks_ and .noisy_starlet_l1_ (a leading
 //     column `real`).  Refused for physical runs.
+//   * --scattering J,L: <directory><simulation>.scattering_<npix>_<suffix>.txt, the wavelet scattering coefficients of
+//     every kappa map over J (1 ... 12, 2^J <= npix) dyadic scales and L (1 ... 16) orientations of Morlet filters, the
+//     map taken as periodic: '#' lines (npix, angle, J, L, the filter constants sigma0, xi0 and slant of
+//     sigma = sigma0 2^j, xi = xi0 2^-j, s = slant / L, the column names), then per source the rows
+//     z order j1 l1 j2 l2 value power (%.17g): order 0, one row, the mean and the mean square of kappa; order 1, per
+//     (j1, l1), s1 and p1, the mean and the mean square of |kappa * psi_{j1 l1}|; order 2, per (j1, l1, j2 > j1, l2),
+//     s2, the mean of ||kappa * psi_{j1 l1}| * psi_{j2 l2}| (power: nan); an index a row does not have is -1.  With
+//     --shape-noise also .noisy_scattering_ of every noisy realisation (a leading column `real`).  Not for the pyramid
+//     levels or the smoothed maps: the transform has its own scales.  npix must be a size the f64 transform takes;
+//     refused for physical runs.  The scattering tables are the last files of a run.
 #include "driver_lensing.hpp"
 
 #include <algorithm>
@@ -281,6 +291,17 @@ int LensingOptions::parse(int argc, char **argv, int &i)
         if (const int rc = uniform_edges(a, v.c_str() + colon + 1, "after J: the first and the last edge", starlet_edges))
             return rc;
         starlet_scales = (int)J;
+    } else if (a == "--scattering") {
+        const vector<string> tok = has_value ? split(argv[++i]) : vector<string>{};
+        char *e0 = nullptr, *e1 = nullptr;
+        const bool two = tok.size() == 2 && !tok[0].empty() && !tok[1].empty() && !isspace((unsigned char)tok[0][0]) &&
+                         !isspace((unsigned char)tok[1][0]);
+        const long J = two ? strtol(tok[0].c_str(), &e0, 10) : 0, L = two ? strtol(tok[1].c_str(), &e1, 10) : 0;
+        if (!two || *e0 != '\0' || *e1 != '\0' || J < 1 || J > SLICER_SCATTERING_MAX_J || L < 1 || L > SLICER_SCATTERING_MAX_L)
+            return bad("bad --scattering (J,L: the number of scales, 1 ... " + std::to_string(SLICER_SCATTERING_MAX_J) +
+                       ", and of orientations, 1 ... " + std::to_string(SLICER_SCATTERING_MAX_L) + ")");
+        scattering_J = (int)J;
+        scattering_L = (int)L;
     } else
         return -1;
     return 0;
@@ -324,6 +345,7 @@ int LensingOptions::check() const
         {!smooth_kind.empty() && no_kappa, "--smooth needs --kappa (the smoothed maps are those of the kappa maps)"},
         {shape_noise && no_kappa, "--shape-noise needs --kappa (the noise is added to the kappa maps)"},
         {starlet_scales > 0 && no_kappa, "--starlet needs --kappa (the transform is that of the kappa maps)"},
+        {scattering_J > 0 && no_kappa, "--scattering needs --kappa (the coefficients are those of the kappa maps)"},
     };
     for (const auto &[broken, message] : rules)
         if (broken)
@@ -403,6 +425,12 @@ int LensingOptions::check_npix(const InputParams &p) const
         return bad("--shape-noise: the galaxy density is per angle, and the pixels of a physical run have none");
     if (starlet_scales > 0 && p.physical)
         return bad("--starlet: the scales are read as angles, and the maps of a physical run have none");
+    if (scattering_J > 0 && p.physical)
+        return bad("--scattering: the table is that of maps with an angle, and the maps of a physical run have none");
+    if (scattering_J > 0 && !slicer_shear_supported(p.npix))
+        return bad("--scattering: " + npix + fft_sizes);
+    if (scattering_J > 0 && (1L << scattering_J) > p.npix)
+        return bad("--scattering: 2^J = " + std::to_string(1L << scattering_J) + " is above " + npix);
     double sigma_pix = 0.0;
     if (shape_noise && slicer_noise_sigma_pix(noise_sigma_e, noise_ngal, p.fov, p.npix, &sigma_pix) != SLICER_OK)
         return bad("--shape-noise: " + npix + ": " + slicer_last_error(nullptr));
@@ -556,6 +584,8 @@ int LensingOutputs::create()
             starlet_scale_edges.push_back(e);
         }
     }
+    if (o.scattering_J > 0 && slicer_scattering_create(h, p.npix, o.scattering_J, o.scattering_L, sch.out()) != SLICER_OK)
+        return fail(h, "slicer_amd: --scattering");
     if (!o.raytrace)
         return 0;
     if (slicer_kappa_create(h, p.npix, 1, lkh.out()) != SLICER_OK ||
@@ -671,7 +701,8 @@ bool LensingOutputs::save(const char *what, const string &token, size_t s, const
 
 // Per source the kappa file, then its moments, then the histograms and the Minkowski functionals of its pyramid (which
 // the moments of the same source left behind), then the shear files, then the smoothed maps with their moments,
-// histograms and functionals, then the noisy maps with theirs; after the sources the tables, the Betti tables last.
+// histograms and functionals, then the noisy maps with theirs; after the sources the tables, the Betti tables and then
+// the scattering tables last.
 int LensingOutputs::write()
 {
     if (slicer_kappa_finalize(kh) != SLICER_OK)
@@ -691,6 +722,8 @@ int LensingOutputs::write()
         if (const int rc = nh ? source_noise(s, d_kappa) : 0)
             return rc;
         if (const int rc = sth ? source_starlet(s, d_kappa, false, ".", {}, "", "") : 0)
+            return rc;
+        if (const int rc = sch ? source_scattering(s, d_kappa, false, "", "") : 0)
             return rc;
     }
     if (const int rc = ph ? power_spectra() : 0)
@@ -732,6 +765,40 @@ int LensingOutputs::write()
     for (int k = 0; k < N_KINDS; k++)
         if (has_statistic[BETTI] && has_kind[k] && write_statistic(BETTI, k))
             return 1;
+    // ... and the scattering tables after those
+    for (int noisy = 0; noisy < (sch ? (nh ? 2 : 1) : 0); noisy++)
+        if (write_table((string("scattering coefficients") + kind[noisy ? NOISY : KAPPA][0]).c_str(),
+                        (string(kind[noisy ? NOISY : KAPPA][1]) + "scattering_").c_str(), scattering_tables[noisy]))
+            return 1;
+    return 0;
+}
+
+// The scattering table: '#' lines (npix, angle, J, L, the filter constants, with --shape-noise its lines, the column
+// names), then per source one row of order 0, J L rows of order 1 and J (J - 1) / 2 L^2 rows of order 2.
+int LensingOutputs::source_scattering(size_t s, const float *d_map, bool noisy, const string &lead_names, const string &lead)
+{
+    const int J = o.scattering_J, L = o.scattering_L, JL = J * L;
+    string &text = scattering_tables[noisy];
+    if (text.empty()) {
+        add(text, "# npix %d\n# angle_deg %.17g\n# J %d\n# L %d\n# sigma0 %.17g\n# xi0 %.17g\n# slant %.17g\n", p.npix, p.fov, J,
+            L, 0.8, 3.0 * M_PI / 4.0, 4.0);
+        text += (noisy ? noise_head() : "") + "# " + lead_names + "z order j1 l1 j2 l2 value power\n";
+    }
+    double s0[2];
+    vector<double> s1(JL), p1(JL), s2((size_t)JL * JL);
+    if (slicer_scattering_run(sch, d_map) != SLICER_OK ||
+        slicer_scattering_read(sch, s0, s1.data(), p1.data(), s2.data()) != SLICER_OK)
+        return fail(h, "slicer_amd: --scattering");
+    const auto row = [&](int order, int j1, int l1, int j2, int l2, double value, double power) {
+        text += lead;
+        add(text, "%.17g %d %d %d %d %d %.17g %.17g\n", plan.zs[s], order, j1, l1, j2, l2, value, power);
+    };
+    row(0, -1, -1, -1, -1, s0[0], s0[1]);
+    for (int a = 0; a < JL; a++)
+        row(1, a / L, a % L, -1, -1, s1[a], p1[a]);
+    for (int a = 0; a < JL; a++)
+        for (int b = (a / L + 1) * L; b < JL; b++)
+            row(2, a / L, a % L, b / L, b % L, s2[(size_t)a * JL + b], NAN);
     return 0;
 }
 
@@ -872,6 +939,8 @@ int LensingOutputs::source_noise(size_t s, const float *d_kappa)
                 return rc;
         }
         if (const int rc = sth ? source_starlet(s, d_noisy, true, ".noisy" + real + "_", keys, "real ", real + " ") : 0)
+            return rc;
+        if (const int rc = sch ? source_scattering(s, d_noisy, true, "real ", real + " ") : 0)
             return rc;
     }
     return 0;

@@ -1,6 +1,6 @@
 // driver_lensing.hpp -- the lensing outputs of the SLICER_amd driver (slicer_main.cpp): their options, their host
 // planning and the device-0 work behind --kappa, --shear, --deflection, --raytrace, --power, --pcl, --xi, --moments, --peaks,
-// --minkowski, --betti, --bispectrum, --smooth, --shape-noise and --starlet (driver_lensing.cpp describes the options), with the small helpers the rest of the driver shares with them.
+// --minkowski, --betti, --bispectrum, --smooth, --shape-noise, --starlet and --scattering (driver_lensing.cpp describes the options), with the small helpers the rest of the driver shares with them.
 #pragma once
 #include <deque>
 #include <string>
@@ -43,6 +43,7 @@ struct LensingOptions {
     int noise_nreal = 1;
     int starlet_scales = 0;              // --starlet J:lo,hi,bins: J, 0 without it
     std::vector<double> starlet_edges;   // ... the bins + 1 uniform edges from lo to hi
+    int scattering_J = 0, scattering_L = 0;  // --scattering J,L: the scales and the orientations, 0 without it
 
     bool gradient() const { return shear_derivative == "gradient"; }
     int n_power_edges(int npix) const { return power_edges.empty() ? npix : (int)power_edges.size(); }
@@ -149,6 +150,9 @@ struct LensingOutputs {
     std::deque<Owned<slicer_peaks_handle, slicer_peaks_destroy>> starlet_pkh{};
     std::deque<Owned<slicer_l1norm_handle, slicer_l1norm_destroy>> starlet_l1h{};
     std::string starlet_tables[2][2]{};
+    // --scattering: one handle for all sources; the tables of the kappa and of the noisy maps
+    Owned<slicer_scattering_handle, slicer_scattering_destroy> sch{};
+    std::string scattering_tables[2]{};
     // --raytrace: a one-source kappa handle that makes a plane's lens map, the rays, their six output buffers, and the
     // sources in ascending redshift with the position of the next one to observe
     Owned<slicer_kappa_handle, slicer_kappa_destroy> lkh{};
@@ -206,6 +210,8 @@ private:
     // its rows of the two tables of the noisy (or not) maps; `lead_names` and `lead` as above
     int source_starlet(size_t s, const float *d_map, bool noisy, const std::string &prefix, const std::vector<FitsKey> &keys,
                        const std::string &lead_names, const std::string &lead);
+    // --scattering of the map at d_map of source s: its rows of the table of the noisy (or not) maps
+    int source_scattering(size_t s, const float *d_map, bool noisy, const std::string &lead_names, const std::string &lead);
     int source_shear(size_t s, const float *d_kappa);
     int power_spectra();
     int pseudo_spectra();

@@ -1,6 +1,6 @@
 // slicer_fft.hpp -- internal (not exported): the forward f64 r2c transform of slicer_shear.hip, shared by the shear
 // handle, the power-spectrum handle (row N7), the bispectrum handle (row N15), the pseudo-C_l
-// handle (row N17) and the correlation-function handle (row N18).  One plan per map size and shear_split value:
+// handle (row N17), the correlation-function handle (row N18) and the scattering handle (row N20).  One plan per map size and shear_split value:
 // the twiddles, the row and column pass chains, and the buffers the forward passes go through.
 #pragma once
 
@@ -37,6 +37,10 @@ SLICER_FFT_INTERNAL int slicer_fft_forward_masked(slicer_fft_s *f, hipStream_t s
 // khat = rfft2(x * y) for two f64 npix^2 maps, the products taken in f64 as the rows are loaded.
 SLICER_FFT_INTERNAL int slicer_fft_forward_product(slicer_fft_s *f, hipStream_t st, const double *x, const double *y,
                                                    double2 *khat);
+// khat = rfft2(sqrt(x * x + y * y)) for two f64 npix^2 maps, the modulus taken in f64 as the rows are loaded, rounded
+// after every operation; it is never stored (the scattering handle, slicer_scattering.hip, row N20).
+SLICER_FFT_INTERNAL int slicer_fft_forward_hypot(slicer_fft_s *f, hipStream_t st, const double *x, const double *y,
+                                                 double2 *khat);
 // out = irfft2(|khat|^2), s = (npix, npix), kept in f64: npix^2 doubles.
 SLICER_FFT_INTERNAL int slicer_fft_inverse_abs2(slicer_fft_s *f, hipStream_t st, const double2 *khat, double *out);
 SLICER_FFT_INTERNAL void slicer_fft_destroy(slicer_fft_s *f);

@@ -1,5 +1,5 @@
 // slicer_host.cpp -- what every file under the C ABI shares (slicer_host.hpp): the error text, grow-only device
-// buffers, the per-kernel profile, and the helpers of the sub-handles (kappa, shear, FFT plan, power, moments, peaks, rays, smooth, noise, minkowski, bispectrum, starlet, l1norm, betti).
+// buffers, the per-kernel profile, and the helpers of the sub-handles (kappa, shear, FFT plan, power, moments, peaks, rays, smooth, noise, minkowski, bispectrum, starlet, l1norm, betti, scattering).
 #include "slicer_host.hpp"
 
 #include <cstdarg>
@@ -17,7 +17,7 @@ const char *kKernelNames[] = {"direct_deposit", "finalize_tsc", "fold_ngp",  "sy
                               "smooth_cols",    "noise_add",    "noise_words",  "minkowski",    "minkowski_finish",
                               "bispectrum_fft", "bispectrum_band", "bispectrum", "bispectrum_finish",
                               "starlet_first",  "starlet_level", "starlet_last", "l1norm",       "l1norm_finish",
-                              "betti_rank",     "betti_link",   "betti_finish"};
+                              "betti_rank",     "betti_link",   "betti_finish", "scattering_first", "scattering_second"};
 static_assert(sizeof kKernelNames / sizeof *kKernelNames == KN_COUNT, "one name per KN_* value");
 
 }  // namespace

@@ -1,6 +1,6 @@
 // slicer_host.hpp -- internal (not installed, not exported): the host layer under the C ABI of include/slicer_amd.h.
 // The handle, its error and profiling plumbing, what the sub-handles (kappa, shear, FFT plan, power, moments, peaks,
-// rays, smooth, noise, minkowski, bispectrum, starlet, l1norm, pcl, xi, betti) share, and the functions that cross the
+// rays, smooth, noise, minkowski, bispectrum, starlet, l1norm, pcl, xi, betti, scattering) share, and the functions that cross the
 // files of the core pass:
 //   slicer_host.cpp    errors, grow-only buffers, profiling, the sub-handle helpers: SubHandle (the base of every
 //                      sub-handle struct) with sub_new / sub_done for its *_create, sub_stream for its launches, sub_read
@@ -48,7 +48,7 @@ enum {
     KN_RAYS_OBSERVE, KN_SMOOTH_ROWS, KN_SMOOTH_NORM, KN_SMOOTH_COLS, KN_NOISE_ADD,
     KN_NOISE_WORDS, KN_MINKOWSKI, KN_MINKOWSKI_FINISH, KN_BISPECTRUM_FFT, KN_BISPECTRUM_BAND, KN_BISPECTRUM,
     KN_BISPECTRUM_FINISH, KN_STARLET_FIRST, KN_STARLET_LEVEL, KN_STARLET_LAST, KN_L1NORM, KN_L1NORM_FINISH,
-    KN_BETTI_RANK, KN_BETTI_LINK, KN_BETTI_FINISH, KN_COUNT
+    KN_BETTI_RANK, KN_BETTI_LINK, KN_BETTI_FINISH, KN_SCATTERING_FIRST, KN_SCATTERING_SECOND, KN_COUNT
 };
 
 // Tuning and test knobs of one handle.  Read from the environment ONCE, in slicer_create (so that the tools/ scripts

@@ -47,18 +47,18 @@ constexpr int kMaxStages = 16;
 
 enum Load {
     L_COMPLEX = 0, L_REAL_EVEN, L_REAL_PAIR, L_SPLIT_EVEN, L_SPLIT_PAIR, L_FILTER, L_C2R_EVEN, L_C2R_PAIR, L_BAND,
-    L_REALW_EVEN, L_REALW_PAIR, L_PROD64_EVEN, L_PROD64_PAIR, L_ABS2
+    L_REALW_EVEN, L_REALW_PAIR, L_PROD64_EVEN, L_PROD64_PAIR, L_ABS2, L_HYPOT_EVEN, L_HYPOT_PAIR
 };
 enum Store { S_COMPLEX = 0, S_REAL_EVEN, S_REAL_PAIR, S_GAMMA_EVEN, S_GAMMA_PAIR, S_REAL64_EVEN, S_REAL64_PAIR };
 // The instantiations of k_fft_pass.  V_PLAIN, the kernel behind the shear, deflection and power outputs, is compiled
 // without the loads and stores below and keeps its registers.  V_BAND adds L_BAND and S_REAL64_*
 // (slicer_fft_inverse_band); V_PCL adds L_REALW_*, L_PROD64_*, L_ABS2 and S_REAL64_* (the masked pseudo-C_l handle,
-// slicer_pcl.hip).
+// slicer_pcl.hip) and L_HYPOT_* (the scattering handle, slicer_scattering.hip).
 enum Variant { V_PLAIN = 0, V_BAND, V_PCL };
 
 struct PassArgs {
     const void *in;
-    const void *in2;    // L_REALW_*: the f32 mask; L_PROD64_*: the second f64 map
+    const void *in2;    // L_REALW_*: the f32 mask; L_PROD64_* and L_HYPOT_*: the second f64 map
     void *out;          // complex f64 (S_COMPLEX) or the f32 map (gamma1 for S_GAMMA_*)
     float *out2, *out3;  // S_GAMMA_*: gamma2, |gamma|
     const double2 *aux;  // S_GAMMA_*: gamma1 in f64, as its last row pass left it
@@ -120,6 +120,16 @@ __device__ double2 load_point(const PassArgs &a, int l, int e)
             const size_t i = (size_t)(2 * l) * n + e;
             const double *x = (const double *)a.in + i, *y = (const double *)a.in2 + i;
             return make_double2(x[0] * y[0], 2 * l + 1 < n ? x[n] * y[n] : 0.0);
+        }
+        case L_HYPOT_EVEN: {  // L_REAL_EVEN of sqrt(x^2 + y^2) of two f64 maps, rounded after every operation
+            const size_t i = (size_t)l * n + 2 * e;
+            const double *x = (const double *)a.in + i, *y = (const double *)a.in2 + i;
+            return make_double2(sqrt(x[0] * x[0] + y[0] * y[0]), sqrt(x[1] * x[1] + y[1] * y[1]));
+        }
+        case L_HYPOT_PAIR: {
+            const size_t i = (size_t)(2 * l) * n + e;
+            const double *x = (const double *)a.in + i, *y = (const double *)a.in2 + i;
+            return make_double2(sqrt(x[0] * x[0] + y[0] * y[0]), 2 * l + 1 < n ? sqrt(x[n] * x[n] + y[n] * y[n]) : 0.0);
         }
         case L_ABS2: {  // |khat[e][l]|^2
             const double2 s = ((const double2 *)a.in)[(size_t)e * H + l];
@@ -573,6 +583,20 @@ int slicer_fft_forward_product(slicer_fft_s *f, hipStream_t st, const double *x,
     p.variant = V_PCL;
     p.in2 = y;
     End e{x, f->A, even ? L_PROD64_EVEN : L_PROD64_PAIR, S_COMPLEX, 0, 0, f->len, 1};
+    if (int rc = run_chain(f, st, f->row_chain, false, false, e, p))
+        return rc;
+    e = End{f->A, khat, even ? L_SPLIT_EVEN : L_SPLIT_PAIR, S_COMPLEX, 0, 0, 1, f->H};
+    return run_chain(f, st, f->col_chain, true, false, e, p);
+}
+
+int slicer_fft_forward_hypot(slicer_fft_s *f, hipStream_t st, const double *x, const double *y, double2 *khat)
+{
+    const bool even = f->n % 2 == 0;
+    PassArgs p{};
+    p.variant = V_PCL;
+    p.in2 = y;
+    // as slicer_fft_forward_product, the row load taking the modulus
+    End e{x, f->A, even ? L_HYPOT_EVEN : L_HYPOT_PAIR, S_COMPLEX, 0, 0, f->len, 1};
     if (int rc = run_chain(f, st, f->row_chain, false, false, e, p))
         return rc;
     e = End{f->A, khat, even ? L_SPLIT_EVEN : L_SPLIT_PAIR, S_COMPLEX, 0, 0, 1, f->H};

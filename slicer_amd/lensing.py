@@ -8,7 +8,7 @@ excursion sets as exact counts (row N14), and the binned bispectra of such maps 
 such maps with the binned absolute sums of its scales, the starlet l1-norm (row N16), and the masked pseudo-C_l of such
 maps: coupled bandpowers, the mask's mode-coupling matrix and the decoupled bandpowers (row N17), and the real-space
 two-point correlation functions xi_kk, xi+ and xi- of such maps and of shear maps (row N18), and the Betti numbers of
-such maps' excursion sets as exact counts (row N19).
+such maps' excursion sets as exact counts (row N19), and the wavelet scattering coefficients of such maps (row N20).
 
 plane_weights wraps the host weights of include/slicer_amd.h (slicer_lensing_weights); Kappa is the device accumulator
 (slicer_kappa_*) bound to a Slicer handle: it reads the finalized plane maps where they are, in HBM.  Shear (slicer_shear_*)
@@ -26,7 +26,9 @@ Bispectrum (slicer_bispectrum_*) contracts the band-filtered f64 maps of a map o
 pixels bin by bin over Peaks' edges; Pcl (slicer_pcl_*) is Power under a mask (a border taper, a user mask or both),
 with the coupling matrix of the mask and the bandpowers decoupled by it; Xi (slicer_xi_*) sums the pair products of
 zero-padded maps over annuli of the lag, divided by the pair weights of one shared weight map; Betti (slicer_betti_*)
-counts the 8-connected components of the sets x >= t_j and the holes in them by a union-find on the device.
+counts the 8-connected components of the sets x >= t_j and the holes in them by a union-find on the device; Scattering
+(slicer_scattering_*) averages the moduli of a map's Morlet wavelet transforms, and of those moduli's transforms at
+coarser scales.
 """
 import ctypes as C
 import math
@@ -1078,6 +1080,68 @@ class Xi(_SubHandle):
         W = 2 * self.max_lag + 1
         out = np.empty((W, W), np.float64)
         self._s._chk(_L.slicer_xi_correlation(self._xh, int(pair), int(which), out.ctypes.data))
+        return out
+
+
+SCATTERING_MAX_J = 12
+SCATTERING_MAX_L = 16
+
+
+def scattering_filter(npix, J, L, j, l):
+    """Host only (no device): the Morlet filter psi^_{jl} of the scattering bank over the full mode plane, f64
+    [npix, npix], as slicer_scattering_filter defines it."""
+    out = np.empty((int(npix), int(npix)) if npix > 0 else (0, 0), np.float64)
+    _host_chk(_L.slicer_scattering_filter(int(npix), int(J), int(L), int(j), int(l), out.ctypes.data))
+    return out
+
+
+def scattering_reduce(s1, s2):
+    """numpy only: the orientation averages of Scattering.read's s1 [J, L] and s2 [J, L, J, L]: s1(j) [J] and
+    s2(j1, j2, (l2 - l1) mod L) [J, J, L], NaN where j2 <= j1."""
+    s1, s2 = np.asarray(s1, np.float64), np.asarray(s2, np.float64)
+    J, L = s1.shape
+    if s2.shape != (J, L, J, L):
+        raise ValueError(f"s2 has shape {s2.shape}, expected {(J, L, J, L)}")
+    l1 = np.arange(L)
+    r2 = np.stack([s2[:, l1, :, (l1 + d) % L].mean(axis=0) for d in range(L)], axis=-1)
+    return s1.mean(axis=1), r2
+
+
+class Scattering(_SubHandle):
+    """Wavelet scattering coefficients of an npix^2 kappa map, orders 0, 1 and 2, over J dyadic scales and L
+    orientations of Morlet filters, on the device of `slicer`, on its stream.  The map is taken
+    as periodic; nothing is subsampled."""
+    _handle, _destroy = "_sh", "slicer_scattering_destroy"
+
+    def __init__(self, slicer: Slicer, npix, J, L):
+        self._s = slicer
+        self.npix, self.J, self.L = int(npix), int(J), int(L)
+        sh = C.c_void_p()
+        slicer._chk(_L.slicer_scattering_create(slicer._h, self.npix, self.J, self.L, C.byref(sh)))
+        self._sh = sh
+
+    def run(self, d_map):
+        """d_map: device address of an f32 npix^2 map.  Enqueued."""
+        self._s._chk(_L.slicer_scattering_run(self._sh, None if d_map is None else int(d_map)))
+
+    def run_kappa(self, kappa: Kappa, s):
+        """The map of source s of a Kappa accumulator, where it is."""
+        self.run(kappa.device_map(s))
+
+    def read(self):
+        """dict: s0 [2] (the mean of kappa and of kappa^2), s1 and p1 [J, L] (the mean of u1 and of u1^2), s2
+        [J, L, J, L] indexed [j1, l1, j2, l2], NaN where j2 <= j1."""
+        J, L = self.J, self.L
+        out = {"s0": np.empty(2, np.float64), "s1": np.empty((J, L), np.float64), "p1": np.empty((J, L), np.float64),
+               "s2": np.empty((J, L, J, L), np.float64)}
+        self._s._chk(_L.slicer_scattering_read(self._sh, *(out[k].ctypes.data for k in ("s0", "s1", "p1", "s2"))))
+        return out
+
+    def modulus(self, d_map, j1, l1, j2=-1, l2=-1):
+        """The f64 [npix, npix] field u1 = W_{j1 l1} kappa, or W_{j2 l2} u1 with j2 > j1, recomputed from d_map."""
+        out = np.empty((self.npix, self.npix), np.float64)
+        self._s._chk(_L.slicer_scattering_modulus(self._sh, None if d_map is None else int(d_map), int(j1), int(l1),
+                                                  int(j2), int(l2), out.ctypes.data))
         return out
 
 
