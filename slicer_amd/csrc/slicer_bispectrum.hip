@@ -1,6 +1,6 @@
 // slicer_bispectrum.hip -- on-device binned bispectra of a kappa map.
 //
-// With khat = rfft2(kappa) in f64 (slicer_fft.hpp, the transform of the shear handle) and the bins of slicer_power_bins
+// With khat = rfft2(kappa) in f64 (slicer_fft.hip, the transform shared with the shear handle) and the bins of slicer_power_bins
 // minus the mode m2 = 0: F_b = irfft2(khat 1[mode in b]) and I_b = irfft2(1[mode in b]), both kept in f64
 // (slicer_fft_inverse_band), and for a triple i <= j <= k
 //   S_ijk = sum_x F_i F_j F_k,   T_ijk = n^4 sum_x I_i I_j I_k,   B_ijk = theta^4 / n^6 * (n^4 S_ijk) / T_ijk.
@@ -31,7 +31,7 @@
 #include <new>
 #include <vector>
 
-#include "slicer_fft.hpp"
+#include "slicer_power_internal.hpp"
 #include "slicer_host.hpp"
 
 namespace {

@@ -6,6 +6,8 @@
 #include <cstdio>
 #include <cstring>
 
+#include "slicer_fft.hpp"
+
 namespace {
 
 thread_local std::string g_null_err;
@@ -182,7 +184,7 @@ void DevAllocs::free_all()
 
 bool fft_size_supported(int n)
 {
-    if (n < 2 || n > 16384)
+    if (n < 2 || n > kFftMaxN)
         return false;
     for (int p : {2, 3, 5, 7})
         while (n % p == 0)

@@ -301,7 +301,7 @@ inline bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t 
 {
     return (uintptr_t)a < (uintptr_t)b + b_bytes && (uintptr_t)b < (uintptr_t)a + a_bytes;
 }
-bool fft_size_supported(int n);  // 2 <= n <= 16384 with prime factors 2, 3, 5, 7 only: what slicer_fft_create plans
+bool fft_size_supported(int n);  // 2 <= n <= kFftMaxN (slicer_fft.hpp) with prime factors 2, 3, 5, 7 only: what slicer_fft_create plans
 
 // ---- pass_plan.cpp ----
 inline bool is_pow2(int n) { return n > 0 && (n & (n - 1)) == 0; }

@@ -2,7 +2,7 @@
 // and the decoupled bandpowers (the definitions are in include/slicer_amd.h).
 //
 // The handle is built on a power handle (slicer_power.hip, row N7), whose plan, bins, slices and binning kernels it
-// uses through the internal entry points of slicer_fft.hpp:
+// uses through slicer_power_internal.hpp; the transforms are those of slicer_fft.hip:
 //   run       slicer_power_run_masked: the forward transforms load w * kappa (slicer_fft_forward_masked), the rest is
 //             slicer_power_run, so the spectra and the coupled bandpowers are bitwise those of the multiplied maps
 //   set_mask  k_pcl_mask builds w from the taper table and the user mask; k_pcl_moments sums w, w^2 and counts the
@@ -20,7 +20,7 @@
 #include <string>
 #include <vector>
 
-#include "slicer_fft.hpp"
+#include "slicer_power_internal.hpp"
 #include "slicer_host.hpp"
 
 namespace {

@@ -1,7 +1,7 @@
 // slicer_power.hip -- on-device binned auto and cross power spectra of kappa maps.
 //
 // For n_maps maps kappa_s, n x n f32 of side theta radians: khat_s = rfft2(kappa_s) in f64 on the [n][n/2+1] half
-// plane (slicer_fft.hpp, the transform of the shear handle).  Mode (i0, i1) has the integer radius^2 m2 = j0^2 + j1^2,
+// plane (slicer_fft.hip, the transform shared with the shear handle).  Mode (i0, i1) has the integer radius^2 m2 = j0^2 + j1^2,
 // j0 the signed fftfreq index of i0, j1 = i1; it is in bin b iff e2[b] <= m2 < e2[b+1] (e2 = the edges squared in f64;
 // the last bin is closed on the right), and
 //   C_st,b = theta^2 / n^4 * (1 / N_b) * sum over the bin's modes of Re(khat_s conj khat_t).
@@ -24,7 +24,7 @@
 #include <new>
 #include <vector>
 
-#include "slicer_fft.hpp"
+#include "slicer_power_internal.hpp"
 #include "slicer_host.hpp"
 
 namespace {
@@ -176,7 +176,7 @@ __global__ void k_power_finish(const double *partial, const int *slice_off, cons
 
 }  // namespace
 
-// The edges, or 0 .. npix-1 for NULL (then n_edges must be npix); "" if they are usable, else why not (slicer_fft.hpp).
+// The edges, or 0 .. npix-1 for NULL (then n_edges must be npix); "" if they are usable, else why not (slicer_power_internal.hpp).
 const char *check_edges(int npix, int n_edges, const double *edges, std::vector<double> &out)
 {
     if (n_edges < 2)

@@ -1,7 +1,7 @@
 // slicer_scattering.hip -- on-device wavelet scattering coefficients of a kappa map, orders 0, 1 and 2 (DESIGN.md S8
 // row N20; the filters, the transform and the outputs are defined in include/slicer_amd.h).
 //
-// Every W_{jl} f = |ifft2(fhat psi^_{jl})| is the modulus of a complex field, and the library owns real transforms only.
+// Every W_{jl} f = |ifft2(fhat psi^_{jl})| is the modulus of a complex field, and slicer_fft.hip has real transforms only.
 // psi^ is real, so with E and O its even and odd parts under negation of the mode index, fhat E and -i fhat O are both
 // Hermitian: x = irfft2(fhat E) and y = irfft2(-i fhat O) are the real and imaginary parts of the complex field.
 //   run   khat = rfft2(kappa) (slicer_fft_forward), s0 (k_scat_sums of the map itself); per (j1, l1): k_scat_filter

@@ -3,6 +3,7 @@
 //
 // The maps are not periodic: every n^2 map is zero-padded to P^2, P >= n + L a size the f64 transform plans, so that the
 // circular correlation of the padded maps is the linear one at every lag |dx|, |dy| <= L.
+// The transform is that of slicer_fft.hip; check_edges and first_at_least come from slicer_power_internal.hpp.
 //   set_weights  k_xi_norm sums w^2 and counts the values that are negative or not finite; k_xi_pad writes w padded in
 //                f64 (the second factor of every field load) and in f32; what = rfft2 (slicer_fft_forward), |what|^2
 //                (k_xi_spectra), W(r) = irfft2 (slicer_fft_inverse_band, every mode kept), W_b and sum W sqrt(m2)
@@ -23,7 +24,7 @@
 #include <new>
 #include <vector>
 
-#include "slicer_fft.hpp"
+#include "slicer_power_internal.hpp"
 #include "slicer_host.hpp"
 
 namespace {
@@ -33,7 +34,7 @@ constexpr int kXiCols = 64;       // columns (lags dy) of one k_xi_bin workgroup
 constexpr int kSumThreads = 256;  // sums of one k_xi_sum workgroup, one a thread
 constexpr int kNormGroups = 256;  // workgroups of k_xi_norm: the partials the host adds up
 constexpr int kMaxFields = 32;
-constexpr int kMaxP = 16384;
+constexpr int kMaxP = kFftMaxN;  // the largest padded size
 
 enum { SPEC_0 = 0, SPEC_PLUS, SPEC_MINUS, SPEC_CROSS };  // k_xi_spectra
 enum { BIN_PLAIN = 0, BIN_SPIN4, BIN_WEIGHT };           // k_xi_bin

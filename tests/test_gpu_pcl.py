@@ -212,6 +212,34 @@ def test_coupling_matrix(n, split, kind):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("n", [30, 45])
+def test_split_chains_at_both_parities(n):
+    """shear_split = 1 at 30 (rows in 2 passes, columns in 3) and at 45 (3 and 3: every pass buffer of the plan is in
+    use; odd, so the rows are loaded and stored as packed pairs and the last pair lacks its second row).  CASES has no odd
+    size under shear_split, and this handle is the only one behind the masked row load and the |khat|^2 column load.
+    The masked transform has the bits of the plain one of the f32 products (Pcl.spectrum against Power.spectrum), and M
+    is inside test_coupling_matrix's bound of numpy's f64 rfft2 / irfft2 route."""
+    maps = maps_for(n, 3)
+    user, width = MASKS["taper_holes"](n)
+    w_ref = pcl_np.mask(n, width, user)
+    edges = log_edges(n)
+    with Session(True) as ss:
+        d = [ss.dev(m) for m in maps]
+        with slicer_amd.Pcl(ss.s, n, ANGLE, 3, cross=True, edges=edges) as p:
+            set_mask(ss, p, user, width)
+            assert np.array_equal(p.mask().view(np.uint32), w_ref.view(np.uint32))
+            M = p.coupling()["M"]
+            p.run(d)
+            spectra = [p.spectrum(k) for k in range(3)]
+        err = float(np.abs(M - pcl_np.coupling_fft(w_ref, edges)).max())
+        print(f"n={n} split: max|M_dev - M_ref| / (1e-12 log2 n mean w^2) = {err / (m_bound(n, w_ref) / C_M):.4g}")
+        assert err <= m_bound(n, w_ref)
+        ref = run_power(ss.s, [w_ref * m for m in maps], ANGLE, True, edges, True)
+        for k in range(3):
+            assert np.array_equal(bits(spectra[k]), bits(ref["spectra"][k])), k
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("kind", sorted(MASKS))
 @pytest.mark.parametrize("n,split", CASES)
 def test_decoupling(n, split, kind):

@@ -66,7 +66,7 @@ def test_shear_matches_restatement(n, split):
 
 
 # Every supported size up to 1200, unforced.  The plan is not exported, so what the sizes reach is restated here from
-# plan_chain (slicer_shear.hip): 2 ... 15 are single-stage and stage-less plans (n = 2: a row chain of length 1);
+# plan_chain (slicer_fft.hip): 2 ... 15 are single-stage and stage-less plans (n = 2: a row chain of length 1);
 # up to 1024 the columns take one pass, from 1029 on two, and the second pass's radix runs through 2, 3, 5, 7 and their
 # products (1029 = 343 * 3, 1050 = 525 * 2, 1080 = 540 * 2, 1125 = 375 * 3, 1134 = 567 * 2, 1176 = 588 * 2, 1200 = 600 * 2, ...),
 # odd n (packed row pairs, a missing last row) included.

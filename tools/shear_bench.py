@@ -13,7 +13,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import slicer_amd  # noqa: E402
 
 HBM_BYTES_PER_S = 6.3e12  # MI355X peak HBM bandwidth (computed floor, not measured)
-LDS_POINTS, COL_CAP = 8192, 1024  # slicer_shear.hip: kLdsPoints, kColCap
+LDS_POINTS, COL_CAP = 8192, 1024  # slicer_fft.hip: kLdsPoints, kColCap
 
 
 def passes(L, cap):
