@@ -199,6 +199,28 @@ int slicer_rand_stream_get(slicer_handle h, uint32_t *v31);
  *                by the streams themselves as usual. */
 int slicer_set_stream(slicer_handle h, void *hip_stream);
 
+/* ---- the deposit: hostile input -------------------------------------------------------------------------------------
+ * What positions and masses that are not ordinary numbers do ("Non-finite and out-of-domain particles";
+ * asserted by tests/test_gpu_hostile_particles.py against the oracle, value classes in tests/hostile_np.py).
+ *   positions     Any f32 bit pattern is allowed.  Maps, per-type maps, nsel and the guard's return code are the
+ *                 oracle's on every route.  The guard is any(x < 0 | y < 0 | z < 0) per particle, so a NaN never trips it;
+ *                 a NaN coordinate fails the slab test or the field-of-view test and the particle drops out.  Deviation:
+ *                 the reference's guard takes a min_element per axis, which a NaN as the FIRST element of an axis
+ *                 silences; here a negative coordinate is reported wherever the NaN stands.
+ *   masses, F32 / F64 (per-particle: hydro types with massarr == 0)
+ *                 A mass that is NaN, negative or -inf has a NaN root: as in the reference its TSC footprint (3 x 3 pixels,
+ *                 clipped to the map) becomes NaN.  The NaN pixels of every output map are exactly the oracle's, for NGP
+ *                 also its +-inf pixels; on every other pixel the accumulator bounds hold against the exact sum over the
+ *                 entries whose capped mass is finite and >= 0.  NaN payloads are not part of the contract.  (+inf,
+ *                 like every mass above MAX_M = 1e3, counts as 0; 1000.0 exactly is kept.)
+ *   masses, FIXED64
+ *                 The integer accumulator cannot hold a NaN: a contribution that is not finite adds nothing, the words are
+ *                 the sum of rint(c 2^e) over the finite contributions bit for bit, the map is finite everywhere, and nsel
+ *                 still counts the entry.
+ *   header masses massarr[t] of a type with npart[t] > 0 that is NaN, negative or infinite is refused by slicer_file_begin
+ *                 with SLICER_ERR_ARG (the message names type and value): such a header is corrupt and would poison every
+ *                 pixel the species touches.  0 stays what it is (hydro types: masses follow per particle).  A finite value
+ *                 above MAX_M is deposited as is, as in the reference: the cap applies to per-particle masses only. */
 int slicer_plane_begin(slicer_handle h, const slicer_plane_desc *desc);
 int slicer_file_begin(slicer_handle h, const slicer_file_desc *file);
 /* pos: AoS [n][3] f32 exactly as in the POS block (raw file units), host memory.  mass: per-particle

@@ -4,6 +4,7 @@
 #include "slicer_host.hpp"
 
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -321,6 +322,13 @@ int slicer_file_begin(slicer_handle h, const slicer_file_desc *file)
     for (int a = 0; a < 3; a++)
         if (file->sgn[a] != 1 && file->sgn[a] != -1)
             return fail(h, SLICER_ERR_ARG, "sgn[%d] = %d is not +-1", a, file->sgn[a]);
+    // A constant header mass that is NaN, negative or infinite belongs to a corrupt header and would poison every pixel
+    // the species touches; refused here, so that no constant-mass kernel has to test for it.  (0 is the hydro types'
+    // "masses follow per particle"; a finite value above MAX_M is deposited as is, as in the reference.)
+    for (int t = 0; t < 6; t++)
+        if (file->npart[t] > 0 && !(file->massarr[t] >= 0.0 && file->massarr[t] <= DBL_MAX))
+            return fail(h, SLICER_ERR_ARG, "slicer_file_begin: massarr[%d] = %g is negative or not finite", t,
+                        file->massarr[t]);
     h->file = *file;
     h->in_file = true;
     h->file_serial++;

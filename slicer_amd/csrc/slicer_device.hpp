@@ -574,6 +574,11 @@ __device__ __forceinline__ unsigned long long rn_scaled_u64(float w, double scal
     return (unsigned long long)__double_as_longlong(fma((double)w, scale, 0x1p52)) & 0xFFFFFFFFFFFFFull;
 }
 
+// A TSC contribution sqrt(m) w * sqrt(m) w' of a per-particle mass m that is NaN or negative (sqrtf -> NaN) is NaN; the
+// integer accumulators skip it (rn_scaled_u64 / __double2ll_rn of a NaN is a meaningless finite number).  Capped masses
+// are <= MAX_M, so +-inf cannot occur; the test covers it all the same.
+__device__ __forceinline__ bool contribution_finite(float c) { return fabsf(c) <= 3.402823466e+38f; }
+
 // densitymaps.cpp:367-369: masses above MAX_M (1e3) are zeroed
 __device__ __forceinline__ float cap_mass(float m) { return m > 1000.0f ? 0.0f : m; }
 

@@ -14,7 +14,9 @@ namespace slicer {
 // ---------------------------------------------------------------------------------------------
 // deposit of one selected entry into a global accumulator map
 // ---------------------------------------------------------------------------------------------
-template <int ACC>
+// HAS_MASS: c may be NaN (per-particle mass NaN or negative); the float atomics carry it to the map as the reference
+// does, the FIXED64 accumulator skips it (slicer_tile_deposit.hip: lds_add)
+template <int ACC, bool HAS_MASS>
 __device__ __forceinline__ void add_global(void *map, size_t idx, float c, const PassParams &P)
 {
     if (ACC == kF32) {
@@ -22,12 +24,14 @@ __device__ __forceinline__ void add_global(void *map, size_t idx, float c, const
     } else if (ACC == kF64) {
         atomicAdd(reinterpret_cast<double *>(map) + idx, (double)c);
     } else if (ACC == kFixed64) {
+        if (HAS_MASS && !contribution_finite(c))
+            return;
         long long v = __double2ll_rn((double)c * P.fixed_scale);
         atomicAdd(reinterpret_cast<unsigned long long *>(map) + idx, (unsigned long long)v);
     }
 }
 
-template <int MAS, int ACC, bool POW2>
+template <int MAS, int ACC, bool POW2, bool HAS_MASS>
 __device__ __forceinline__ void deposit_global(void *map, float xs, float ys, float m, float sm, const PassParams &P)
 {
     const int nn = P.nn;
@@ -60,7 +64,7 @@ __device__ __forceinline__ void deposit_global(void *map, float xs, float ys, fl
                 int px = gx + a - 1;
                 if (px < 0 || px >= nn)
                     continue;
-                add_global<ACC>(map, (size_t)px + (size_t)nn * (size_t)py, wx[a] * wy[b], P);
+                add_global<ACC, HAS_MASS>(map, (size_t)px + (size_t)nn * (size_t)py, wx[a] * wy[b], P);
             }
         }
     }
@@ -103,7 +107,7 @@ __global__ __launch_bounds__(256) void k_direct(const float *__restrict__ pos, c
                     if (!project(x, y, z, ni, nj, P, xs, ys))
                         continue;
                     atomicAdd(&s_cnt[p], 1u);
-                    deposit_global<MAS, ACC, POW2>(T.acc[p], xs, ys, m, sm, P);
+                    deposit_global<MAS, ACC, POW2, HAS_MASS>(T.acc[p], xs, ys, m, sm, P);
                 }
         }
     }
@@ -242,7 +246,7 @@ __global__ __launch_bounds__(256) void k_thin_deposit(const float *__restrict__ 
                 if (!((double)u < thr))
                     continue;  // ms = 0: contributes nothing (adds of +0.0f in the reference)
                 const float m = (float)(mfac * (double)m0);  // ms.push_back(pow(2, snopt) * num_float1)
-                deposit_global<MAS, ACC, POW2>(T.acc[0], xs, ys, m, sqrt_mass(m), P);
+                deposit_global<MAS, ACC, POW2, HAS_MASS>(T.acc[0], xs, ys, m, sqrt_mass(m), P);
             }
     }
     // selected-entry counter (all selected entries, kept or not, as totPartxyi counts them)

@@ -38,13 +38,20 @@ struct TileQuantum {
     float cmin;               // 2^(le - 25): every contribution >= this is an exact multiple of the quantum
 };
 
-template <int ACC>
+// HAS_MASS: the contribution carries a per-particle mass, which may be NaN or negative (sqrt -> NaN).  The f64 cells
+// carry such a NaN to the map as the reference does; the FIXED64 accumulator cannot hold one, so there a contribution
+// that is not finite adds nothing (include/slicer_amd.h, "hostile input").  Constant masses are checked on the host
+// (slicer_file_begin): those instantiations have no test here.
+template <int ACC, bool HAS_MASS>
 __device__ __forceinline__ void lds_add(typename AccT<ACC>::lds *cell, float c, const PassParams &P, const TileQuantum &Q)
 {
-    if (ACC == kF32 || ACC == kF64)
+    if (ACC == kF32 || ACC == kF64) {
         atomicAdd(reinterpret_cast<double *>(cell), (double)c);  // ds_add_f64
-    else if (ACC == kFixed64)
+    } else if (ACC == kFixed64) {
+        if (HAS_MASS && !contribution_finite(c))
+            return;
         atomicAdd(reinterpret_cast<unsigned long long *>(cell), rn_scaled_u64(c, P.fixed_scale));  // ds_add_u64
+    }
     else if (kIntCells<ACC>)
         atomicAdd(reinterpret_cast<unsigned long long *>(cell), rn_scaled_u64(c, Q.scale));
 }
@@ -187,7 +194,10 @@ __device__ __forceinline__ void deposit_record(float xs, float ys, float mraw, f
             if (HAS_MASS && m == 0.0f)
                 return;  // (a mass above MAX_M counts as 0: nine additions of +0)
             const float cmin = fminf(wx[0], wx[2]) * fminf(wy[0], wy[2]);
-            if (cmin < Q.cmin) {  // rare: a contribution that is not a multiple of the tile's quantum
+            // rare: a contribution that is not a multiple of the tile's quantum.  With per-particle masses also a NaN
+            // (mass NaN or negative: every weight is NaN), which must not reach rn_scaled_u64: slow_record hands it to
+            // the float atomic, and the map's pixel becomes NaN as in the reference
+            if (HAS_MASS ? !(cmin >= Q.cmin) : cmin < Q.cmin) {
                 const unsigned k = atomicAdd(s_nslow, 1u);
                 if (k < kSlowCap)
                     s_slow[k] = make_uint2(c, i);
@@ -207,7 +217,7 @@ __device__ __forceinline__ void deposit_record(float xs, float ys, float mraw, f
                 const int px = gx + a - 1;
                 if (CHECK && (px < 0 || px >= nn))
                     continue;
-                lds_add<ACC>(cell0 + b * W + a, wx[a] * wy[b], P, Q);
+                lds_add<ACC, HAS_MASS>(cell0 + b * W + a, wx[a] * wy[b], P, Q);
             }
         }
     }
@@ -613,7 +623,8 @@ __device__ __forceinline__ void merged_run(const float2 *__restrict__ sxy, float
                         if ((int)lane_id() == lead && tot)
                             atomicAdd(reinterpret_cast<unsigned long long *>(tile + cell0 + b * W + a), tot);
                     } else if (ACC == kFixed64) {
-                        const unsigned long long tot = wave_sum(in ? rn_scaled_u64(cf, P.fixed_scale) : 0ull);
+                        const bool add = in && (!HAS_MASS || contribution_finite(cf));  // (see lds_add)
+                        const unsigned long long tot = wave_sum(add ? rn_scaled_u64(cf, P.fixed_scale) : 0ull);
                         if ((int)lane_id() == lead && tot)
                             atomicAdd(reinterpret_cast<unsigned long long *>(tile + cell0 + b * W + a), tot);
                     } else {
@@ -622,7 +633,7 @@ __device__ __forceinline__ void merged_run(const float2 *__restrict__ sxy, float
                             atomicAdd(reinterpret_cast<double *>(tile + cell0 + b * W + a), tot);
                     }
                 } else if (in) {
-                    lds_add<ACC>(tile + cell + b * W + a, cf, P, Q);
+                    lds_add<ACC, HAS_MASS>(tile + cell + b * W + a, cf, P, Q);
                 }
             }
         }

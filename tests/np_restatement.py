@@ -14,6 +14,11 @@ F32 = np.float32
 F64 = np.float64
 
 
+# Non-finite input (tests/hostile_np.py): the IEEE "invalid" flag -- a signalling NaN converted, inf - inf, the root of a
+# negative mass -- is what the C oracle raises silently; here it must not become a warning.  Results are unchanged.
+_quiet = np.errstate(invalid="ignore")
+
+
 def _wrap(v):
     v = v.astype(F32)
     hi = v.astype(F64) > 1.0
@@ -26,6 +31,7 @@ def _wrap(v):
 _FACE = {1: (0, 1, 2), 2: (0, 2, 1), 3: (1, 2, 0), 4: (1, 0, 2), 5: (2, 0, 1), 6: (2, 1, 0)}
 
 
+@_quiet
 def transform(raw, boxsize, sgn, face, center, rcase):
     raw = np.asarray(raw, F32).reshape(-1, 3)
     b = []
@@ -43,6 +49,7 @@ def transform(raw, boxsize, sgn, face, center, rcase):
     return x, y, z
 
 
+@_quiet
 def select_project(x, y, z, m, ld, ld2, boxsize, nrep, fov, npix):
     """m: f32 array per particle (already MAX_M-capped) -> xs, ys, ms, idx (reference order)."""
     minD = F64(ld) / F64(boxsize) * 1.e+3 / 1.0
@@ -84,6 +91,7 @@ def weight(ixx, ixh, dx):
     return np.where(Ad <= 0.5 * F64(dx), w1, np.where(Ad <= 0.5 * 3.0 * F64(dx), w2, F32(0))).astype(F32)
 
 
+@_quiet
 def tsc_contributions(xs, ys, ws, nn):
     """Per-particle 9 (pixel, value) pairs in reference j-order; pixel = -1 if clipped."""
     dl = 1. / F64(nn)
@@ -105,6 +113,7 @@ def tsc_contributions(xs, ys, ws, nn):
     return pix, val
 
 
+@_quiet
 def gridist_w(xs, ys, ws, nn, do_ngp):
     """Sequential f32 accumulation in particle order (slow python loop over entries; small cases only)."""
     grid = np.zeros(nn * nn, F32)

@@ -10,6 +10,8 @@ observables, all compared exactly:
   nsel           per-type selected counts == the oracle's.
 tests/golden/k1_edges.npz holds raw positions at the kernel's decision edges (tests/k1_edges_np.py has the classes,
 tests/test_k1_edges_host.py keeps the file honest).
+Expect, run and check also serve tests/test_gpu_hostile_particles.py, which runs the same passes through ALGO_DIRECT as
+well and feeds per-particle masses that are NaN or negative (check compares NGP maps with the oracle's NaN pixels).
 """
 import functools
 import itertools
@@ -95,7 +97,9 @@ class Expect:
 
     def _make_tsc(self, p):
         xs, ys, ms, _ = self.entries[p]
-        ms = tnp.cap_mass(ms)
+        # (the cap at MAX_M is for per-particle masses only: densitymaps.cpp:367-369; a NaN or negative one poisons its
+        # footprint in the reference, and the FIXED64 accumulator skips the entry)
+        ms, _ = tdep.clean_mass(tnp.cap_mass(ms) if self.hydro else ms)
         pix, val = npr.tsc_contributions(xs, ys, ms, self.ps.npix)
         le = tnp.mass_le(ms.max(initial=0.0) if self.hydro else self.mconst)
         return SimpleNamespace(P=tnp.Pixels(pix, val, self.ps.npix, le), E=None, k=None, npix=self.ps.npix,
@@ -118,7 +122,7 @@ class Expect:
         return tot, toti, nsel
 
 
-def run(S, ex, ngp, chunks=None, deposit=None, **options):
+def run(S, ex, ngp, chunks=None, deposit=None, algo=slicer_amd.ALGO_BINNED, **options):
     """One pass over ex.pos as one file (deposit calls `chunks`, default one); -> per plane (tot, toti, nsel, acc), mask."""
     ps, r, n = ex.ps, ex.ps.rnd, len(ex.pos)
     for k in ("k1_general", "k1_stack", "sort2", "unit_rows", "bin_batch"):
@@ -129,7 +133,7 @@ def run(S, ex, ngp, chunks=None, deposit=None, **options):
     assert not set(options) - set(OPTION_KEYS), set(options) - set(OPTION_KEYS)
     S.plane_begin(ps.npix, ps.fov, [a for a, _ in ps.slabs], [b for _, b in ps.slabs], [ps.nrep] * len(ps.slabs),
                   mas=slicer_amd.MAS_NGP if ngp else slicer_amd.MAS_TSC, accum=F32A if ngp else FIXA,
-                  algo=slicer_amd.ALGO_BINNED, hydro=ex.hydro)
+                  algo=algo, hydro=ex.hydro)
     npart, massarr = [0] * 6, [0.0] * 6
     npart[ex.ptype], massarr[ex.ptype] = n, 0.0 if ex.hydro else ex.mconst
     S.file_begin(npart, massarr, ps.box, r["sgn"], r["face"], r["center"], r["rcase"])
@@ -149,26 +153,31 @@ def run(S, ex, ngp, chunks=None, deposit=None, **options):
     return out, S.algo_mask()
 
 
-def check(ex, out, mask, ngp, fast=True, sort2=False, tag=""):
-    assert (mask & 7) == 1 << slicer_amd.ALGO_BINNED, f"{tag}: the binned path did not run alone: mask {mask:#x}"
-    if fast:
-        assert mask & FAST and not mask & GENERAL, f"{tag}: the fast kernel did not run alone: mask {mask:#x}"
+def check(ex, out, mask, ngp, fast=True, sort2=False, tag="", algo=slicer_amd.ALGO_BINNED):
+    """NGP maps are compared bit for bit, any NaN of the oracle's matching any NaN here (tdep.same_bits: a pixel that is
+    NaN on one side only differs)."""
+    if algo == slicer_amd.ALGO_DIRECT:
+        assert (mask & 7) == 1 << slicer_amd.ALGO_DIRECT and not mask & (FAST | GENERAL), f"{tag}: DIRECT did not run alone: mask {mask:#x}"
     else:
-        assert mask & GENERAL and not mask & FAST, f"{tag}: the pass was not refused: mask {mask:#x}"
+        assert (mask & 7) == 1 << slicer_amd.ALGO_BINNED, f"{tag}: the binned path did not run alone: mask {mask:#x}"
+        if fast:
+            assert mask & FAST and not mask & GENERAL, f"{tag}: the fast kernel did not run alone: mask {mask:#x}"
+        else:
+            assert mask & GENERAL and not mask & FAST, f"{tag}: the pass was not refused: mask {mask:#x}"
     total = 0
     for p, (tot, toti, nsel, acc) in enumerate(out):
         t = f"{tag} plane {p}"
         if ngp:
             ref_tot, ref_toti, ref_nsel = ex.ngp(p)
             assert np.array_equal(nsel, ref_nsel), f"{t}: nsel {nsel} != {ref_nsel}"
-            assert np.array_equal(tot.view(np.uint32), ref_tot.view(np.uint32)), f"{t}: NGP map differs"
-            assert np.array_equal(toti.view(np.uint32), ref_toti.view(np.uint32)), f"{t}: NGP type maps differ"
+            assert tdep.same_bits(tot, ref_tot), f"{t}: NGP map differs"
+            assert tdep.same_bits(toti, ref_toti), f"{t}: NGP type maps differ"
             total += int(ref_nsel.sum())
         else:
             case = ex.tsc(p)
             assert int(nsel[ex.ptype]) == case.n and int(nsel.sum()) == case.n, f"{t}: nsel {nsel} != {case.n}"
             assert np.array_equal(tot.view(np.uint32), toti[ex.ptype].view(np.uint32)), t
-            tdep.check(case, tot, acc, mask, FIXA, 0, int(sort2), tag=t)
+            tdep.check(case, tot, acc, mask, FIXA, 0, int(sort2), tag=t, algo=algo)
             total += case.n
     return total
 

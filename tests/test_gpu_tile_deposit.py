@@ -10,6 +10,10 @@ derived, none measured, compared in integer arithmetic:
 J (tile_np.addends) is restated from the forced tile geometry, the chunks per launch and the part rule of
 k_build_items, including its lower whole-bin cap in launches with integer cells.
 Every input condition -- records per bin, predicted noted records, k >> J -- is asserted before the GPU is called.
+Per-particle masses that are NaN or negative (tests/test_gpu_hostile_particles.py): E, k and J come from the other
+entries (clean_mass), the NaN pixels of an F32 / F64 map must be exactly the oracle's (Case.nan_mask) and are left out
+of the value comparison; a FIXED64 map holds no NaN.  With ALGO_DIRECT every contribution is an atomic add of its own:
+J = k.
 """
 import functools
 
@@ -101,6 +105,15 @@ def decade_masses(n, rng, top=2e-5):
     return m
 
 
+def clean_mass(ms):
+    """Capped masses with the entries that poison a TSC map (NaN or negative: the root is NaN) set to 0 -> masses, and
+    which entries those were."""
+    ms = np.asarray(ms, np.float32)
+    with np.errstate(invalid="ignore"):
+        ok = np.isfinite(ms) & (ms >= 0)
+    return np.where(ok, ms, np.float32(0)).astype(np.float32), ~ok
+
+
 class Case:
     """Positions (and masses) of one species, cut into deposit calls; the restatement of what the design does with
     them for a tile geometry."""
@@ -112,7 +125,12 @@ class Case:
         n = len(self.pos)
         self.files = files if files is not None else [[(0, n)]]  # files -> deposit calls (first, end)
         xs, ys, ms, idx = forward(self.pos, mass, 0.0 if self.hydro else mconst, npix)
-        self.xs, self.ys, self.ms, self.idx = xs, ys, ms, idx
+        self.nan_mask = None  # the oracle's NaN pixels (TSC), where a mass poisons its footprint
+        capped = ms
+        ms, poisoned = clean_mass(capped)
+        if poisoned.any():
+            self.nan_mask = np.isnan(oracle.gridist_w(xs, ys, capped, npix, False))
+        self.xs, self.ys, self.ms, self.idx, self.poisoned = xs, ys, ms, idx, poisoned
         gx, gy = centre_pixels(xs, ys, npix)
         self.gx, self.gy = gx, gy
         ntx = (npix + (1 << tl) - 1) >> tl
@@ -143,14 +161,14 @@ class Case:
         return int(sel.sum())
 
 
-def run(S, case, accum, k4_int, sort2=0, pending=32, ngp=False):
+def run(S, case, accum, k4_int, sort2=0, pending=32, ngp=False, algo=slicer_amd.ALGO_BINNED):
     S.set_option("tile_log2", case.tl)
     S.set_option("tile_h_log2", case.tl)
     S.set_option("k4_int", k4_int)
     S.set_option("sort2", sort2)
     S.set_option("pending", pending)
     S.plane_begin(case.npix, FOV, [LD], [LD2], mas=slicer_amd.MAS_NGP if ngp else slicer_amd.MAS_TSC, accum=accum,
-                  algo=slicer_amd.ALGO_BINNED, hydro=case.hydro)
+                  algo=algo, hydro=case.hydro)
     for f in case.files:
         npart, massarr = [0] * 6, [0.0] * 6
         npart[case.ptype] = sum(b - a for a, b in f)
@@ -166,40 +184,58 @@ def run(S, case, accum, k4_int, sort2=0, pending=32, ngp=False):
         acc = S.to_host(ptrs[case.ptype], (case.npix, case.npix), np.float64 if accum == F64A else np.uint64)
     tot, toti, nsel = S.plane_read(0)
     mask = S.algo_mask()  # (after the read: the pending chunks' tile launch has happened)
-    assert (mask & 7) == 1 << slicer_amd.ALGO_BINNED, f"the binned path did not run alone: mask {mask:#x}"
+    assert (mask & 7) == 1 << algo, f"the {'binned' if algo == slicer_amd.ALGO_BINNED else 'direct'} path did not run alone: mask {mask:#x}"
     assert int(nsel[case.ptype]) == len(case.xs) and int(nsel.sum()) == len(case.xs)
-    assert np.array_equal(tot.view(np.uint32), toti[case.ptype].view(np.uint32))  # one species: the sum is that map
+    assert same_bits(tot, toti[case.ptype])  # one species: the sum is that map
     return tot, acc, mask
 
 
-def check(case, tot, acc, mask, accum, k4_int, sort2=0, pending=32, tag=""):
+def same_bits(a, b):
+    """Bit for bit, any NaN equal to any NaN (payloads are not part of the contract)."""
+    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
+    q = np.uint32(0x7FC00000)
+    return np.array_equal(np.where(np.isnan(a), q, a.view(np.uint32)), np.where(np.isnan(b), q, b.view(np.uint32)))
+
+
+def check(case, tot, acc, mask, accum, k4_int, sort2=0, pending=32, tag="", algo=slicer_amd.ALGO_BINNED):
     P, E, k = case.P, case.E, case.k
-    int_cells = k4_int == 2 and accum != FIXA
+    direct = algo == slicer_amd.ALGO_DIRECT
+    int_cells = k4_int == 2 and accum != FIXA and not direct
+    nan = case.nan_mask if getattr(case, "nan_mask", None) is not None else np.zeros((case.npix, case.npix), bool)
     assert bool(mask & (1 << 6)) == int_cells, f"{tag}: integer cells {'did not run' if int_cells else 'ran'}: {mask:#x}"
     assert bool(mask & (1 << 7)) == bool(sort2), f"{tag}: run-table walk: mask {mask:#x}"
     touched = np.zeros(case.npix * case.npix, bool)
     touched[P.upix] = True
     assert not tot.reshape(-1)[~touched].any(), f"{tag}: mass in a pixel no contribution reaches"
     if accum == FIXA:
+        assert np.isfinite(tot).all(), f"{tag}: a FIXED64 map holds a NaN or an infinity"
         want = P.full(P.fixed(case.fixed_exp), np.int64)
         bad = np.argwhere(acc.view(np.int64) != want)
         assert len(bad) == 0, f"{tag}: FIXED64 accumulator differs at {bad[:4]} of {len(bad)} pixels"
         want32 = (want.astype(np.float32) * np.float32(np.ldexp(1.0, -case.fixed_exp))).astype(np.float32)
         assert np.array_equal(tot.view(np.uint32), want32.view(np.uint32)), f"{tag}: FIXED64 map != RN32(acc)"
         return
-    J, _ = case.J(int_cells, pending)
-    extra = 0 if int_cells else k.astype(object)  # f64 cells: the tile sum is a sequential f64 sum
+    # the NaN pixels are exactly the oracle's; the bounds hold on all others
+    bad = np.argwhere(np.isnan(tot) != nan)
+    assert len(bad) == 0, f"{tag}: NaN pixels differ from the oracle's at {bad[:4]} of {len(bad)} ({int(nan.sum())} expected)"
+    keep = ~nan.reshape(-1)[P.upix]
+    if direct:  # one global atomic per contribution
+        J, extra = k, 0
+    else:
+        J, _ = case.J(int_cells, pending)
+        extra = 0 if int_cells else k.astype(object)  # f64 cells: the tile sum is a sequential f64 sum
     if accum == F64A:
-        assert np.array_equal(tot.view(np.uint32), acc.astype(np.float32).view(np.uint32)), f"{tag}: map != RN32(acc)"
-        err = abs(P.units(acc) - E) * (1 << 53)
+        assert np.array_equal(np.isnan(acc), nan), f"{tag}: NaN pixels of the accumulator differ from the oracle's"
+        assert same_bits(tot, acc.astype(np.float32)), f"{tag}: map != RN32(acc)"
+        err = abs(P.units(np.where(nan, 0.0, acc)) - E) * (1 << 53)
         lim = (2 * J.astype(object) + extra) * E
     else:
-        got = P.units(tot)
+        got = P.units(np.where(nan, np.float32(0), tot))
         err = abs(got - E) * (1 << 53)
         lim = ((2 * J.astype(object) - 1) * (1 << 29) + extra) * E
-        one = (k == 1)
+        one = (k == 1) & keep
         assert np.all(got[one] == E[one]), f"{tag}: a pixel with a single contribution is not exact"
-    bad = np.nonzero(err > lim)[0]
+    bad = np.nonzero((err > lim) & keep)[0]
     if len(bad):
         w = bad[np.argmax([float(err[i]) / max(float(lim[i]), 1e-300) if lim[i] else np.inf for i in bad])]
         raise AssertionError(f"{tag}: {len(bad)} pixels outside the {ACC_IDS[accum]} bound; worst pixel {P.upix[w]}: "
