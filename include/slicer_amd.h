@@ -933,8 +933,8 @@ int slicer_l1norm_destroy(slicer_l1norm_handle lh);
  *   border taper        (NaMaster's C1 apodisation, separable) on an axis x_i = min(i, n-1-i) + 0.5, t = x_i / width_pix,
  *                       f_i = 1 if t >= 1, else t - sin(2 pi t) / (2 pi); w = (float)(f[i0] * f[i1]), the product in f64;
  *                       with a user mask as well, that value times the user mask in f32
- * Out of scope: spin-2 fields and E/B, purification, contaminant deprojection, bandpower window functions, a different
- * mask per map, noise-bias subtraction, the curved sky.
+ * Out of scope: purification, contaminant deprojection, bandpower window functions, a different mask per map,
+ * noise-bias subtraction, the curved sky.  Spin-2 fields and E/B are row N21 below (slicer_pcl2_*).
  *   slicer_pcl_taper     host only: f [npix] in f64.  npix < 2, or a width that is not positive and finite: SLICER_ERR_ARG
  *   slicer_pcl_create    arguments and refusals as slicer_power_create, except that the edges are required (NULL:
  *                        SLICER_ERR_ARG) and more than SLICER_PCL_MAX_BINS bins are SLICER_ERR_UNSUPPORTED.  Device memory
@@ -965,6 +965,86 @@ int slicer_pcl_run(slicer_pcl_handle ph, const float *const *d_maps);
 int slicer_pcl_spectrum(slicer_pcl_handle ph, int32_t map, double *host);
 int slicer_pcl_read(slicer_pcl_handle ph, double *cl, double *coupled, double *ell_mean, int64_t *counts);
 int slicer_pcl_destroy(slicer_pcl_handle ph);
+
+/* ---- E/B pseudo-C_l of masked shear maps, spin-2 ----
+ * Notation of rows N7 and N17 above: n = npix, the [n][n/2+1] half plane, the integer mode indices j0 = fftfreq (-n/2 for
+ * the Nyquist row of an even n) and j1 = 0 ... n/2 in the half plane (fftfreq in the full plane), m2 = j0^2 + j1^2, the
+ * bins, H_b, F_b and N_b (the m2 = 0 mode stays in a bin when r_0 = 0), and one shared f32 mask w built exactly as
+ * slicer_pcl_set_mask builds it (taper, user mask, or both).
+ *   spin phases         for a mode with m2 > 0, every operation one IEEE f64 operation, no FMA:
+ *                         c2 = (j0^2 - j1^2) / m2, s2 = 2 j0 j1 / m2 (the integers are exact),
+ *                         c4 = c2 c2 - s2 s2 (each product rounded, then the difference), s4 = 2 (c2 s2);
+ *                       at m2 = 0, c2 = c4 = 1 and s2 = s4 = 0: the rotation is the identity there.  On the Nyquist lines of
+ *                       an even n (|j0| = n/2 or |j1| = n/2) s2 = s4 = 0 and c2, c4 keep their values: the grid cannot
+ *                       tell +n/2 from -n/2, so the odd functions take the mean over the two aliases (otherwise the
+ *                       sine-weighted indicators would not be Hermitian and their inverse transforms not real).  There
+ *                       c2^2 + s2^2 < 1, so E and B are NOT separated on those lines; edges that stop below n/2 avoid them.
+ *                       (C_s, S_s) = (c2, s2) for s = 2 and (c4, s4) for s = 4.
+ *   E/B spectra         of a field (gamma1, gamma2): g1 = rfft2(w gamma1), g2 = rfft2(w gamma2), bitwise row N17's masked
+ *                       transforms; Ehat = c2 g1 + s2 g2, Bhat = c2 g2 - s2 g1 on the real and imaginary parts separately,
+ *                       each product rounded, then the sum.  This inverts row N6's filters (axis 0 is the slow axis).  With
+ *                       with_kappa the field's third component is khat = rfft2(w kappa), bitwise row N17's.
+ *   component list      per field E, B, and kappa if present; field f's components are 3f, 3f+1, 3f+2 (2f, 2f+1 without kappa)
+ *   coupled bandpowers  Ct_xy,b = theta^2 / n^4 * (1 / N_b) * sum over H_b of Re(x conj y): slicer_power_run's slices,
+ *                       summation order and finish on those spectra, no atomics
+ *   coupling matrices   for s = 2, 4, what = fft2(w) unnormalised:
+ *                         M_s[b][b'] = 1 / (N_b n^4) * sum over k in H_b, k' in F_b' of |what(k - k')|^2 *
+ *                                      (C_s(k) C_s(k') + S_s(k) S_s(k'))      (the weight cos s(phi' - phi))
+ *                         X_s[b][b'] = the same sum with (C_s(k) S_s(k') - S_s(k) C_s(k'))  (sin s(phi' - phi); zero for a
+ *                                      mirror-symmetric mask, not in general)
+ *                       and M_0 is row N17's M, bitwise.  Computed per non-empty b' with A = irfft2(|rfft2 w|^2):
+ *                       G_c = irfft2(1[F_b'] C_s), G_s = irfft2(1[F_b'] S_s), Q_c = Re rfft2(A G_c) / n^2,
+ *                       Q_s = Re rfft2(A G_s) / n^2, M_s[.][b'] = the binned mean over H_b of C_s(k) Q_c + S_s(k) Q_s and
+ *                       X_s[.][b'] that of C_s(k) Q_s - S_s(k) Q_c.  Rows and columns of empty bins are 0.  Five inverse and
+ *                       five forward transforms per non-empty bin, against row N17's one and one.
+ *   decoupling          the mask's first-order mixing, spectra taken flat within a bin as in row N17:
+ *                         kappa kappa:                 Ct = M_0 C
+ *                         (kE, kB) of a field pair:    the 2B x 2B system [[M_2, -X_2], [X_2, M_2]]
+ *                         (EE, EB, BE, BB) of a pair (f, g), EB = E_f B_g and BE = B_f E_g: the 4B x 4B system
+ *                             [ P -T -T  R ]
+ *                             [ T  P -R -T ]     P = (M_0 + M_4) / 2, R = (M_0 - M_4) / 2, T = X_4 / 2
+ *                             [ T -R  P -T ]
+ *                             [ R  T  T  P ]
+ *                         (for f = g, BE is EB).  Each system is restricted to the active bins (N_b > 0), factorised once per
+ *                       mask by row N17's f64 LU with partial pivoting on the host and solved per pair in slicer_pcl2_read; the
+ *                       other bins read NaN.  Because the 4B system is solved on the host, at most SLICER_PCL2_MAX_BINS bins.
+ * Out of scope: purification, bandpower window functions, per-field masks, noise bias, the curved sky, spin-1, and the
+ * driver reading --raytrace outputs (slicer_pcl2_run takes any device maps, the ray tracer's included).
+ *   slicer_pcl2_phases    host only: C, S [npix][npix/2+1] in f64 for spin 2 or 4.  Another spin, npix < 2 or a null
+ *                         output: SLICER_ERR_ARG
+ *   slicer_pcl2_create    n_fields fields of (gamma1, gamma2) and, with with_kappa = 1, kappa.  cross = 0: the pairs within
+ *                         each field, field after field, in slicer_power_create's pair order over (E, B, kappa):
+ *                         EE, EB, Ek, BB, Bk, kk (EE, EB, BB without kappa).  cross = 1: all pairs i <= j of the component
+ *                         list in slicer_power_create's pair order.  Refusals as slicer_pcl_create; more than
+ *                         SLICER_PCL2_MAX_BINS bins, or n_fields outside 1 ... 128 / (2 + with_kappa) (the power handle's
+ *                         128 maps): SLICER_ERR_UNSUPPORTED; with_kappa or cross not 0 or 1: SLICER_ERR_ARG.  Device memory
+ *                         beyond slicer_power_create's over the components: A, G_c, G_s (8 npix^2 each), w (4 npix^2) and
+ *                         four spectra of 16 npix (npix/2+1) bytes (SLICER_ERR_NOMEM)
+ *   slicer_pcl2_set_mask  as slicer_pcl_set_mask; "coupling matrix singular" (SLICER_ERR_ARG) for a zero or non-finite pivot
+ *                         in any of the three systems.  A new mask invalidates the last run; after a refused one the handle
+ *                         has no mask.  Waits for the stream
+ *   slicer_pcl2_read_mask w; slicer_pcl2_coupling: M_0, M_2, X_2, M_4, X_4 [B][B] row-major, mean(w), mean(w^2) (any of
+ *                         them NULL).  Before a mask: SLICER_ERR_STATE
+ *   slicer_pcl2_run       the device f32 maps, per field gamma1, gamma2, then kappa with with_kappa; enqueued, no
+ *                         synchronisation.  Before a mask: SLICER_ERR_STATE
+ *   slicer_pcl2_spectrum  the spectrum of component comp (0, 1, 2 = E, B, kappa) of field `field` of the last run; auto mode
+ *                         keeps the last field's only (SLICER_ERR_STATE for another)
+ *   slicer_pcl2_read      cl (decoupled) and coupled [pairs][B] in the order above, ell_mean and counts [B] (any of them
+ *                         NULL); waits for the stream.  Before a run: SLICER_ERR_STATE
+ * No atomics: the same mask and maps give bitwise the same matrices and bandpowers. */
+typedef struct slicer_pcl2_s *slicer_pcl2_handle;
+#define SLICER_PCL2_MAX_BINS 128
+int slicer_pcl2_phases(int32_t npix, int32_t spin, double *C, double *S);
+int slicer_pcl2_create(slicer_handle h, int32_t npix, double angle_deg, int32_t n_fields, int32_t with_kappa,
+                       int32_t cross, int32_t n_edges, const double *edges, slicer_pcl2_handle *out);
+int slicer_pcl2_set_mask(slicer_pcl2_handle ph, const float *d_mask, double taper_width_pix);
+int slicer_pcl2_read_mask(slicer_pcl2_handle ph, float *host);
+int slicer_pcl2_coupling(slicer_pcl2_handle ph, double *M0, double *M2, double *X2, double *M4, double *X4,
+                         double *mean_w, double *mean_w2);
+int slicer_pcl2_run(slicer_pcl2_handle ph, const float *const *d_maps);
+int slicer_pcl2_spectrum(slicer_pcl2_handle ph, int32_t field, int32_t comp, double *host);
+int slicer_pcl2_read(slicer_pcl2_handle ph, double *cl, double *coupled, double *ell_mean, int64_t *counts);
+int slicer_pcl2_destroy(slicer_pcl2_handle ph);
 
 /* ---- Real-space two-point correlation functions xi_kk(theta), xi+(theta), xi-(theta) ----
  * Fields and weights.  A spin-0 field is one f32 map a; a spin-2 field is two, (a1, a2) = (gamma1, gamma2).  Every map is

@@ -19,6 +19,7 @@ from .lensing import SMOOTH_GAUSS, SMOOTH_MAP, SMOOTH_MAX_RADIUS, Smooth, smooth
 from .lensing import Noise, noise_sigma_pix, noise_words, smooth_noise_gain  # noqa: F401
 from .lensing import STARLET_MAX_SCALES, L1Norm, Starlet, starlet_gains  # noqa: F401
 from .lensing import PCL_MAX_BINS, Pcl, pcl_taper  # noqa: F401
+from .lensing import PCL2_B, PCL2_E, PCL2_KAPPA, PCL2_MAX_BINS, PclShear, spin_phases  # noqa: F401
 from .lensing import BETTI_MAX_NPIX, BETTI_MAX_THRESHOLDS, Betti  # noqa: F401
 from .lensing import SCATTERING_MAX_J, SCATTERING_MAX_L, Scattering, scattering_filter, scattering_reduce  # noqa: F401
 from .lensing import XI_CROSS, XI_MAX_BINS, XI_MINUS, XI_PLUS, XI_WEIGHTS, Xi, xi_bins  # noqa: F401

@@ -183,6 +183,17 @@ SYMBOLS = {
     "slicer_pcl_spectrum": (C.c_int, [_H, C.c_int32, C.c_void_p]),
     "slicer_pcl_read": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "slicer_pcl_destroy": (C.c_int, [_H]),
+    "slicer_pcl2_phases": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "slicer_pcl2_create": (C.c_int, [_H, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                     C.POINTER(C.c_void_p)]),
+    "slicer_pcl2_set_mask": (C.c_int, [_H, C.c_void_p, C.c_double]),
+    "slicer_pcl2_read_mask": (C.c_int, [_H, C.c_void_p]),
+    "slicer_pcl2_coupling": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "slicer_pcl2_run": (C.c_int, [_H, C.POINTER(C.c_void_p)]),
+    "slicer_pcl2_spectrum": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p]),
+    "slicer_pcl2_read": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "slicer_pcl2_destroy": (C.c_int, [_H]),
     "slicer_xi_bins": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
     "slicer_xi_create": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                    C.POINTER(C.c_void_p)]),

@@ -22,6 +22,13 @@
 //     masked pseudo-C_l of the kappa maps, the layout of the .cl_ file with '#' lines for the mask (mean_w, mean_w2,
 //     taper_arcmin, taper_pix, mask) and per pair the decoupled bandpower C_s_t followed by the coupled one Ct_s_t; and
 //     .pclm_<npix>_<suffix>.txt, the mode-coupling matrix M, one row per line.
+//   * --pcl-shear (with --pcl and --shear; at most 129 edges): the E/B pseudo-C_l of every source's (gamma1, gamma2) as
+//     they are written, with its kappa map, under --pcl's mask, edges and mode: .pcleb_<npix>_<suffix>.txt, the '#'
+//     lines and the bin columns of the .pcl_ file, then for the sources s <= t (cross; s = t with auto) the decoupled
+//     and the coupled bandpowers C_EE_s_t Ct_EE_s_t, and likewise EB, BE (s < t only: BE_s_s is EB_s_s), BB, kE, kB and,
+//     for s < t, kE_t_s and kB_t_s (XY_s_t: component X of source s against Y of source t; kk is in the .pcl_ file);
+//     and .pclebm_<npix>_<suffix>.txt, the coupling matrices M0, M2, X2, M4, X4 one after another, each under a
+//     '# <name>' line, one row per line.
 //   * --xi auto|cross with --xi-edges a0,a1,... (required; at most 513 edges in arcminutes, one arcminute being
 //     npix / (60 ANGLE) pixels) and optionally --xi-mask FILE.fits (an image of the maps' size, BITPIX -32 or -64, finite
 //     and >= 0: the weight map shared by all maps): <directory><simulation>.xi_<npix>_<suffix>.txt, the real-space
@@ -207,6 +214,7 @@ int LensingOptions::parse(int argc, char **argv, int &i)
             return bad("bad --pcl-taper (the width of the border taper in arcminutes, positive)");
         pcl_taper_given = true;
     } else if (a == "--pcl-mask" && has_value) pcl_mask = argv[++i];
+    else if (a == "--pcl-shear") pcl_shear = true;
     else if (a == "--xi" && has_value) xi = argv[++i];
     else if (a == "--xi-edges" && has_value) {
         if (!parse_doubles(argv[++i], xi_edges))
@@ -327,6 +335,8 @@ int LensingOptions::check() const
         {!pcl_mask.empty() && !pc, "--pcl-mask needs --pcl"},
         {pc && pcl_edges.empty(), "--pcl needs --pcl-edges (the bin edges in units of l_f)"},
         {pc && !pcl_taper_given && pcl_mask.empty(), "--pcl needs --pcl-taper or --pcl-mask (or both)"},
+        {pcl_shear && !pc, "--pcl-shear needs --pcl (the mask, the edges and the mode are those of --pcl)"},
+        {pcl_shear && !shear, "--pcl-shear needs --shear (the fields are the shear maps of the sources)"},
         {x && xi != "auto" && xi != "cross", "bad --xi (auto or cross)"},
         {x && no_kappa, "--xi needs --kappa (the correlation functions are those of the kappa maps)"},
         {!xi_edges.empty() && !x, "--xi-edges needs --xi"},
@@ -350,6 +360,9 @@ int LensingOptions::check() const
     for (const auto &[broken, message] : rules)
         if (broken)
             return bad(message);
+    if (pcl_shear && pcl_edges.size() > SLICER_PCL2_MAX_BINS + 1)
+        return bad("--pcl-shear: " + std::to_string(pcl_edges.size()) + " edges in --pcl-edges, at most " +
+                   std::to_string(SLICER_PCL2_MAX_BINS + 1));
     return 0;
 }
 
@@ -500,6 +513,18 @@ int LensingOutputs::create()
     if (!o.pcl.empty() && slicer_pcl_create(h, p.npix, p.fov, (int)zs.size(), o.pcl == "cross", (int)o.pcl_edges.size(),
                                             o.pcl_edges.data(), pclh.out()) != SLICER_OK)
         return fail(h, "slicer_amd: --pcl");
+    if (o.pcl_shear && zs.size() > 42) {
+        cerr << "slicer_amd: --pcl-shear: " << zs.size() << " sources, at most 42" << endl;
+        return 2;
+    }
+    if (o.pcl_shear) {
+        if (slicer_pcl2_create(h, p.npix, p.fov, (int)zs.size(), 1, o.pcl == "cross", (int)o.pcl_edges.size(),
+                               o.pcl_edges.data(), pcl2h.out()) != SLICER_OK)
+            return fail(h, "slicer_amd: --pcl-shear");
+        for (size_t k = 0; k < 2 * zs.size(); k++)
+            if (!pcl2_gamma.add(p.npix))
+                return fail(h, "slicer_amd: --pcl-shear");
+    }
     if (!o.xi.empty()) {
         const char *who = "slicer_amd: --xi";
         const vector<double> e = o.xi_edges_pix(p.npix, p.fov);
@@ -1124,10 +1149,14 @@ int LensingOutputs::source_shear(size_t s, const float *d_kappa)
         return fail(h, "slicer_amd: --kappa");
     if ((g && slicer_shear_fd(shh) != SLICER_OK) || (o.deflection && !g && slicer_shear_deflection(shh) != SLICER_OK))
         return fail(h, "slicer_amd: --shear");
-    for (int k = 0; k < (o.deflection ? 6 : 4); k++)
+    for (int k = 0; k < (o.deflection ? 6 : 4); k++) {
         if (slicer_shear_read(shh, g ? fd[k] : spectral[k], map.data()) != SLICER_OK ||
             !save(k < 4 ? "shear" : "deflection", token[k], s))
             return fail(h, "slicer_amd: --kappa");
+        if (pcl2h && k < 2 &&  // the gamma just written, kept on the device for --pcl-shear
+            slicer_copy_to_device(h, pcl2_gamma.maps[2 * s + k], map.data(), map.size() * sizeof(float)) != SLICER_OK)
+            return fail(h, "slicer_amd: --pcl-shear");
+    }
     if (xipmh) {  // xi+ and xi- of the gammas just written
         const int B = (int)o.xi_edges.size() - 1;
         float *g12[2] = {nullptr, nullptr};
@@ -1224,6 +1253,7 @@ int LensingOutputs::pseudo_spectra()
         o.pcl_taper_arcmin, taper_pix);
     cl += o.pcl_mask.empty() ? "none" : o.pcl_mask;
     add(cl, "\n# ell_lo ell_hi ell_mean n_modes");
+    const string head = cl;  // the '#' lines up to the first column names
     for (int s = 0; s < S; s++)
         for (int t = s; t < (cross ? S : s + 1); t++)
             add(cl, " C_%d_%d Ct_%d_%d", s, t, s, t);
@@ -1244,7 +1274,98 @@ int LensingOutputs::pseudo_spectra()
     for (int b = 0; b < B; b++)
         for (int k = 0; k < B; k++)
             add(m, k + 1 < B ? "%.17g " : "%.17g\n", M[(size_t)b * B + k]);
-    return write_table("mode-coupling matrix", ".pclm_", m);
+    if (const int rc = write_table("mode-coupling matrix", ".pclm_", m))
+        return rc;
+    return pcl2h ? shear_pseudo_spectra(mask.maps.empty() ? nullptr : mask.maps[0], taper_pix, head) : 0;
+}
+
+// --pcl-shear, after --pcl's own tables, with its mask.  The E/B table: `head` (the '#' lines of the .pcl_ table and its
+// bin columns' names), the names of the columns described at the top of this file, then per bin ell_lo ell_hi ell_mean
+// n_modes and per column pair the decoupled C and the coupled Ct (%.17g; nan for an empty bin).  The matrix table: '#'
+// lines (npix, the bin edges in multipoles), then under '# M0', '# M2', '# X2', '# M4', '# X4' the rows of each (%.17g).
+int LensingOutputs::shear_pseudo_spectra(const float *d_mask, double taper_pix, const string &head)
+{
+    const char *who = "slicer_amd: --pcl-shear";
+    const int S = (int)plan.zs.size(), B = (int)o.pcl_edges.size() - 1;
+    const bool cross = o.pcl == "cross";
+    const size_t n_rows = cross ? (size_t)(3 * S) * (3 * S + 1) / 2 : (size_t)6 * S;
+    if (slicer_pcl2_set_mask(pcl2h, d_mask, taper_pix) != SLICER_OK)
+        return fail(h, who);
+    vector<float *> maps(3 * (size_t)S);
+    for (int s = 0; s < S; s++) {
+        maps[3 * s] = pcl2_gamma.maps[2 * s];
+        maps[3 * s + 1] = pcl2_gamma.maps[2 * s + 1];
+        if (slicer_kappa_device_map(kh, s, &maps[3 * s + 2]) != SLICER_OK)
+            return fail(h, who);
+    }
+    vector<double> c(n_rows * B), ct(n_rows * B), ell(B), M[5];
+    vector<int64_t> counts(B);
+    for (auto &m : M)
+        m.resize((size_t)B * B);
+    if (slicer_pcl2_run(pcl2h, maps.data()) != SLICER_OK ||
+        slicer_pcl2_read(pcl2h, c.data(), ct.data(), ell.data(), counts.data()) != SLICER_OK ||
+        slicer_pcl2_coupling(pcl2h, M[0].data(), M[1].data(), M[2].data(), M[3].data(), M[4].data(), nullptr, nullptr) !=
+            SLICER_OK)
+        return fail(h, who);
+    // the table row of (component a of source s, component b of source t), a, b = 0, 1, 2 for E, B, kappa: the pair
+    // order of slicer_pcl2_create
+    const auto pair_of = [](int i, int j, int n) {
+        if (i > j)
+            std::swap(i, j);
+        return i * n - i * (i - 1) / 2 + (j - i);
+    };
+    const auto row = [&](int s, int a, int t, int b) {
+        return cross ? (size_t)pair_of(3 * s + a, 3 * t + b, 3 * S) : (size_t)6 * s + pair_of(a, b, 3);
+    };
+    struct Column {
+        string name;
+        size_t row;
+    };
+    vector<Column> cols;
+    static const char letter[3] = {'E', 'B', 'k'};
+    const auto column = [&](int s, int a, int t, int b) {
+        cols.push_back({string(1, letter[a]) + letter[b] + "_" + std::to_string(s) + "_" + std::to_string(t), row(s, a, t, b)});
+    };
+    for (int s = 0; s < S; s++)
+        for (int t = s; t < (cross ? S : s + 1); t++) {
+            column(s, 0, t, 0);
+            column(s, 0, t, 1);
+            if (s < t)
+                column(s, 1, t, 0);
+            column(s, 1, t, 1);
+            column(s, 2, t, 0);
+            column(s, 2, t, 1);
+            if (s < t) {
+                column(t, 2, s, 0);
+                column(t, 2, s, 1);
+            }
+        }
+    const double ell_f = 2.0 * M_PI / (p.fov * M_PI / 180.0);
+    string cl = head;
+    for (const Column &q : cols)
+        cl += " C_" + q.name + " Ct_" + q.name;
+    cl += "\n";
+    for (int b = 0; b < B; b++) {
+        add(cl, "%.17g %.17g %.17g %lld", o.pcl_edges[b] * ell_f, o.pcl_edges[b + 1] * ell_f, ell[b], (long long)counts[b]);
+        for (const Column &q : cols)
+            add(cl, " %.17g %.17g", c[q.row * B + b], ct[q.row * B + b]);
+        add(cl, "\n");
+    }
+    if (const int rc = write_table("E/B pseudo-spectra", ".pcleb_", cl))
+        return rc;
+    static const char *const name[5] = {"M0", "M2", "X2", "M4", "X4"};
+    string m;
+    add(m, "# npix %d\n# ell_edges", p.npix);
+    for (double r : o.pcl_edges)
+        add(m, " %.17g", r * ell_f);
+    add(m, "\n");
+    for (int k = 0; k < 5; k++) {
+        add(m, "# %s\n", name[k]);
+        for (int b = 0; b < B; b++)
+            for (int j = 0; j < B; j++)
+                add(m, j + 1 < B ? "%.17g " : "%.17g\n", M[k][(size_t)b * B + j]);
+    }
+    return write_table("spin-2 coupling matrices", ".pclebm_", m);
 }
 
 // --xi.  Both tables: '#' lines (npix, angle, source redshifts, mask: the file as given or "none", padded: P, the column

@@ -1,5 +1,5 @@
 // driver_lensing.hpp -- the lensing outputs of the SLICER_amd driver (slicer_main.cpp): their options, their host
-// planning and the device-0 work behind --kappa, --shear, --deflection, --raytrace, --power, --pcl, --xi, --moments, --peaks,
+// planning and the device-0 work behind --kappa, --shear, --deflection, --raytrace, --power, --pcl, --pcl-shear, --xi, --moments, --peaks,
 // --minkowski, --betti, --bispectrum, --smooth, --shape-noise, --starlet and --scattering (driver_lensing.cpp describes the options), with the small helpers the rest of the driver shares with them.
 #pragma once
 #include <deque>
@@ -25,6 +25,7 @@ struct LensingOptions {
     bool pcl_taper_given = false;
     double pcl_taper_arcmin = 0.0;    // --pcl-taper: the width of the border taper, 0 without it
     std::string pcl_mask;             // --pcl-mask: a FITS image of the map's size, "" without it
+    bool pcl_shear = false;           // --pcl-shear: with --pcl and --shear, the E/B pseudo-spectra as well (at most 129 edges)
     std::string xi;                   // "" (no --xi), "auto" or "cross"
     std::vector<double> xi_edges;     // --xi-edges in arcminutes, required with it: at most 513
     std::string xi_mask;              // --xi-mask: a FITS image of the map's size, "" without it
@@ -122,6 +123,10 @@ struct LensingOutputs {
     Owned<slicer_shear_handle, slicer_shear_destroy> shh{};  // --shear and --raytrace
     Owned<slicer_power_handle, slicer_power_destroy> ph{};
     Owned<slicer_pcl_handle, slicer_pcl_destroy> pclh{};  // --pcl
+    // --pcl-shear: every source a field (gamma1, gamma2, kappa); the device copies of each source's gammas, made as
+    // they are written (the shear handle keeps one source's at a time)
+    Owned<slicer_pcl2_handle, slicer_pcl2_destroy> pcl2h{};
+    DeviceMaps pcl2_gamma{h};
     // --xi: the kappa maps' handle (spin 0, every source a field) and with --shear a spin-2 one of one field, run as
     // each source's shear is made; the rows of the .xipm_ table, [source][bin] of (xi+, xi-)
     Owned<slicer_xi_handle, slicer_xi_destroy> xih{}, xipmh{};
@@ -215,6 +220,7 @@ private:
     int source_shear(size_t s, const float *d_kappa);
     int power_spectra();
     int pseudo_spectra();
+    int shear_pseudo_spectra(const float *d_mask, double taper_pix, const std::string &head);
     int correlations();
     int bispectra();
     int write_table(const char *what, const char *token, const std::string &text) const;

@@ -1,5 +1,5 @@
 // slicer_fft.hpp -- internal (not exported): the f64 real-to-complex transform of npix^2 maps and its inverse
-// (slicer_fft.hip), shared by the handles of DESIGN.md S8 rows N6/N8, N7, N15, N17, N18 and N20.  One plan per map size
+// (slicer_fft.hip), shared by the handles of DESIGN.md S8 rows N6/N8, N7, N15, N17, N18, N20 and N21.  One plan per map size
 // and shear_split value: the twiddles, the row and column pass chains, and the buffers the passes go through.  Every
 // transform is enqueued on the caller's stream, and none of its arguments is one of the plan's buffers.
 #pragma once

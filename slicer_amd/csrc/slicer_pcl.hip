@@ -9,7 +9,8 @@
 //             values that are not finite; A = irfft2(|rfft2 w|^2) (slicer_fft_forward, slicer_fft_inverse_abs2); then per
 //             non-empty bin b': G = irfft2(1[F_b']) (slicer_fft_inverse_band with the DC mode kept), Q = rfft2(A G)
 //             (slicer_fft_forward_product) and column b' of M from the binning of Re Q (slicer_power_bin_real)
-//   read      the LU of the active part of M, factorised by set_mask on the host, applied to the coupled bandpowers
+//   read      the LU of the active part of M (slicer_pcl_internal.hpp), factorised by set_mask on the host, applied to the
+//             coupled bandpowers
 // No atomics: the moments are per-workgroup partials in a fixed tree, summed in workgroup order on the host.
 #include <hip/hip_runtime.h>
 
@@ -22,11 +23,12 @@
 
 #include "slicer_power_internal.hpp"
 #include "slicer_host.hpp"
+#include "slicer_pcl_internal.hpp"
 
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kMomentGroups = 256;  // workgroups of k_pcl_moments: the partials the host adds up
+constexpr int kMomentGroups = kPclMomentGroups;
 
 // w = (float)(f[i0] * f[i1]) (1 without a table), times the user mask in f32 where there is one
 __global__ __launch_bounds__(kThreads) void k_pcl_mask(const double *f, const float *user, float *w, int n)
@@ -169,64 +171,41 @@ int slicer_pcl_create(slicer_handle h, int32_t npix, double angle_deg, int32_t n
     return sub_done(rc, ph, out);
 }
 
-namespace {
-
-// LU with partial pivoting of the na x na matrix a (row-major, in place); false at a zero or non-finite pivot
-bool lu_factor(std::vector<double> &a, int na, std::vector<int> &piv)
+int pcl_build_mask(slicer_handle h, const char *who, hipStream_t st, int n, const float *d_mask, double taper_width_pix,
+                   float *d_w, double *d_f, double2 *d_partial, unsigned long long *d_bad, double *mean_w, double *mean_w2)
 {
-    piv.assign(na, 0);
-    for (int k = 0; k < na; k++) {
-        int p = k;
-        double best = -1.0;
-        for (int i = k; i < na; i++) {
-            const double v = std::fabs(a[(size_t)i * na + k]);
-            if (!std::isfinite(v))
-                return false;
-            if (v > best) {
-                best = v;
-                p = i;
-            }
-        }
-        if (!(best > 0.0))
-            return false;
-        piv[k] = p;
-        if (p != k)
-            for (int j = 0; j < na; j++)
-                std::swap(a[(size_t)k * na + j], a[(size_t)p * na + j]);
-        const double d = a[(size_t)k * na + k];
-        for (int i = k + 1; i < na; i++) {
-            const double m = a[(size_t)i * na + k] / d;
-            a[(size_t)i * na + k] = m;
-            for (int j = k + 1; j < na; j++)
-                a[(size_t)i * na + j] -= m * a[(size_t)k * na + j];
-        }
+    const size_t px = (size_t)n * n;
+    const bool taper = taper_width_pix > 0.0;
+    std::vector<double> f;
+    if (taper) {
+        f.resize(n);
+        if (int rc = slicer_pcl_taper(n, taper_width_pix, f.data()))
+            return fail(h, rc, "%s", slicer_last_error(nullptr));
+        HIPCHK(h, hipMemcpyAsync(d_f, f.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
     }
-    for (double v : a)
-        if (!std::isfinite(v))
-            return false;
-    return true;
+    const unsigned groups = (unsigned)std::min<size_t>(4096, (px + kThreads - 1) / kThreads);
+    hipLaunchKernelGGL(k_pcl_mask, dim3(groups), dim3(kThreads), 0, st, taper ? d_f : nullptr, d_mask, d_w, n);
+    HIPCHK(h, hipGetLastError());
+    hipLaunchKernelGGL(k_pcl_moments, dim3(kMomentGroups), dim3(kThreads), 0, st, d_w, px, d_partial, d_bad);
+    HIPCHK(h, hipGetLastError());
+    std::vector<double2> part(kMomentGroups);
+    std::vector<unsigned long long> bad(kMomentGroups);
+    HIPCHK(h, hipMemcpyAsync(part.data(), d_partial, kMomentGroups * sizeof(double2), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipMemcpyAsync(bad.data(), d_bad, kMomentGroups * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIPCHK(h, hipStreamSynchronize(st));  // also: f is a host temporary
+    double s1 = 0.0, s2 = 0.0;
+    unsigned long long nbad = 0;
+    for (int g = 0; g < kMomentGroups; g++) {
+        s1 += part[g].x;
+        s2 += part[g].y;
+        nbad += bad[g];
+    }
+    if (nbad)
+        return fail(h, SLICER_ERR_ARG, "%s: the mask has %llu values that are not finite", who, nbad);
+    *mean_w = s1 / (double)px;
+    *mean_w2 = s2 / (double)px;
+    return SLICER_OK;
 }
-
-// x <- (LU)^-1 P x: the row exchanges, the forward and the back substitution
-void lu_solve(const std::vector<double> &a, int na, const std::vector<int> &piv, double *x)
-{
-    for (int k = 0; k < na; k++)
-        std::swap(x[k], x[piv[k]]);
-    for (int i = 1; i < na; i++) {
-        double s = x[i];
-        for (int j = 0; j < i; j++)
-            s -= a[(size_t)i * na + j] * x[j];
-        x[i] = s;
-    }
-    for (int i = na - 1; i >= 0; i--) {
-        double s = x[i];
-        for (int j = i + 1; j < na; j++)
-            s -= a[(size_t)i * na + j] * x[j];
-        x[i] = s / a[(size_t)i * na + i];
-    }
-}
-
-}  // namespace
 
 int slicer_pcl_set_mask(slicer_pcl_handle ph, const float *d_mask, double taper_width_pix)
 {
@@ -243,35 +222,9 @@ int slicer_pcl_set_mask(slicer_pcl_handle ph, const float *d_mask, double taper_
         return rc;
     ph->has_mask = ph->ran = false;
     const int n = ph->n, B = ph->B;
-    const size_t px = (size_t)n * n;
-    std::vector<double> f;
-    if (taper) {
-        f.resize(n);
-        if (int rc = slicer_pcl_taper(n, taper_width_pix, f.data()))
-            return fail(h, rc, "%s", slicer_last_error(nullptr));
-        HIPCHK(h, hipMemcpyAsync(ph->f, f.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
-    }
-    const unsigned groups = (unsigned)std::min<size_t>(4096, (px + kThreads - 1) / kThreads);
-    hipLaunchKernelGGL(k_pcl_mask, dim3(groups), dim3(kThreads), 0, st, taper ? ph->f : nullptr, d_mask, ph->w, n);
-    HIPCHK(h, hipGetLastError());
-    hipLaunchKernelGGL(k_pcl_moments, dim3(kMomentGroups), dim3(kThreads), 0, st, ph->w, px, ph->partial, ph->bad);
-    HIPCHK(h, hipGetLastError());
-    std::vector<double2> part(kMomentGroups);
-    std::vector<unsigned long long> bad(kMomentGroups);
-    HIPCHK(h, hipMemcpyAsync(part.data(), ph->partial, kMomentGroups * sizeof(double2), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipMemcpyAsync(bad.data(), ph->bad, kMomentGroups * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIPCHK(h, hipStreamSynchronize(st));  // also: f is a host temporary
-    double s1 = 0.0, s2 = 0.0;
-    unsigned long long nbad = 0;
-    for (int g = 0; g < kMomentGroups; g++) {
-        s1 += part[g].x;
-        s2 += part[g].y;
-        nbad += bad[g];
-    }
-    if (nbad)
-        return fail(h, SLICER_ERR_ARG, "slicer_pcl_set_mask: the mask has %llu values that are not finite", nbad);
-    ph->mean_w = s1 / (double)px;
-    ph->mean_w2 = s2 / (double)px;
+    if (int rc = pcl_build_mask(h, "slicer_pcl_set_mask", st, n, d_mask, taper_width_pix, ph->w, ph->f, ph->partial,
+                                ph->bad, &ph->mean_w, &ph->mean_w2))
+        return rc;
 
     // A, then M column by column
     slicer_fft_s *plan = slicer_power_plan(ph->pw);

@@ -468,6 +468,29 @@ int slicer_power_run_masked(slicer_power_handle ph, const float *const *d_maps, 
     return SLICER_OK;
 }
 
+int slicer_power_transform_masked(slicer_power_handle ph, hipStream_t st, int s, const float *d_map, const float *d_w)
+{
+    ProfScope ps(ph->h, KN_POWER_FFT);
+    ph->ran = false;
+    return slicer_fft_forward_masked(ph->fft, st, d_map, d_w, slicer_power_stored(ph, s));
+}
+
+double2 *slicer_power_stored(slicer_power_handle ph, int s) { return ph->spec + (size_t)s * ph->n * ph->H; }
+
+int slicer_power_bin_stored(slicer_power_handle ph, hipStream_t st, double *d_copy)
+{
+    {
+        ProfScope ps(ph->h, KN_POWER_BIN);
+        if (int rc = bin_launch(ph, st, 0))
+            return rc;
+    }
+    if (d_copy)
+        HIPCHK(ph->h, hipMemcpyAsync(d_copy, ph->cl, (size_t)ph->npairs * ph->B * sizeof(double),
+                                     hipMemcpyDeviceToDevice, st));
+    ph->ran = true;
+    return SLICER_OK;
+}
+
 int slicer_power_spectrum(slicer_power_handle ph, int32_t map, double *host)
 {
     if (!ph || !host)

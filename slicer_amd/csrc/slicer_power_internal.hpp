@@ -1,5 +1,5 @@
 // slicer_power_internal.hpp -- internal (not exported): what slicer_power.hip shares with the handles built on its
-// bins: pseudo-C_l (slicer_pcl.hip), bispectrum (slicer_bispectrum.hip) and xi (slicer_xi.hip).
+// bins: pseudo-C_l (slicer_pcl.hip, slicer_pcl_shear.hip), bispectrum (slicer_bispectrum.hip) and xi (slicer_xi.hip).
 #pragma once
 
 #include <algorithm>
@@ -11,6 +11,16 @@
 // slicer_power_run with the maps multiplied by the f32 mask d_w on their way in (slicer_fft_forward_masked).
 SLICER_FFT_INTERNAL int slicer_power_run_masked(slicer_power_handle ph, const float *const *d_maps, const float *d_w);
 SLICER_FFT_INTERNAL slicer_fft_s *slicer_power_plan(slicer_power_handle ph);
+// slicer_power_run_masked of a cross handle in its two halves, for a caller that changes the stored spectra in between
+// (the E/B rotation of slicer_pcl_shear.hip); all enqueued on st.  slicer_power_transform_masked: the spectrum of map
+// `s` = rfft2(d_w * d_map), and the handle has no run until the next slicer_power_bin_stored.  slicer_power_stored:
+// where that spectrum lies, [n][n/2+1].  slicer_power_bin_stored: the binning and finish of slicer_power_run over
+// the n_maps stored spectra, after which slicer_power_read and slicer_power_spectrum serve them; d_copy (or NULL)
+// receives the [pairs][B] bandpowers as well.
+SLICER_FFT_INTERNAL int slicer_power_transform_masked(slicer_power_handle ph, hipStream_t st, int s, const float *d_map,
+                                                      const float *d_w);
+SLICER_FFT_INTERNAL double2 *slicer_power_stored(slicer_power_handle ph, int s);
+SLICER_FFT_INTERNAL int slicer_power_bin_stored(slicer_power_handle ph, hipStream_t st, double *d_copy);
 // d_out[column * B + b] = norm / N_b * (sum of Re spec over the half-plane modes of bin b), NaN for an empty bin: the
 // binning of slicer_power_run (same slices, same summation order) of the real parts; enqueued on st.
 SLICER_FFT_INTERNAL int slicer_power_bin_real(slicer_power_handle ph, hipStream_t st, const double2 *spec, double norm,

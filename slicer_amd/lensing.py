@@ -8,7 +8,8 @@ excursion sets as exact counts (row N14), and the binned bispectra of such maps 
 such maps with the binned absolute sums of its scales, the starlet l1-norm (row N16), and the masked pseudo-C_l of such
 maps: coupled bandpowers, the mask's mode-coupling matrix and the decoupled bandpowers (row N17), and the real-space
 two-point correlation functions xi_kk, xi+ and xi- of such maps and of shear maps (row N18), and the Betti numbers of
-such maps' excursion sets as exact counts (row N19), and the wavelet scattering coefficients of such maps (row N20).
+such maps' excursion sets as exact counts (row N19), and the wavelet scattering coefficients of such maps (row N20), and
+the E/B pseudo-C_l of masked shear maps: the spin-2 coupling matrices of the mask and the block decoupling (row N21).
 
 plane_weights wraps the host weights of include/slicer_amd.h (slicer_lensing_weights); Kappa is the device accumulator
 (slicer_kappa_*) bound to a Slicer handle: it reads the finalized plane maps where they are, in HBM.  Shear (slicer_shear_*)
@@ -28,7 +29,9 @@ with the coupling matrix of the mask and the bandpowers decoupled by it; Xi (sli
 zero-padded maps over annuli of the lag, divided by the pair weights of one shared weight map; Betti (slicer_betti_*)
 counts the 8-connected components of the sets x >= t_j and the holes in them by a union-find on the device; Scattering
 (slicer_scattering_*) averages the moduli of a map's Morlet wavelet transforms, and of those moduli's transforms at
-coarser scales.
+coarser scales; PclShear (slicer_pcl2_*) is Pcl for fields of (gamma1, gamma2) and optionally kappa: it rotates the
+masked spectra to E and B, bins EE, EB, BB and the kappa crosses, and undoes the mask's mixing of E and B with the
+spin-0, spin-2 and spin-4 coupling matrices; spin_phases gives the rotation's tables.
 """
 import ctypes as C
 import math
@@ -992,6 +995,125 @@ class Pcl(_SubHandle):
             return out
         return {"ell_lo": self.edges[:-1] * self.ell_f, "ell_hi": self.edges[1:] * self.ell_f, "ell": ell,
                 "counts": counts, "cl": square(flat), "coupled": square(cflat)}
+
+
+PCL2_MAX_BINS = 128
+PCL2_E, PCL2_B, PCL2_KAPPA = 0, 1, 2
+
+
+def spin_phases(npix, spin):
+    """(C, S), each f64 [npix, npix // 2 + 1]: cos and sin of spin (2 or 4) times the mode's polar angle as
+    slicer_pcl2_phases makes them (the sines 0 on the Nyquist lines of an even npix); host only, no device needed."""
+    n = max(int(npix), 0)
+    c, s = np.zeros((n, n // 2 + 1), np.float64), np.zeros((n, n // 2 + 1), np.float64)
+    _host_chk(_L.slicer_pcl2_phases(int(npix), int(spin), c.ctypes.data, s.ctypes.data))
+    return c, s
+
+
+class PclShear(_SubHandle):
+    """E/B pseudo-C_l of n_fields masked shear fields (gamma1, gamma2; with_kappa: and kappa) of npix^2 pixels and side
+    angle_deg degrees under one shared mask, on the device of `slicer`, on its stream: the
+    coupled bandpowers of E, B and kappa, the coupling matrices M0, M2, X2, M4, X4 of the mask and the bandpowers
+    decoupled by their block systems.  cross: all pairs of fields, else the pairs within each field.  The edges
+    (required; units of l_f, or ell_edges in multipoles) as for Pcl, at most 128 bins."""
+    _handle, _destroy = "_ph", "slicer_pcl2_destroy"
+
+    def __init__(self, slicer: Slicer, npix, angle_deg, n_fields, with_kappa=False, cross=False, edges=None,
+                 ell_edges=None):
+        self._s = slicer
+        self.npix, self.angle_deg, self.n_fields = int(npix), float(angle_deg), int(n_fields)
+        self.with_kappa, self.cross = bool(with_kappa), bool(cross)
+        self.n_comp = 3 if self.with_kappa else 2  # per field
+        ok = math.isfinite(self.angle_deg) and self.angle_deg > 0  # otherwise slicer_pcl2_create refuses it
+        self.ell_f = ell_fundamental(self.angle_deg) if ok else math.nan
+        if edges is None and ell_edges is None:
+            raise ValueError("PclShear needs edges or ell_edges")
+        n_edges, e = _edges(self.npix, edges, ell_edges, self.angle_deg)
+        self.edges = e.copy()
+        self.n_bins = n_edges - 1
+        ph = C.c_void_p()
+        slicer._chk(_L.slicer_pcl2_create(slicer._h, self.npix, self.angle_deg, self.n_fields, int(self.with_kappa),
+                                          int(self.cross), n_edges, _dptr(e), C.byref(ph)))
+        self._ph = ph
+
+    def set_mask(self, d_mask=None, taper_pix=0.0):
+        """As Pcl.set_mask; builds the five coupling matrices and the three block systems; waits for the stream."""
+        self._s._chk(_L.slicer_pcl2_set_mask(self._ph, None if d_mask is None else int(d_mask), float(taper_pix)))
+
+    def mask(self):
+        """The mask in use, f32 [npix, npix]."""
+        out = np.empty((self.npix, self.npix), np.float32)
+        self._s._chk(_L.slicer_pcl2_read_mask(self._ph, out.ctypes.data))
+        return out
+
+    def coupling(self):
+        """dict: M0, M2, X2, M4, X4, each [B, B] (rows and columns of empty bins are 0), mean_w, mean_w2."""
+        B = max(self.n_bins, 0)
+        m = {k: np.empty((B, B), np.float64) for k in ("M0", "M2", "X2", "M4", "X4")}
+        m1, m2 = C.c_double(), C.c_double()
+        self._s._chk(_L.slicer_pcl2_coupling(self._ph, *(a.ctypes.data for a in m.values()), C.byref(m1), C.byref(m2)))
+        m.update(mean_w=m1.value, mean_w2=m2.value)
+        return m
+
+    def run(self, ptrs):
+        """ptrs: device addresses of the f32 npix^2 maps, per field gamma1, gamma2 and, with kappa, kappa (unmasked)."""
+        ptrs = [int(p) for p in ptrs]
+        if len(ptrs) != self.n_fields * self.n_comp:
+            raise ValueError(f"expected {self.n_fields * self.n_comp} maps, got {len(ptrs)}")
+        arr = (C.c_void_p * len(ptrs))(*ptrs)
+        self._s._chk(_L.slicer_pcl2_run(self._ph, arr))
+
+    def run_shear(self, shears, kappas=None):
+        """The gamma1, gamma2 device maps of the last run of every Shear handle in `shears`, where they are; kappas:
+        with kappa, the device address of each field's kappa map."""
+        ptrs = []
+        for f, sh in enumerate(shears):
+            ptrs += [sh.device_map(SHEAR_GAMMA1), sh.device_map(SHEAR_GAMMA2)]
+            if self.with_kappa:
+                ptrs.append(kappas[f])
+        self.run(ptrs)
+
+    def spectrum(self, field, comp):
+        """The spectrum of component comp (0, 1, 2 = E, B, kappa) of field `field` of the last run,
+        [npix, npix // 2 + 1] complex128 (auto mode: the last field only)."""
+        out = np.empty((self.npix, self.npix // 2 + 1), np.complex128)
+        self._s._chk(_L.slicer_pcl2_spectrum(self._ph, int(field), int(comp), out.ctypes.data))
+        return out
+
+    def read(self):
+        """dict: ell_lo, ell_hi, ell (mean l), counts, and `cl` (decoupled; NaN in empty bins) and `coupled`, each a
+        dict of named arrays EE, EB, BE, BB and, with kappa, kE, kB, Ek, Bk, kk: XY[f][g][B] is component X of field f
+        against component Y of field g (cross), or XY[f][B] within field f (auto)."""
+        F, B, nc = self.n_fields, self.n_bins, self.n_comp
+        S = F * nc
+        npairs = S * (S + 1) // 2 if self.cross else F * (nc * (nc + 1) // 2)
+        flat, cflat = np.empty((npairs, B), np.float64), np.empty((npairs, B), np.float64)
+        ell = np.empty(B, np.float64)
+        counts = np.empty(B, np.int64)
+        self._s._chk(_L.slicer_pcl2_read(self._ph, flat.ctypes.data, cflat.ctypes.data, ell.ctypes.data,
+                                         counts.ctypes.data))
+
+        def pair(i, j, n):
+            i, j = min(i, j), max(i, j)
+            return i * n - i * (i - 1) // 2 + (j - i)
+
+        def named(x):
+            out = {}
+            for a, la in enumerate("EBk"[:nc]):
+                for b, lb in enumerate("EBk"[:nc]):
+                    if self.cross:
+                        v = np.empty((F, F, B), np.float64)
+                        for f in range(F):
+                            for g in range(F):
+                                v[f, g] = x[pair(f * nc + a, g * nc + b, S)]
+                    else:
+                        v = np.empty((F, B), np.float64)
+                        for f in range(F):
+                            v[f] = x[f * (nc * (nc + 1) // 2) + pair(a, b, nc)]
+                    out[la + lb] = v
+            return out
+        return {"ell_lo": self.edges[:-1] * self.ell_f, "ell_hi": self.edges[1:] * self.ell_f, "ell": ell,
+                "counts": counts, "cl": named(flat), "coupled": named(cflat)}
 
 
 XI_MAX_BINS = 512
