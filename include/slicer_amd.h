@@ -1222,6 +1222,82 @@ int slicer_scattering_modulus(slicer_scattering_handle sh, const float *d_map, i
                               int32_t l2, double *host);
 int slicer_scattering_destroy(slicer_scattering_handle sh);
 
+/* ---- Catalogue of a map's peaks and minima: positions, heights, sub-pixel offsets ----
+ * Input: any device f32 map of npix^2 pixels (row-major), only read, 1 <= npix <= SLICER_CATALOGUE_MAX_NPIX.
+ * Candidates and definition are those of slicer_peaks_* (row N10): the pixels (i, j) with 1 <= i, j <= npix-2; a peak is
+ * strictly greater, in f32, than each of its 8 neighbours, a minimum strictly less; ties give neither, every comparison
+ * with a NaN is false, nothing wraps.
+ * Selection, given with every run: `kinds` is a bitmask, SLICER_CATALOGUE_PEAKS | SLICER_CATALOGUE_MINIMA; a peak is kept
+ * iff (double)x >= min_peak, a minimum iff (double)x <= max_minimum, compared in f64 against the f64 thresholds;
+ * -inf / +inf keep every one.
+ * Record: slicer_catalogue_record, 32 bytes: row, col; value, the pixel itself; flags, bit 0 (SLICER_CATALOGUE_MINIMUM)
+ * set for a minimum, bit 1 (SLICER_CATALOGUE_FALLBACK) where the refinement was not accepted; dy, dx, the offset of the
+ * extremum from the pixel's centre along the rows and along the columns, in pixels.
+ * Order: ascending row * npix + col, peaks and minima interleaved in that one order.  The order and every byte of every
+ * record depend on the map and the selection alone: not on the launch shape, the number of compute units or the
+ * alignment of the map, and they are the same on every run.
+ * Refinement: the least-squares quadratic of the 3 x 3 window z[a][b], a the row offset and b the column offset, each in
+ * {-1, 0, 1}.  Every value is widened exactly to f64; every operation is rounded once, none is fused, in this order:
+ *   R(a) = (z[a][-1] + z[a][0]) + z[a][1],  C(b) = (z[-1][b] + z[0][b]) + z[1][b]
+ *   gy = (R(1) - R(-1)) / 6,  gx = (C(1) - C(-1)) / 6
+ *   hyy = ((R(1) + R(-1)) - 2 R(0)) / 3,  hxx = ((C(1) + C(-1)) - 2 C(0)) / 3
+ *   hxy = ((z[1][1] + z[-1][-1]) - (z[1][-1] + z[-1][1])) / 4
+ *   det = hyy hxx - hxy hxy
+ *   dy = -((hxx gy - hxy gx) / det),  dx = -((hyy gx - hxy gy) / det)
+ * The offsets are accepted iff det > 0, hyy < 0 for a peak (hyy > 0 for a minimum), dy and dx are finite, |dy| <= 0.5
+ * and |dx| <= 0.5.  Otherwise dy = dx = +0.0 and SLICER_CATALOGUE_FALLBACK is set; a window with an infinite value ends
+ * there.
+ * Capacity: a handle holds `capacity` records, 1 <= capacity <= SLICER_CATALOGUE_MAX_CAPACITY = 2^29 (no two peaks and
+ * no two minima are adjacent: at most npix^2 / 2 records, 2^29 at the largest npix).  A run always gives the exact
+ * totals of the kept peaks and the kept minima and stores the first min(total, capacity) records of the order above;
+ * an overflow is no error -- the counts show it -- and nothing behind `capacity` records is ever written.
+ * No atomics and no waiting between workgroups; every count and total is rewritten by every run.
+ * Out of scope: stacked profiles and sampling of companion maps at the records, sorting by height or a top-K on the
+ * device, plateaux, periodic maps, the curved sky, FITS binary tables, npix above 32768.
+ *   slicer_catalogue_create    on the device and stream of h (h's current one: slicer_set_stream, destroy it before h).
+ *                              d_records: NULL, and the handle allocates its records, or a device buffer of the caller's
+ *                              for `capacity` records, which must outlive the handle.  Checked before the handle, in this
+ *                              order, so that they can be checked without a device: npix < 1: SLICER_ERR_ARG; npix >
+ *                              SLICER_CATALOGUE_MAX_NPIX: SLICER_ERR_UNSUPPORTED; a capacity outside 1 ... 2^29, records
+ *                              off the 16-byte grid, then a NULL h or out: SLICER_ERR_ARG.  Device memory: 32 bytes per
+ *                              record of the capacity (unless they are the caller's), 4 bytes per segment of 64 columns of
+ *                              a row -- 4 npix ceil(npix / 64) bytes: 1 MiB at 4096^2, 64 MiB at 32768^2 -- 12 bytes per 4096
+ *                              segments and 24 bytes of totals (SLICER_ERR_NOMEM)
+ *   slicer_catalogue_run       any device f32 map of the handle's npix^2 pixels (e.g. slicer_kappa_device_map); enqueued,
+ *                              no synchronisation.  Checked in this order, the first two before the handle: kinds outside
+ *                              1 ... 3, a NaN threshold, a NULL handle or map: SLICER_ERR_ARG
+ *   slicer_catalogue_run_npix  the same of a smaller map of npix^2 pixels, 1 <= npix <= the handle's (others:
+ *                              SLICER_ERR_ARG, after the checks above), so that one handle serves every level of a
+ *                              moments pyramid (slicer_moments_device_map)
+ *   slicer_catalogue_count     the kept peaks, the kept minima and the stored records of the last run (any of them NULL);
+ *                              waits for the stream.  Before any run: SLICER_ERR_STATE
+ *   slicer_catalogue_read      the first min(stored, max_records) records into host memory, *copied (may be NULL) their
+ *                              number; waits for the stream.  Before any run: SLICER_ERR_STATE
+ *   slicer_catalogue_device    where the last run left its results on the device: the records, and three int64 {peaks,
+ *                              minima, stored}; ordered after the run on the handle's stream, valid until the next run or
+ *                              the destroy.  Before any run: SLICER_ERR_STATE */
+typedef struct slicer_catalogue *slicer_catalogue_handle;
+#define SLICER_CATALOGUE_MAX_NPIX 32768
+#define SLICER_CATALOGUE_MAX_CAPACITY 536870912 /* 2^29 */
+#define SLICER_CATALOGUE_PEAKS 1    /* kinds */
+#define SLICER_CATALOGUE_MINIMA 2
+#define SLICER_CATALOGUE_MINIMUM 1u  /* flags */
+#define SLICER_CATALOGUE_FALLBACK 2u
+typedef struct {
+    int32_t row, col;
+    float value;
+    uint32_t flags;
+    double dy, dx;
+} slicer_catalogue_record;
+int slicer_catalogue_create(slicer_handle h, int32_t npix, int64_t capacity, void *d_records, slicer_catalogue_handle *out);
+int slicer_catalogue_run(slicer_catalogue_handle ch, const float *d_map, int32_t kinds, double min_peak, double max_minimum);
+int slicer_catalogue_run_npix(slicer_catalogue_handle ch, const float *d_map, int32_t kinds, double min_peak,
+                              double max_minimum, int32_t npix);
+int slicer_catalogue_count(slicer_catalogue_handle ch, int64_t *n_peaks, int64_t *n_minima, int64_t *stored);
+int slicer_catalogue_read(slicer_catalogue_handle ch, slicer_catalogue_record *records, int64_t max_records, int64_t *copied);
+int slicer_catalogue_device(slicer_catalogue_handle ch, slicer_catalogue_record **d_records, int64_t **d_counts);
+int slicer_catalogue_destroy(slicer_catalogue_handle ch);
+
 /* per-kernel HIP-event timing (off by default; adds two event records per launch) */
 int slicer_profile_enable(slicer_handle h, int on);
 int slicer_profile_reset(slicer_handle h);

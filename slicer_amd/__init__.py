@@ -21,6 +21,8 @@ from .lensing import STARLET_MAX_SCALES, L1Norm, Starlet, starlet_gains  # noqa:
 from .lensing import PCL_MAX_BINS, Pcl, pcl_taper  # noqa: F401
 from .lensing import PCL2_B, PCL2_E, PCL2_KAPPA, PCL2_MAX_BINS, PclShear, spin_phases  # noqa: F401
 from .lensing import BETTI_MAX_NPIX, BETTI_MAX_THRESHOLDS, Betti  # noqa: F401
+from .lensing import (CATALOGUE_DTYPE, CATALOGUE_FALLBACK, CATALOGUE_MAX_CAPACITY, CATALOGUE_MAX_NPIX,  # noqa: F401
+                      CATALOGUE_MINIMA, CATALOGUE_MINIMUM, CATALOGUE_PEAKS, PeakCatalogue)
 from .lensing import SCATTERING_MAX_J, SCATTERING_MAX_L, Scattering, scattering_filter, scattering_reduce  # noqa: F401
 from .lensing import XI_CROSS, XI_MAX_BINS, XI_MINUS, XI_PLUS, XI_WEIGHTS, Xi, xi_bins  # noqa: F401
 from .lensing import (RAYS_COUNT, RAYS_DEFLECTION1, RAYS_DEFLECTION2, RAYS_GAMMA1, RAYS_GAMMA2, RAYS_KAPPA,  # noqa: F401

@@ -33,6 +33,12 @@ class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("launches", C.c_uint64), ("total_ms", C.c_double)]
 
 
+class CatalogueRecord(C.Structure):
+    """slicer_catalogue_record: one peak or minimum of a PeakCatalogue."""
+    _fields_ = [("row", C.c_int32), ("col", C.c_int32), ("value", C.c_float), ("flags", C.c_uint32),
+                ("dy", C.c_double), ("dx", C.c_double)]
+
+
 # every symbol include/slicer_amd.h declares: (restype, argtypes)
 _H = C.c_void_p
 SYMBOLS = {
@@ -129,6 +135,13 @@ SYMBOLS = {
     "slicer_betti_run_npix": (C.c_int, [_H, C.c_void_p, C.c_int32]),
     "slicer_betti_read": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "slicer_betti_destroy": (C.c_int, [_H]),
+    "slicer_catalogue_create": (C.c_int, [_H, C.c_int32, C.c_int64, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "slicer_catalogue_run": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_double, C.c_double]),
+    "slicer_catalogue_run_npix": (C.c_int, [_H, C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_int32]),
+    "slicer_catalogue_count": (C.c_int, [_H, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "slicer_catalogue_read": (C.c_int, [_H, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)]),
+    "slicer_catalogue_device": (C.c_int, [_H, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "slicer_catalogue_destroy": (C.c_int, [_H]),
     "slicer_scattering_filter": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "slicer_scattering_create": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     "slicer_scattering_run": (C.c_int, [_H, C.c_void_p]),

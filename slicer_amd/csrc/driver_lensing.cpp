@@ -96,7 +96,21 @@
 //     s2, the mean of ||kappa * psi_{j1 l1}| * psi_{j2 l2}| (power: nan); an index a row does not have is -1.  With
 //     --shape-noise also .noisy_scattering_ of every noisy realisation (a leading column `real`).  Not for the pyramid
 //     levels or the smoothed maps: the transform has its own scales.  npix must be a size the f64 transform takes;
-//     refused for physical runs.  The scattering tables are the last files of a run.
+//     refused for physical runs.  The scattering tables are the last files of a run without --catalogue (DESIGN.md S8
+//     row N20).
+//   * --catalogue min_peak[,capacity]: <directory><simulation>.catalogue_<npix>_<suffix>.txt, the peaks of every kappa
+//     map (strictly above all 8 neighbours, as --peaks counts them) whose value is >= min_peak (-inf: all of them), in
+//     ascending row * npix + col, at most `capacity` (1 ... 2^29; 1048576 where it is not given) of a map: '#' lines
+//     (npix, angle, min_peak, capacity, the column names), then per map a line '# map z [real] [scale] n_peaks stored'
+//     with the exact number of such peaks and the number listed, and one row per listed peak:
+//     z [real] [scale] row col value dy dx off_row_deg off_col_deg flags (%.17g): (dy, dx) the sub-pixel offset of a
+//     quadratic fit to the 3 x 3 window, (0, 0) and flags = 2 where it was not accepted; off_row_deg =
+//     (((row + dy) + 0.5) / npix - 0.5) angle_deg, the angle from the field's centre, and likewise along the columns.
+//     A map with more peaks than the capacity is announced on stderr and in a '# overflow' line; the run goes on.  With
+//     --smooth and --shape-noise also .smooth_catalogue_, .noisy_catalogue_ and .noisy_smooth_catalogue_ (columns
+//     `scale`, `real`, `real scale` after z), the maps of which --peaks writes its tables; not for pyramid levels.
+//     Refused for physical runs and for npix above 32768.  The catalogue tables are the last files of a run (DESIGN.md
+//     S8 row N22).
 #include "driver_lensing.hpp"
 
 #include <algorithm>
@@ -310,6 +324,17 @@ int LensingOptions::parse(int argc, char **argv, int &i)
                        ", and of orientations, 1 ... " + std::to_string(SLICER_SCATTERING_MAX_L) + ")");
         scattering_J = (int)J;
         scattering_L = (int)L;
+    } else if (a == "--catalogue") {
+        const vector<string> tok = has_value ? split(argv[++i]) : vector<string>{};
+        char *end = nullptr;
+        const bool shaped = (tok.size() == 1 || tok.size() == 2) && whole_double(tok[0], &catalogue_min_peak) &&
+                            !std::isnan(catalogue_min_peak) && (tok.size() == 1 || (!tok[1].empty() && !isspace((unsigned char)tok[1][0])));
+        const long long capacity = shaped && tok.size() == 2 ? strtoll(tok[1].c_str(), &end, 10) : catalogue_capacity;
+        if (!shaped || (end && *end != '\0') || capacity < 1 || capacity > SLICER_CATALOGUE_MAX_CAPACITY)
+            return bad("bad --catalogue (min_peak[,capacity]: the lowest peak to list, -inf for all of them, and the most "
+                       "records of a map, 1 ... " + std::to_string(SLICER_CATALOGUE_MAX_CAPACITY) + ")");
+        catalogue_capacity = capacity;
+        catalogue = true;
     } else
         return -1;
     return 0;
@@ -356,6 +381,7 @@ int LensingOptions::check() const
         {shape_noise && no_kappa, "--shape-noise needs --kappa (the noise is added to the kappa maps)"},
         {starlet_scales > 0 && no_kappa, "--starlet needs --kappa (the transform is that of the kappa maps)"},
         {scattering_J > 0 && no_kappa, "--scattering needs --kappa (the coefficients are those of the kappa maps)"},
+        {catalogue && no_kappa, "--catalogue needs --kappa (the peaks are those of the kappa maps)"},
     };
     for (const auto &[broken, message] : rules)
         if (broken)
@@ -444,6 +470,10 @@ int LensingOptions::check_npix(const InputParams &p) const
         return bad("--scattering: " + npix + fft_sizes);
     if (scattering_J > 0 && (1L << scattering_J) > p.npix)
         return bad("--scattering: 2^J = " + std::to_string(1L << scattering_J) + " is above " + npix);
+    if (catalogue && p.physical)
+        return bad("--catalogue: the offsets are angles, and the maps of a physical run have none");
+    if (catalogue && p.npix > SLICER_CATALOGUE_MAX_NPIX)
+        return bad("--catalogue: " + npix + " is above " + std::to_string(SLICER_CATALOGUE_MAX_NPIX));
     double sigma_pix = 0.0;
     if (shape_noise && slicer_noise_sigma_pix(noise_sigma_e, noise_ngal, p.fov, p.npix, &sigma_pix) != SLICER_OK)
         return bad("--shape-noise: " + npix + ": " + slicer_last_error(nullptr));
@@ -558,6 +588,8 @@ int LensingOutputs::create()
     if (!o.betti_thresholds.empty() &&
         slicer_betti_create(h, p.npix, (int)o.betti_thresholds.size(), o.betti_thresholds.data(), bth.out()) != SLICER_OK)
         return fail(h, "slicer_amd: --betti");
+    if (o.catalogue && slicer_catalogue_create(h, p.npix, o.catalogue_capacity, nullptr, cth.out()) != SLICER_OK)
+        return fail(h, "slicer_amd: --catalogue");
     if (!o.bispectrum.empty()) {
         const int B = (int)o.bispectrum_edges.size() - 1;
         for (int i = 0; i < B; i++)
@@ -795,6 +827,49 @@ int LensingOutputs::write()
         if (write_table((string("scattering coefficients") + kind[noisy ? NOISY : KAPPA][0]).c_str(),
                         (string(kind[noisy ? NOISY : KAPPA][1]) + "scattering_").c_str(), scattering_tables[noisy]))
             return 1;
+    // ... and the catalogues last
+    for (int k = 0; k < N_KINDS; k++)
+        if (cth && has_kind[k] &&
+            write_table((string("peak catalogues") + kind[k][0]).c_str(), (string(kind[k][1]) + "catalogue_").c_str(),
+                        catalogue_tables[k]))
+            return 1;
+    return 0;
+}
+
+// The catalogue table: '#' lines (npix, angle, min_peak, capacity, `head`, the column names), then per map a '# map' line
+// with its totals -- and a '# overflow' line where the capacity did not hold them -- and one row per stored record.
+int LensingOutputs::source_catalogue(size_t s, const float *d_map, string &text, const string &head, const string &lead_names,
+                                     const string &lead)
+{
+    const char *who = "slicer_amd: --catalogue";
+    if (text.empty()) {
+        add(text, "# npix %d\n# angle_deg %.17g\n# min_peak %.17g\n# capacity %lld\n", p.npix, p.fov, o.catalogue_min_peak,
+            (long long)o.catalogue_capacity);
+        text += head + "# z " + lead_names + "row col value dy dx off_row_deg off_col_deg flags\n";
+    }
+    int64_t n_peaks = 0, stored = 0, copied = 0;
+    if (slicer_catalogue_run(cth, d_map, SLICER_CATALOGUE_PEAKS, o.catalogue_min_peak, INFINITY) != SLICER_OK ||
+        slicer_catalogue_count(cth, &n_peaks, nullptr, &stored) != SLICER_OK)
+        return fail(h, who);
+    catalogue_records.resize((size_t)stored);
+    if (slicer_catalogue_read(cth, catalogue_records.data(), stored, &copied) != SLICER_OK || copied != stored)
+        return fail(h, who);
+    string z;
+    add(z, "%.17g ", plan.zs[s]);
+    text += "# map " + z + lead;
+    add(text, "n_peaks %lld stored %lld\n", (long long)n_peaks, (long long)stored);
+    if (n_peaks > stored) {
+        cerr << who << ": the map z " << lead_names << "= " << z << lead << "has " << n_peaks << " peaks, above the capacity: the first "
+             << stored << " are listed" << endl;
+        text += "# overflow " + z + lead;
+        add(text, "%lld peaks are not listed\n", (long long)(n_peaks - stored));
+    }
+    const auto degrees = [&](int32_t pixel, double offset) { return ((((double)pixel + offset) + 0.5) / (double)p.npix - 0.5) * p.fov; };
+    for (const slicer_catalogue_record &r : catalogue_records) {
+        text += z + lead;
+        add(text, "%d %d %.17g %.17g %.17g %.17g %.17g %u\n", (int)r.row, (int)r.col, (double)r.value, r.dy, r.dx,
+            degrees(r.row, r.dy), degrees(r.col, r.dx), (unsigned)r.flags);
+    }
     return 0;
 }
 
@@ -1001,7 +1076,9 @@ int LensingOutputs::map_statistics(size_t s, float *d_map, MapKind kind, const s
         return rc;
     if (const int rc = mkh ? source_minkowski(s, d_map, tables[MINKOWSKI][kind], head, lead_names, lead) : 0)
         return rc;
-    return bth ? source_betti(s, d_map, tables[BETTI][kind], head, lead_names, lead) : 0;
+    if (const int rc = bth ? source_betti(s, d_map, tables[BETTI][kind], head, lead_names, lead) : 0)
+        return rc;
+    return cth ? source_catalogue(s, d_map, catalogue_tables[kind], head, lead_names, lead) : 0;
 }
 
 void LensingOutputs::counts_head(string &text, const char *name, const vector<double> &values, const string &head,

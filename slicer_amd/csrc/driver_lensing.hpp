@@ -1,6 +1,6 @@
 // driver_lensing.hpp -- the lensing outputs of the SLICER_amd driver (slicer_main.cpp): their options, their host
 // planning and the device-0 work behind --kappa, --shear, --deflection, --raytrace, --power, --pcl, --pcl-shear, --xi, --moments, --peaks,
-// --minkowski, --betti, --bispectrum, --smooth, --shape-noise, --starlet and --scattering (driver_lensing.cpp describes the options), with the small helpers the rest of the driver shares with them.
+// --minkowski, --betti, --bispectrum, --smooth, --shape-noise, --starlet, --scattering and --catalogue (driver_lensing.cpp describes the options), with the small helpers the rest of the driver shares with them.
 #pragma once
 #include <deque>
 #include <string>
@@ -45,6 +45,9 @@ struct LensingOptions {
     int starlet_scales = 0;              // --starlet J:lo,hi,bins: J, 0 without it
     std::vector<double> starlet_edges;   // ... the bins + 1 uniform edges from lo to hi
     int scattering_J = 0, scattering_L = 0;  // --scattering J,L: the scales and the orientations, 0 without it
+    bool catalogue = false;                  // --catalogue min_peak[,capacity]
+    double catalogue_min_peak = 0.0;
+    int64_t catalogue_capacity = 1 << 20;    // records a map: 32 MiB on the device
 
     bool gradient() const { return shear_derivative == "gradient"; }
     int n_power_edges(int npix) const { return power_edges.empty() ? npix : (int)power_edges.size(); }
@@ -158,6 +161,9 @@ struct LensingOutputs {
     // --scattering: one handle for all sources; the tables of the kappa and of the noisy maps
     Owned<slicer_scattering_handle, slicer_scattering_destroy> sch{};
     std::string scattering_tables[2]{};
+    // --catalogue: one handle for every map, the host copy of a map's records, the table of every kind of map
+    Owned<slicer_catalogue_handle, slicer_catalogue_destroy> cth{};
+    std::vector<slicer_catalogue_record> catalogue_records{};
     // --raytrace: a one-source kappa handle that makes a plane's lens map, the rays, their six output buffers, and the
     // sources in ascending redshift with the position of the next one to observe
     Owned<slicer_kappa_handle, slicer_kappa_destroy> lkh{};
@@ -173,6 +179,7 @@ struct LensingOutputs {
     enum Statistic { MOMENTS, PEAKS, MINKOWSKI, BETTI, N_STATISTICS };
     enum MapKind { KAPPA, SMOOTH, NOISY, NOISY_SMOOTH, N_KINDS };
     std::string tables[N_STATISTICS][N_KINDS]{};
+    std::string catalogue_tables[N_KINDS]{};
 
     int create();
     // The planes i0 .. i1-1 of one pass go into the kappa maps as ONE batch whether they were deposited now (their
@@ -197,8 +204,11 @@ private:
                          const std::string &lead);
     int source_betti(size_t s, float *d_map, std::string &text, const std::string &head, const std::string &lead_names,
                      const std::string &lead);
+    // --catalogue: the peaks of the map itself (no pyramid levels), z in front of `lead`
+    int source_catalogue(size_t s, const float *d_map, std::string &text, const std::string &head,
+                         const std::string &lead_names, const std::string &lead);
     // ... of every statistic that is on, into its table of this kind of map: moments, then peaks, Minkowski, Betti (the
-    // last three read the pyramid that the moments of the same map left behind)
+    // last three read the pyramid that the moments of the same map left behind), then the catalogue
     int map_statistics(size_t s, float *d_map, MapKind kind, const std::string &head = "", const std::string &lead_names = "",
                        const std::string &lead = "");
     // The '#' lines of a --peaks / --minkowski / --betti table while `text` is empty: npix, angle, levels, `name` and the values,

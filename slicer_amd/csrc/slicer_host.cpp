@@ -1,5 +1,5 @@
 // slicer_host.cpp -- what every file under the C ABI shares (slicer_host.hpp): the error text, grow-only device
-// buffers, the per-kernel profile, and the helpers of the sub-handles (kappa, shear, FFT plan, power, moments, peaks, rays, smooth, noise, minkowski, bispectrum, starlet, l1norm, betti, scattering).
+// buffers, the per-kernel profile, and the helpers of the sub-handles (kappa, shear, FFT plan, power, moments, peaks, rays, smooth, noise, minkowski, bispectrum, starlet, l1norm, betti, scattering, catalogue).
 #include "slicer_host.hpp"
 
 #include <cstdarg>

@@ -1,6 +1,6 @@
 // slicer_host.hpp -- internal (not installed, not exported): the host layer under the C ABI of include/slicer_amd.h.
 // The handle, its error and profiling plumbing, what the sub-handles (kappa, shear, FFT plan, power, moments, peaks,
-// rays, smooth, noise, minkowski, bispectrum, starlet, l1norm, pcl, pcl2, xi, betti, scattering) share, and the functions that cross the
+// rays, smooth, noise, minkowski, bispectrum, starlet, l1norm, pcl, pcl2, xi, betti, scattering, catalogue) share, and the functions that cross the
 // files of the core pass:
 //   slicer_host.cpp    errors, grow-only buffers, profiling, the sub-handle helpers: SubHandle (the base of every
 //                      sub-handle struct) with sub_new / sub_done for its *_create, sub_stream for its launches, sub_read

@@ -10,7 +10,7 @@
 //     over the snapshot (the reference re-reads and re-transforms it for each of them);   --single-plane disables
 //   * nparttype* keys carry the real selected counts (the reference writes 0: densitymaps.cpp:497), which also makes
 //     partinplanes runs write their per-type files;                                      --reference-counts disables
-//   * --kappa with --shear, --deflection, --shear-derivative, --raytrace, --power, --pcl, --pcl-shear, --xi, --moments, --peaks, --minkowski, --betti, --bispectrum, --smooth, --shape-noise, --starlet and --scattering adds the
+//   * --kappa with --shear, --deflection, --shear-derivative, --raytrace, --power, --pcl, --pcl-shear, --xi, --moments, --peaks, --minkowski, --betti, --bispectrum, --smooth, --shape-noise, --starlet, --scattering and --catalogue adds the
 //     lensing outputs computed on device 0 from the finalized planes (driver_lensing.cpp describes them)
 //   * SubFind / halo-catalogue mode (npix == 0) is not supported; with snopt > 0 and several devices every rank thread
 //     draws from its own copy of the libc stream, like the reference's MPI ranks (Ranks::create).

@@ -9,7 +9,8 @@ such maps with the binned absolute sums of its scales, the starlet l1-norm (row 
 maps: coupled bandpowers, the mask's mode-coupling matrix and the decoupled bandpowers (row N17), and the real-space
 two-point correlation functions xi_kk, xi+ and xi- of such maps and of shear maps (row N18), and the Betti numbers of
 such maps' excursion sets as exact counts (row N19), and the wavelet scattering coefficients of such maps (row N20), and
-the E/B pseudo-C_l of masked shear maps: the spin-2 coupling matrices of the mask and the block decoupling (row N21).
+the E/B pseudo-C_l of masked shear maps: the spin-2 coupling matrices of the mask and the block decoupling (row N21), and
+the catalogue of such maps' peaks and minima: positions, heights and sub-pixel offsets (row N22).
 
 plane_weights wraps the host weights of include/slicer_amd.h (slicer_lensing_weights); Kappa is the device accumulator
 (slicer_kappa_*) bound to a Slicer handle: it reads the finalized plane maps where they are, in HBM.  Shear (slicer_shear_*)
@@ -31,7 +32,8 @@ counts the 8-connected components of the sets x >= t_j and the holes in them by 
 (slicer_scattering_*) averages the moduli of a map's Morlet wavelet transforms, and of those moduli's transforms at
 coarser scales; PclShear (slicer_pcl2_*) is Pcl for fields of (gamma1, gamma2) and optionally kappa: it rotates the
 masked spectra to E and B, bins EE, EB, BB and the kappa crosses, and undoes the mask's mixing of E and B with the
-spin-0, spin-2 and spin-4 coupling matrices; spin_phases gives the rotation's tables.
+spin-0, spin-2 and spin-4 coupling matrices; spin_phases gives the rotation's tables; PeakCatalogue
+(slicer_catalogue_*) lists the peaks and minima that Peaks counts, in pixel order, and leaves the records on the device.
 """
 import ctypes as C
 import math
@@ -92,13 +94,13 @@ class _MapRuns:
         if hasattr(self, "last_npix"):
             self.last_npix = self.npix if npix is None else int(npix)
 
-    def run_kappa(self, kappa: "Kappa", s):
-        """The map of source s of a Kappa accumulator, where it is."""
-        self.run(kappa.device_map(s), kappa.npix)
+    def run_kappa(self, kappa: "Kappa", s, **how):
+        """The map of source s of a Kappa accumulator, where it is; `how`: what the class's run takes besides the map."""
+        self.run(kappa.device_map(s), kappa.npix, **how)
 
-    def run_level(self, moments: "Moments", level):
+    def run_level(self, moments: "Moments", level, **how):
         """Level `level` >= 1 of the last run of a Moments pyramid, where it is (level 0 is the caller's own map)."""
-        self.run(moments.device_map(level), moments.npix >> int(level))
+        self.run(moments.device_map(level), moments.npix >> int(level), **how)
 
 
 def _plane_args(ld, ld2, zsnap, sources):
@@ -587,6 +589,64 @@ class Betti(_MapRuns, _SubHandle):
                                           nan.ctypes.data))
         return {"thresholds": self.thresholds.copy(), "components": components, "holes": holes, "faces": faces,
                 "nan": int(nan[0]), "npix": self.last_npix}
+
+
+CATALOGUE_MAX_NPIX = 32768
+CATALOGUE_MAX_CAPACITY = 1 << 29
+CATALOGUE_PEAKS, CATALOGUE_MINIMA = 1, 2    # kinds
+CATALOGUE_MINIMUM, CATALOGUE_FALLBACK = 1, 2  # flags
+# slicer_catalogue_record (_lib.CatalogueRecord): 32 bytes
+CATALOGUE_DTYPE = np.dtype([("row", "<i4"), ("col", "<i4"), ("value", "<f4"), ("flags", "<u4"), ("dy", "<f8"), ("dx", "<f8")])
+
+
+class PeakCatalogue(_MapRuns, _SubHandle):
+    """The peaks and minima of an npix^2 map -- those that Peaks counts -- as records (row, col, value, flags, dy, dx) in
+    ascending row * npix + col, with the sub-pixel offset (dy, dx) of a quadratic fit to the 3 x 3 window, on the device
+    of `slicer`, on its stream.  The handle holds `capacity` records; a run counts every kept
+    peak and minimum and stores the first `capacity` of them.  d_records: the address of a device buffer of the caller's
+    for the records (32 * capacity bytes, on the 16-byte grid) instead of one of the handle's own."""
+    _handle, _destroy = "_ch", "slicer_catalogue_destroy"
+
+    def __init__(self, slicer: Slicer, npix, capacity, d_records=None):
+        self._s = slicer
+        self.npix = int(npix)
+        self.capacity = int(capacity)
+        ch = C.c_void_p()
+        slicer._chk(_L.slicer_catalogue_create(slicer._h, self.npix, self.capacity,
+                                               None if d_records is None else int(d_records), C.byref(ch)))
+        self._ch = ch
+        self.last_npix = None  # of the last run
+
+    def run(self, d_map, npix=None, kinds=CATALOGUE_PEAKS, min_peak=-math.inf, max_minimum=math.inf):
+        """d_map: device address of an f32 map of npix^2 pixels (None: the handle's npix; otherwise at most that).
+        kinds: CATALOGUE_PEAKS | CATALOGUE_MINIMA; a peak is kept iff its value >= min_peak, a minimum iff <= max_minimum."""
+        d = None if d_map is None else int(d_map)
+        self._s._chk(_L.slicer_catalogue_run_npix(self._ch, d, int(kinds), float(min_peak), float(max_minimum),
+                                                  self.npix if npix is None else int(npix)))
+        self.last_npix = self.npix if npix is None else int(npix)
+
+    def counts(self):
+        """dict: peaks, minima (the kept ones of the last run, whatever the capacity), stored, and npix of that run."""
+        n = [C.c_int64() for _ in range(3)]
+        self._s._chk(_L.slicer_catalogue_count(self._ch, *(C.byref(v) for v in n)))
+        return {"peaks": n[0].value, "minima": n[1].value, "stored": n[2].value, "npix": self.last_npix}
+
+    def read(self, max_records=None):
+        """The stored records of the last run (at most max_records of them), a structured array of CATALOGUE_DTYPE."""
+        most = self.capacity if max_records is None else int(max_records)
+        stored = C.c_int64()
+        self._s._chk(_L.slicer_catalogue_count(self._ch, None, None, C.byref(stored)))
+        out = np.empty(max(0, min(most, stored.value)), CATALOGUE_DTYPE)
+        copied = C.c_int64()
+        self._s._chk(_L.slicer_catalogue_read(self._ch, out.ctypes.data if out.size else None, out.size, C.byref(copied)))
+        return out[:copied.value]
+
+    def device_records(self):
+        """(address of the records, address of the int64 {peaks, minima, stored}) of the last run, on the device: valid
+        until the next run or close."""
+        r, c = C.c_void_p(), C.c_void_p()
+        self._s._chk(_L.slicer_catalogue_device(self._ch, C.byref(r), C.byref(c)))
+        return r.value, c.value
 
 
 BISPECTRUM_MAX_BINS = 32
